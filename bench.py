@@ -6,6 +6,7 @@
     python bench.py --model stage2 --shot 5 --batch 8                  stage-1 prior + stage 2, 5-shot, configs[3]
     python bench.py --dataset COCO                                     COCO-20i-shaped episodes, configs[4]
     python bench.py --model baseline --batch 12                        Baseline VGG-16, configs[0]
+    python bench.py ... --dump-outputs DIR                             + what the last timed step computed, DIR/<name>.npy
 
 A "step" is one pass of the hot path over ``--batch`` synthetic episodes already resident in HBM: for eval the device
 work of Evaluator.test_step (encoder, meta-prototype module, cosine map, upsample + argmax + CE + IoU counts; reference
@@ -74,8 +75,15 @@ def parse():
     ap.add_argument("--no-single", action="store_true", help="skip the one-episode-per-step figure")
     ap.add_argument("--no-sides", action="store_true", help="default line: skip the `train` / `stage2_5shot` / `coco` / `baseline_vgg16` objects")
     ap.add_argument("--bf16-side", action="store_true", help="default line: also measure the bf16-operand side figure")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write what the last timed step computed (rank 0's share) as DIR/<name>.npy: eval -> qry_pred (arg-max "
+                         "class per pixel) and stats (ce_sum, n_valid, tp/fp/fn bg, tp/fp/fn fg per episode); train -> loss "
+                         "and weights (the flat parameter buffer after the step)")
     ap.add_argument("--cpu-leg", default="", help=argparse.SUPPRESS)        # internal: "<threads>" -> run one CPU-baseline leg
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 # ---------------------------------------------------------------------------------------------
@@ -1238,6 +1246,8 @@ def main_train(args, world, rank, dev):
         dist.destroy_process_group()
     if rank != 0:
         return
+    if args.dump_outputs:           # before the roofline pass below, which takes more steps
+        dump_outputs(args.dump_outputs, {"loss": ls[-1], "weights": tr.eng.flat.data})
     step_ms = dt / args.steps * 1e3
     out = {
         "metric": "train episodes/sec (PEMP %s train_step, ResNet-50, %d-shot, 401x401)" % ("stage-2" if s2 else "stage-1", args.shot),
@@ -1302,6 +1312,34 @@ def side_train(dev, model="stage1", shot=1, batch=4, steps=10, warmup=4, keep=No
             "last_loss": round(float(ls[-1]), 5),
             "note": "frac = conv + weight-gradient flops of a step / timed step / fp32 MFMA peak; kernel_frac = the same flops / "
                     "the summed durations of those kernels in a single-stream pass"}
+
+
+# ---------------------------------------------------------------------------------------------
+# --dump-outputs: what the timed path computed, so that two builds can be compared output for output
+# ---------------------------------------------------------------------------------------------
+DUMP_LIMIT_BYTES = 60 * 10 ** 6          # array data of one dump; the files stay under 64 MB with their headers
+
+
+def dump_outputs(outdir, arrays):
+    """Write ``arrays`` ({name: tensor or array}) as ``outdir/<name>.npy``: float64 stays float64, every other dtype becomes
+    float32 (exact for class indices).  Smallest array first, each one gets at most an equal share of the DUMP_LIMIT_BYTES
+    still left; an array larger than its share is replaced by a fixed sample of it: the flattened elements at sorted indices
+    drawn without replacement by a generator seeded with 0, the same elements on every run with the same arguments.  A set
+    that fits is written whole."""
+    os.makedirs(outdir, exist_ok=True)
+    out = {}
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+        out[name] = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+    left, n = DUMP_LIMIT_BYTES, len(out)
+    for name in sorted(out, key=lambda k: out[k].nbytes):
+        a = out[name]
+        keep = min(a.size, left // n // a.itemsize)
+        if keep < a.size:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(outdir, name + ".npy"), a)
+        left, n = left - a.nbytes, n - 1
+    print(f"bench.py: wrote {', '.join(f'{k}.npy' for k in out)} to {outdir}", file=sys.stderr)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -1411,7 +1449,7 @@ class EvalRunner:
             st.wait_stream(cur)
         dbg_ev = []
         for i in range(steps):
-            self.step(i)
+            am = self.step(i)
             if os.environ.get("PEMP_BENCH_DEBUG") and self.lane_streams:
                 ev = torch.cuda.Event(enable_timing=True)
                 ev.record(self.lane_streams[i % self.lanes])
@@ -1432,6 +1470,9 @@ class EvalRunner:
                 print("[timed] step completion deltas (ms): " + " ".join(f"{b - a:.2f}" for a, b in zip([0.0] + ends[:-1], ends)), file=sys.stderr)
         local_dt = e_start.elapsed_time(e_steps) * 1e-3
         beat()
+        self.last_outputs = {"qry_pred": am, "stats": self.stats_log[steps - 1]}        # what the last timed step returned
+        if self.aux_log:
+            self.last_outputs["align_loss"] = self.aux_log[-1]
         if world > 1:
             tmax = torch.tensor([dt], dtype=torch.float64, device=dev)
             dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -1527,6 +1568,9 @@ def main():
         raise SystemExit(launch_ranks(args.gpus))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
+    # the training engines seed their DropBlock / Dropout2d Philox stream from torch.initial_seed(): one fixed seed per rank,
+    # so that the same arguments give the same inputs on every run (episodes and weights are seeded already)
+    torch.manual_seed(rank)
     local = int(os.environ.get("LOCAL_RANK", "0"))
     if world != args.gpus and rank == 0:
         print(f"bench.py: --gpus {args.gpus} but the launcher started {world} rank(s); reporting n_gpus = {world}", file=sys.stderr)
@@ -1580,6 +1624,8 @@ def main():
         dist.destroy_process_group()
     if rank != 0:
         return
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, run.last_outputs)
 
     eps_total = args.steps * args.batch * world
     name = "Baseline" if args.model == "baseline" else "PANet" if args.model == "panet" else \

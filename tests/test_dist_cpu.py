@@ -354,6 +354,39 @@ def test_bench_train_stub_roofline_pass_with_collectives_left_on_would_mismatch(
     assert not dist.is_initialized()
 
 
+def test_bench_dump_outputs_hold_the_last_timed_step(tmp_path):
+    """`--dump-outputs DIR` writes what the LAST timed step computed, before the roofline pass takes more steps: the stub's
+    loss counts its calls and every step moves each weight by -0.1, so --warmup 2 --steps 3 leave loss 5 and weights -0.5."""
+    import json
+    r = _run_bench({"PEMP_BENCH_STUB": "1", "PEMP_BENCH_DRYRUN": ""}, "--gpus", "1", "--steps", "3", "--warmup", "2",
+                   "--mode", "train", "--dump-outputs", str(tmp_path))
+    assert r.returncode == 0, r.stderr[-2000:]
+    out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
+    assert out["steps"] == 3 and out["config"]["last_loss"] == 5.0
+    assert "roofline" in out and "error" not in out["roofline"], out.get("roofline")
+    assert sorted(os.listdir(tmp_path)) == ["loss.npy", "weights.npy"]
+    loss, w = np.load(tmp_path / "loss.npy"), np.load(tmp_path / "weights.npy")
+    assert loss.dtype == np.float32 and loss.shape == () and loss == 5.0
+    assert w.dtype == np.float32 and w.shape == (1 << 16,) and np.abs(w + 0.5).max() < 1e-6
+
+
+def test_bench_dump_outputs_sample_what_does_not_fit(tmp_path, monkeypatch):
+    """Over the size limit, small arrays are written whole and the large one as the same seeded sample on every call;
+    float64 stays float64, everything else becomes float32."""
+    import bench
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 4000)
+    arrays = {"big": np.arange(3000, dtype=np.float32), "cls": np.arange(10, dtype=np.uint8), "stats": np.ones((2, 8))}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    got = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in arrays}
+    assert all(np.array_equal(got[k], np.load(tmp_path / "b" / f"{k}.npy")) for k in arrays)
+    assert got["cls"].dtype == np.float32 and np.array_equal(got["cls"], np.arange(10))
+    assert got["stats"].dtype == np.float64 and np.array_equal(got["stats"], arrays["stats"])
+    big = got["big"]
+    assert big.dtype == np.float32 and 0 < big.size < 3000 and len(np.unique(big)) == big.size and (np.diff(big) > 0).all()
+    assert sum(a.nbytes for a in got.values()) <= 4000
+
+
 def test_bench_launcher_watchdog_stops_a_silent_job():
     """A rank that never reaches the collective the others wait in: no heartbeat for PEMP_BENCH_SILENCE_S seconds ->
     the launcher terminates every rank and exits 124."""

@@ -213,3 +213,28 @@ def test_reference_test_step_body_takes_host_tensors(hip_lib, dev):
         p2, l2 = ev.test_step(tuple(x.pin_memory() for x in host), t["qry_mask"])
         assert isinstance(p1, np.ndarray) and p1.shape == (1, 80, 120) and isinstance(l1, float)
         assert np.array_equal(p0, p1) and np.array_equal(p0, p2) and l0 == l1 == l2
+
+
+def test_bench_dump_outputs_are_the_last_timed_step(hip_lib, dev, tmp_path):
+    """``bench.py --dump-outputs``: qry_pred and stats come from the LAST timed step -- its episode group sets the label size,
+    which differs from the first group's -- and from the same step: the tp / fp / fn of every episode recounted from the
+    dumped arg-max against the episode's labels are the dumped statistics."""
+    import os
+    import subprocess
+    import sys
+    import bench
+    steps, batch = 3, 2
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", str(steps), "--warmup", "1", "--batch", str(batch),
+                        "--no-roofline", "--no-single", "--no-e2e", "--no-sides", "--cpu-episodes", "0", "--dump-outputs", str(tmp_path)],
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    pool = bench.episode_pool(torch.device("cpu"), 1, batch, 0)
+    labels = pool[(steps - 1) % len(pool)]["qry_mask"].numpy()
+    assert labels.shape != tuple(pool[0]["qry_mask"].shape)
+    pred, stats = np.load(tmp_path / "qry_pred.npy"), np.load(tmp_path / "stats.npy")
+    assert pred.dtype == np.float32 and pred.shape == labels.shape and set(np.unique(pred)) <= {0.0, 1.0}
+    assert stats.dtype == np.float64 and stats.shape == (batch, 8) and (stats[:, 0] > 0).all()
+    for b in range(batch):
+        assert stats[b, 1] == (labels[b] != 255).sum()
+        assert np.array_equal(stats[b, 2:], util.counts(pred[b], labels[b]).reshape(-1))
