@@ -50,7 +50,8 @@ typedef struct pemp_conv_desc {
                                buffer-addressed kernels; 28 = 32x64 blocks of 16-row wave tiles on
                                v_mfma_f32_16x16x4_f32 (few-row launches: finer granularity); 29 = hybrid of 23
                                and 28 in one grid for launches of a few rounds (other geometries: 23)
-                               -- all bit-identical results; 31..37: split-K forms of 21..27 (see below) */
+                               -- all bit-identical results; 31..37: split-K forms of 21..27 (see below);
+                               41..44, 46 / 51, 52, 54, 56: the split3 family (see pemp_pack_split3_bf16) */
 } pemp_conv_desc;
 
 const char* pemp_last_error(void);
@@ -94,6 +95,18 @@ int pemp_conv2d_hybrid_rows(const pemp_conv_desc* d);
 int pemp_conv2d_group_nhwc_f32(int n, const pemp_conv_desc* d, const float* const* x, const float* const* w,
                                float* const* y, const float* const* scale, const float* const* shift,
                                const float* const* residual, const float* const* pad_value, void* stream);
+
+/* Split3 family (tile ids 41..44, 46 = the shapes of 21..24, 26; 51, 52, 54, 56 = their split-K forms, through the split-K entries and
+ * workspace like 31..36): the same convolution with fp32 operands on v_mfma_f32_32x32x16_bf16.  Every fp32 value is split exactly
+ * into three bf16 pieces h + m + l (round to nearest at each stage); a product is taken as its six pieces' products above one
+ * fp32 rounding (hl, lh, mm, mh, hm, hh), accumulated in fp32: fp32-accurate, not bit-identical to the fp32-chain ids 21..37, and
+ * bit-identical among 41..44, 46 and their grouped launches (ascending K order, fixed product order).  With these ids `w` is NOT the
+ * [Cout][Kpad] fp32 weight but its split form from pemp_pack_split3_bf16.  Entries: pemp_conv2d_nhwc_f32, _padv_, _splitk_,
+ * _padv_splitk_, _group_ (41..44, 46).  Plain epilogue only (no stats / bnbwd / dropblock / bf16 forms); buffer-addressed geometries
+ * only (no stem, <= 32 taps): an error, never a fall-back, elsewhere.
+ * pemp_pack_split3_bf16: [Cout][Kpad] fp32 (Kpad % 32 == 0) -> [Cout][Kpad / 32][3][32] bf16 (Cout * Kpad * 6 bytes): per row and
+ * 32-channel K step the h, m and l planes, channel order unchanged.                                                           */
+int pemp_pack_split3_bf16(const float* w, void* out, int cout, int kpad, void* stream);
 
 /* SIDE-FIGURE VARIANT, not the product path's arithmetic: the same convolution with bf16 OPERANDS (x, w, residual, pad_value:
  * bf16 tensors; descriptor in bf16 elements, Cin % 64 == 0, ldx % 8 == 0) and fp32 accumulation on

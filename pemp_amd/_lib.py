@@ -45,6 +45,7 @@ SYMBOLS = {
     "pemp_conv2d_padv_nhwc_f32": (c_int, [C.POINTER(ConvDesc), c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp]),
     "pemp_conv2d_group_nhwc_f32": (c_int, [c_int, C.POINTER(ConvDesc)] + [C.POINTER(c_fp)] * 7 + [c_fp]),
     "pemp_conv2d_bf16_nhwc": (c_int, [C.POINTER(ConvDesc), c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_fp]),
+    "pemp_pack_split3_bf16": (c_int, [c_fp, c_fp, c_int, c_int, c_fp]),
     "pemp_convert_f32_bf16": (c_int, [c_fp, c_fp, C.c_longlong, c_fp]),
     "pemp_convert_bf16_f32": (c_int, [c_fp, c_fp, C.c_longlong, c_fp]),
     "pemp_conv2d_dropblock_nhwc_f32": (c_int, [C.POINTER(ConvDesc), c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_size, c_fp]),

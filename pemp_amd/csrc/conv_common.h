@@ -27,6 +27,21 @@ __device__ __forceinline__ unsigned int bf16_bits(float f) {
     return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
 }
 
+// x = h + m + l exactly, for the 8 fp32 values of two quads: h = bf16(x), m = bf16(x - h), l = bf16(x - h - m), each rounded to
+// nearest even (the differences are exact in fp32).  The split3 conv kernels (conv_dma2.hip, S3) and pemp_pack_split3_bf16.
+__device__ __forceinline__ void split3_bf16(const v4f& x0, const v4f& x1, bf16x8& h, bf16x8& m, bf16x8& l) {
+    const float x[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const __bf16 he = (__bf16)x[e];
+        const float r = x[e] - (float)he;
+        const __bf16 me = (__bf16)r;
+        h[e] = he;
+        m[e] = me;
+        l[e] = (__bf16)(r - (float)me);
+    }
+}
+
 __device__ __forceinline__ void store_quad(float* base, size_t off, const v4f& o, unsigned bf16) {
     if (!bf16) {
         *(v4f*)(base + off) = o;
@@ -301,5 +316,10 @@ int conv_dma2_tile_rows(int tile);
 struct SplitKPlan { int full, split, pieces; size_t ws_bytes; };
 SplitKPlan conv_dma2_splitk_plan(int tile, const ConvArgs& a);
 int launch_conv_dma2_splitk(int tile, ConvArgs a, void* ws, size_t ws_bytes, hipStream_t st);
+// split3 family (tile ids 41..46, split-K 51..56; a.w = the weights from pemp_pack_split3_bf16): tile = 1..6, split: the
+// split-K form (ws as for launch_conv_dma2_splitk)
+int launch_conv_dma2_split3(int tile, ConvArgs a, void* ws, size_t ws_bytes, bool split, hipStream_t st);
+int launch_conv_dma2_group_split3(int tile, ConvGroupArgs& g, hipStream_t st);
+int pack_split3(const float* w, void* out, int cout, int kpad, hipStream_t st);
 
 }  // namespace pemp

@@ -47,21 +47,36 @@ typedef __attribute__((address_space(3))) void* lptr_t;
 // buys: granularity.  A one-episode step has 5202 output rows; a 256-channel conv is 1304 wave tiles of 32 x 32 on 1024 SIMDs --
 // two rounds, the second 27 % full, 64 % of the chip's MFMA time at best -- and 2608 of 16 x 32 -- three rounds of half the
 // length, 85 %.  It pays twice the LDS reads per flop for that, so it only wins where a launch is a few rounds long.
-template <int BM, int BN, int WGM, int NW, bool PADV, int EPI = 0, bool SK = false, bool BF16 = false, bool DB = false, bool R16 = false>
+// S3 (tile ids 41..46 / 51..56, pemp_hip.h): fp32 operands on the bf16 MFMA pipe.  Every fp32 x is split exactly into three bf16
+// pieces x = h + m + l (round to nearest at each stage: |m| <= 2^-8 |x|, |l| <= 2^-16 |x|); a product a b is taken as the six
+// bf16 x bf16 products whose size is above one fp32 rounding of it (lh, hl, mm, mh, hm, hh -- in that fixed order, smallest
+// first), each exact in the MFMA's fp32 sum.  The activations stay fp32 in memory and in LDS (same DMA, swizzle, tap masks and
+// padding values as the fp32 kernels) and are split in registers after the fragment read; the weights come pre-split
+// (pemp_pack_split3_bf16: per row and 32-channel K step, three 64-byte planes h, m, l), 192 bytes per row and K step in LDS.
+// A K step is two K16 slices of v_mfma_f32_32x32x16_bf16 (lane half lh of slice s: channels 16 s + 8 lh .. + 7); every
+// accumulator sees the slices in ascending K order, so all unsplit S3 variants are bit-identical to each other (not to the
+// fp32-chain variants: a different, equally fp32-accurate, rounding sequence).
+template <int BM, int BN, int WGM, int NW, bool PADV, int EPI = 0, bool SK = false, bool BF16 = false, bool DB = false, bool R16 = false,
+          bool S3 = false>
 __device__ __forceinline__ void conv_dma2_body(const ConvArgs& a, const int bid, const int nblk) {
 #if defined(__HIP_DEVICE_COMPILE__)     // the host pass only needs the launch stub (buffer-resource builtins / "s" asm operands are device-only)
     constexpr int WGN = NW / WGM;
     constexpr int RPI = NW * 8;                 // rows covered by one DMA instruction round of the block
     constexpr int WM = BM / WGM, WN = BN / WGN;
     static_assert(!R16 || (WM == 16 && WN % 16 == 0 && EPI == 0 && !SK && !BF16 && !DB), "R16: 16-row wave tiles, plain epilogue only");
+    static_assert(!S3 || (EPI == 0 && !BF16 && !DB && !R16), "S3: plain epilogue, fp32 operands");
     constexpr int TM = R16 ? 1 : WM / 32, TN = R16 ? WN / 16 : WN / 32;      // R16: TN counts 16-column MFMA tiles
-    constexpr int AL = BM / RPI, BL = BN / RPI; // DMA wave-instructions per thread per K step
-    constexpr int NMF = R16 ? 2 * TN : TM * TN * (BF16 ? 1 : 4), NDS = R16 ? 1 + TN : TM + TN, NDMA = AL + BL;   // per quarter step: MFMAs, fragment reads; DMAs per step
+    constexpr int BQ = S3 ? 12 : 8;             // 16-byte quads of B per row and K step in LDS
+    static_assert(!S3 || (BN * BQ) % (NW * 64) == 0, "S3: whole B DMA rounds");
+    constexpr int AL = BM / RPI, BL = S3 ? BN * BQ / (NW * 64) : BN / RPI; // DMA wave-instructions per thread per K step
+    // per quarter step (S3: per half step): MFMAs, fragment reads; DMAs per step
+    constexpr int NMF = S3 ? 6 * TM * TN : R16 ? 2 * TN : TM * TN * (BF16 ? 1 : 4), NDS = S3 ? 2 * TM + 3 * TN : R16 ? 1 + TN : TM + TN,
+                  NDMA = AL + BL;
     constexpr int PER = (NDS + NDMA + NMF - 1) / NMF;
 
     extern __shared__ __attribute__((aligned(16))) v4f smem[];
     v4f* As = smem;                      // [2][BM][8]
-    v4f* Bs = smem + 2 * BM * 8;         // [2][BN][8]
+    v4f* Bs = smem + 2 * BM * 8;         // [2][BN][BQ]
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -134,7 +149,15 @@ __device__ __forceinline__ void conv_dma2_body(const ConvArgs& a, const int bid,
         a_inv[i] = ~mask;
     }
 #pragma unroll
-    for (int i = 0; i < BL; ++i) b_voff[i] = (unsigned)((n0 + r + RPI * i) * a.Kpad + sq * 4) * 4u;
+    for (int i = 0; i < BL; ++i) {
+        if constexpr (S3) {     // LDS quad q of the tile = row q / 12, position q % 12 = plane * 4 + (quad ^ ((row >> 2) & 3))
+            const int q = i * NW * 64 + tid, row = q / 12, pos = q - row * 12;
+            const int src = (pos & ~3) | ((pos & 3) ^ ((row >> 2) & 3));
+            b_voff[i] = (unsigned)((n0 + row) * a.Kpad * 6 + src * 16);
+        } else {
+            b_voff[i] = (unsigned)((n0 + r + RPI * i) * a.Kpad + sq * 4) * 4u;
+        }
+    }
 
     // wave-uniform K-step state.  Multi-tap convs: channel chunk OUTER, tap INNER (same order as every other conv
     // kernel of the library: variants stay bit-identical); 1x1: chunks in sequence.
@@ -155,9 +178,9 @@ __device__ __forceinline__ void conv_dma2_body(const ConvArgs& a, const int bid,
 #define PEMP_DMA2(buf_)                                                                                           \
     do {                                                                                                          \
         v4f* Ad_ = As + (buf_) * BM * 8 + wave * 64;                                                              \
-        v4f* Bd_ = Bs + (buf_) * BN * 8 + wave * 64;                                                              \
+        v4f* Bd_ = Bs + (buf_) * BN * BQ + wave * 64;                                                             \
         const int sa_ = kh_i * taph + kw_i * tapw + cb * 128;                                                     \
-        const int sb_ = (tap * a.Cin + cb * 32) * 4;                                                              \
+        const int sb_ = (tap * a.Cin + cb * 32) * (S3 ? 6 : 4);                                                   \
         const int sh_ = 31 - tap;                                                                                 \
         const unsigned oob_ = PADV ? padv_off - (unsigned)(kh_i * taph + kw_i * tapw) : 0x80000000u;              \
         _Pragma("unroll") for (int i = 0; i < AL; ++i) {                                                          \
@@ -243,12 +266,25 @@ __device__ __forceinline__ void conv_dma2_body(const ConvArgs& a, const int bid,
     const int rsw16 = (r16 >> 1) & 7;                 // wm0 / wn0 / 16 ni are multiples of 16: the row's swizzle is that of r16
     const int arow16 = (wm0 + r16) * 32 + (g16 >> 1), brow16 = (wn0 + r16) * 32 + (g16 >> 1);     // in floats
     float a16[2][2], b16[2][R16 ? TN : 1][2];
+    // S3: half step j of a lane: fp32 quads 4 j + 2 lh and 4 j + 2 lh + 1 of its A rows, quad 2 j + lh of each weight plane
+    v4f af3[2][S3 ? TM : 1][2], bf3[2][S3 ? TN : 1][3];
+    const int brow3 = (wn0 + lr) * 12, bsw3 = (lr >> 2) & 3;
 
 #define PEMP_READ(dst_, buf_, j_)                                                                                 \
     do {                                                                                                          \
         const v4f* Ab_ = As + (buf_) * BM * 8;                                                                    \
-        const v4f* Bb_ = Bs + (buf_) * BN * 8;                                                                    \
-        if constexpr (R16) {                                                                                      \
+        const v4f* Bb_ = Bs + (buf_) * BN * BQ;                                                                   \
+        if constexpr (S3) {                                                                                       \
+            const int p0_ = (4 * (j_) + 2 * lh) ^ rsw, p1_ = (4 * (j_) + 2 * lh + 1) ^ rsw;                       \
+            const int pb_ = (2 * (j_) + lh) ^ bsw3;                                                               \
+            _Pragma("unroll") for (int mi = 0; mi < TM; ++mi) {                                                   \
+                af3[dst_][mi][0] = Ab_[arow + mi * 256 + p0_];                                                    \
+                af3[dst_][mi][1] = Ab_[arow + mi * 256 + p1_];                                                    \
+            }                                                                                                     \
+            _Pragma("unroll") for (int ni = 0; ni < TN; ++ni)                                                     \
+                _Pragma("unroll") for (int pl = 0; pl < 3; ++pl)                                                  \
+                    bf3[dst_][ni][pl] = Bb_[brow3 + ni * 32 * 12 + pl * 4 + pb_];                                 \
+        } else if constexpr (R16) {                                                                               \
             const int pos_ = ((2 * (j_) + (g16 & 1)) ^ rsw16) * 4;                                                \
             const float* pa_ = (const float*)Ab_ + arow16 + pos_;                                                 \
             a16[dst_][0] = pa_[0];                                                                                \
@@ -267,7 +303,22 @@ __device__ __forceinline__ void conv_dma2_body(const ConvArgs& a, const int bid,
 
 #define PEMP_MMA(src_)                                                                                            \
     do {                                                                                                          \
-        if constexpr (R16) {      /* column tiles interleaved: no MFMA waits for the one in front of it */         \
+        if constexpr (S3) {                                                                                       \
+            bf16x8 ah_[TM], am_[TM], al_[TM];                                                                     \
+            _Pragma("unroll") for (int mi = 0; mi < TM; ++mi)                                                     \
+                split3_bf16(af3[src_][mi][0], af3[src_][mi][1], ah_[mi], am_[mi], al_[mi]);                       \
+            _Pragma("unroll") for (int mi = 0; mi < TM; ++mi) _Pragma("unroll") for (int ni = 0; ni < TN; ++ni) { \
+                const bf16x8 bh_ = __builtin_bit_cast(bf16x8, bf3[src_][ni][0]);                                  \
+                const bf16x8 bm_ = __builtin_bit_cast(bf16x8, bf3[src_][ni][1]);                                  \
+                const bf16x8 bl_ = __builtin_bit_cast(bf16x8, bf3[src_][ni][2]);                                  \
+                acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al_[mi], bh_, acc[mi][ni], 0, 0, 0);        \
+                acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah_[mi], bl_, acc[mi][ni], 0, 0, 0);        \
+                acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am_[mi], bm_, acc[mi][ni], 0, 0, 0);        \
+                acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am_[mi], bh_, acc[mi][ni], 0, 0, 0);        \
+                acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah_[mi], bm_, acc[mi][ni], 0, 0, 0);        \
+                acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah_[mi], bh_, acc[mi][ni], 0, 0, 0);        \
+            }                                                                                                     \
+        } else if constexpr (R16) {      /* column tiles interleaved: no MFMA waits for the one in front of it */  \
             _Pragma("unroll") for (int h_ = 0; h_ < 2; ++h_) _Pragma("unroll") for (int ni = 0; ni < TN; ++ni)    \
                 acc16[ni] = __builtin_amdgcn_mfma_f32_16x16x4f32(a16[src_][h_], b16[src_][ni][h_], acc16[ni], 0, 0, 0); \
         } else                                                                                                    \
@@ -294,14 +345,16 @@ __device__ __forceinline__ void conv_dma2_body(const ConvArgs& a, const int bid,
         __builtin_amdgcn_sched_barrier(0);                                                                        \
         PEMP_MMA(0);                                                                                              \
         __builtin_amdgcn_sched_barrier(0);                                                                        \
-        PEMP_READ(0, buf_, 2);                                                                                    \
-        __builtin_amdgcn_sched_barrier(0);                                                                        \
-        PEMP_MMA(1);                                                                                              \
-        __builtin_amdgcn_sched_barrier(0);                                                                        \
-        PEMP_READ(1, buf_, 3);                                                                                    \
-        __builtin_amdgcn_sched_barrier(0);                                                                        \
-        PEMP_MMA(0);                                                                                              \
-        __builtin_amdgcn_sched_barrier(0);                                                                        \
+        if constexpr (!S3) {            /* S3: two half steps, the first one above */                             \
+            PEMP_READ(0, buf_, 2);                                                                                \
+            __builtin_amdgcn_sched_barrier(0);                                                                    \
+            PEMP_MMA(1);                                                                                          \
+            __builtin_amdgcn_sched_barrier(0);                                                                    \
+            PEMP_READ(1, buf_, 3);                                                                                \
+            __builtin_amdgcn_sched_barrier(0);                                                                    \
+            PEMP_MMA(0);                                                                                          \
+            __builtin_amdgcn_sched_barrier(0);                                                                    \
+        }                                                                                                         \
         /* every LDS read of `buf` by this wave has returned; this wave's DMA pieces of step kt+1 have landed */  \
         __builtin_amdgcn_s_waitcnt(0x0070);          /* vmcnt(0) lgkmcnt(0), visible to hipcc's own wait bookkeeping */ \
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   /* (the LDS-DMA loads are not in that bookkeeping) */    \
@@ -484,9 +537,10 @@ __device__ __forceinline__ void conv_dma2_body(const ConvArgs& a, const int bid,
 #endif
 }
 
-template <int BM, int BN, int WGM, int NW, bool PADV, int EPI = 0, bool SK = false, bool BF16 = false, bool DB = false, bool R16 = false>
+template <int BM, int BN, int WGM, int NW, bool PADV, int EPI = 0, bool SK = false, bool BF16 = false, bool DB = false, bool R16 = false,
+          bool S3 = false>
 __global__ __launch_bounds__(NW * 64) void conv_dma2_kernel(ConvArgs a) {
-    conv_dma2_body<BM, BN, WGM, NW, PADV, EPI, SK, BF16, DB, R16>(a, blockIdx.x, gridDim.x);
+    conv_dma2_body<BM, BN, WGM, NW, PADV, EPI, SK, BF16, DB, R16, S3>(a, blockIdx.x, gridDim.x);
 }
 
 // Several INDEPENDENT convs of the same tile shape in ONE launch: member i owns the blocks [first[i], first[i] + nblk[i]) (the
@@ -495,20 +549,20 @@ __global__ __launch_bounds__(NW * 64) void conv_dma2_kernel(ConvArgs a) {
 // CUs -- and convs that do not depend on each other (the dilated ASPP branches; a stage's downsample conv beside its conv1):
 // together they fill the chip without splitting K and without one launch + drain per member.  Same tiles, same K order: every
 // member's result is bit-identical to its own launch.
-template <int BM, int BN, int WGM, int NW, bool PADV, bool R16 = false>
+template <int BM, int BN, int WGM, int NW, bool PADV, bool R16 = false, bool S3 = false>
 __global__ __launch_bounds__(NW * 64) void conv_dma2_group_kernel(ConvGroupArgs g) {
     int which = 0;
 #pragma unroll
     for (int i = 1; i < CONV_GROUP_MAX; ++i) which += (i < g.n && (int)blockIdx.x >= g.first[i]) ? 1 : 0;
     const int bid = (int)blockIdx.x - g.first[which];
     if (bid >= g.nblk[which]) return;
-    conv_dma2_body<BM, BN, WGM, NW, PADV, 0, false, false, false, R16>(g.a[which], bid, g.nblk[which]);
+    conv_dma2_body<BM, BN, WGM, NW, PADV, 0, false, false, false, R16, S3>(g.a[which], bid, g.nblk[which]);
 }
 
-template <int BM, int BN, int WGM, int NW, bool R16 = false>
+template <int BM, int BN, int WGM, int NW, bool R16 = false, bool S3 = false>
 static int launch_dma2_group(ConvGroupArgs& g, bool padv, hipStream_t st) {
-    const size_t lds = (size_t)2 * 8 * (BM + BN) * sizeof(v4f);
-    auto kern = padv ? conv_dma2_group_kernel<BM, BN, WGM, NW, true, R16> : conv_dma2_group_kernel<BM, BN, WGM, NW, false, R16>;
+    const size_t lds = (size_t)2 * (8 * BM + (S3 ? 12 : 8) * BN) * sizeof(v4f);
+    auto kern = padv ? conv_dma2_group_kernel<BM, BN, WGM, NW, true, R16, S3> : conv_dma2_group_kernel<BM, BN, WGM, NW, false, R16, S3>;
     if (lds > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) {
@@ -760,6 +814,90 @@ int launch_conv_dma2_splitk(int tile, ConvArgs a, void* ws, size_t ws_bytes, hip
     if (tile == 5) return launch_dma2_sk<128, 64, 4, 8>(a, grid, st);
     if (tile == 1) return launch_dma2_sk<128, 128, 2, 4>(a, grid, st);
     return launch_dma2_sk<128, 64, 2, 4>(a, grid, st);
+}
+
+// ---- split3 family: the S3 body on the shapes of tiles 1..4 and 6 (tile 5, 128 x 64 in 8 waves, has no whole B DMA rounds at
+// 192 bytes per row; tile 7, 256 x 256, would need all 160 KiB of LDS) ----
+template <int BM, int BN, int WGM, int NW, bool SK>
+static int launch_dma2_s3(const ConvArgs& a, int grid, hipStream_t st) {
+    const size_t lds = (size_t)2 * (8 * BM + 12 * BN) * sizeof(v4f);
+    auto kern = a.padv ? conv_dma2_kernel<BM, BN, WGM, NW, true, 0, SK, false, false, false, true>
+                       : conv_dma2_kernel<BM, BN, WGM, NW, false, 0, SK, false, false, false, true>;
+    if (lds > 64 * 1024) {
+        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) {
+            set_error("hipFuncSetAttribute(lds=%zu): %s", lds, hipGetErrorString(e));
+            return (int)e;
+        }
+    }
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), lds, st, a);
+    return launch_status(SK ? "conv_dma2/split3/splitk" : "conv_dma2/split3");
+}
+
+template <bool SK>
+static int launch_s3_tile(int tile, const ConvArgs& a, int grid, hipStream_t st) {
+    if (tile == 6) return launch_dma2_s3<256, 128, 4, 8, SK>(a, grid, st);
+    if (tile == 4) return launch_dma2_s3<128, 128, 4, 8, SK>(a, grid, st);
+    if (tile == 1) return launch_dma2_s3<128, 128, 2, 4, SK>(a, grid, st);
+    if (tile == 2) return launch_dma2_s3<128, 64, 2, 4, SK>(a, grid, st);
+    return launch_dma2_s3<64, 64, 2, 4, SK>(a, grid, st);
+}
+
+int launch_conv_dma2_split3(int tile, ConvArgs a, void* ws, size_t ws_bytes, bool split, hipStream_t st) {
+    if (tile < 1 || tile > 6 || tile == 5 || a.stats || a.rowmask || (a.flags & PEMP_CONV_BF16_IO)) {
+        set_error("conv split3: tile %d / epilogue outside the family", tile);
+        return -1;
+    }
+    int bm, bn;
+    tile_shape(tile, bm, bn);
+    if (split) {
+        const SplitKPlan p = conv_dma2_splitk_plan(tile, a);
+        if (p.pieces >= 2) {
+            if (!ws || ws_bytes < p.ws_bytes || ((uintptr_t)ws & 15)) {
+                set_error("conv split-K: workspace of %zu bytes needed (16-byte aligned), got %zu", p.ws_bytes, ws_bytes);
+                return -1;
+            }
+            a.sk_cnt = (int*)ws;
+            a.sk_ws = (float*)((char*)ws + 1024);
+            a.sk_full = p.full;
+            a.sk_S = p.pieces;
+            return launch_s3_tile<true>(tile, a, p.full + p.split * p.pieces, st);
+        }
+    }
+    return launch_s3_tile<false>(tile, a, cdiv(a.M, bm) * (a.Cout / bn), st);
+}
+
+int launch_conv_dma2_group_split3(int tile, ConvGroupArgs& g, hipStream_t st) {
+    if (tile == 5) {
+        set_error("conv split3: no 128 x 64 8-wave form");
+        return -1;
+    }
+    const bool padv = g.a[0].padv != nullptr;
+    if (tile == 6) return launch_dma2_group<256, 128, 4, 8, false, true>(g, padv, st);
+    if (tile == 4) return launch_dma2_group<128, 128, 4, 8, false, true>(g, padv, st);
+    if (tile == 1) return launch_dma2_group<128, 128, 2, 4, false, true>(g, padv, st);
+    if (tile == 2) return launch_dma2_group<128, 64, 2, 4, false, true>(g, padv, st);
+    return launch_dma2_group<64, 64, 2, 4, false, true>(g, padv, st);
+}
+
+// [Cout][Kpad] fp32 -> [Cout][Kpad / 32][3][32] bf16: per row and 32-channel K step the h, m and l planes of split3_bf16
+__global__ __launch_bounds__(256) void pack_split3_kernel(const float* __restrict__ w, unsigned short* __restrict__ out, long long n8) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;      // one 8-channel octet (= one quad of each plane)
+    if (i >= n8) return;
+    const v4f x0 = *(const v4f*)(w + i * 8), x1 = *(const v4f*)(w + i * 8 + 4);
+    bf16x8 h, m, l;
+    split3_bf16(x0, x1, h, m, l);
+    const long long step = i >> 2;                   // (row, K step): 4 octets each
+    unsigned short* o = out + step * 96 + (i & 3) * 8;
+    *(bf16x8*)o = h;
+    *(bf16x8*)(o + 32) = m;
+    *(bf16x8*)(o + 64) = l;
+}
+
+int pack_split3(const float* w, void* out, int cout, int kpad, hipStream_t st) {
+    const long long n8 = (long long)cout * kpad / 8;
+    hipLaunchKernelGGL(pack_split3_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, st, w, (unsigned short*)out, n8);
+    return launch_status("pack_split3");
 }
 
 // true when the geometry / operands fit this variant (the caller falls back to conv_dma.hip otherwise)

@@ -265,7 +265,8 @@ static int conv2d_impl(const pemp_conv_desc* d, const float* x, const float* w, 
 extern "C" int pemp_conv2d_padv_nhwc_f32(const pemp_conv_desc* d, const float* x, const float* w, float* y,
                                          const float* scale, const float* shift, const float* residual,
                                          const float* pad_value, void* stream) {
-    PEMP_REQUIRE(!d || d->tile < 31 || d->tile > 37, "conv2d: the split-K tile ids 31..37 need pemp_conv2d_splitk_nhwc_f32 (workspace)");
+    PEMP_REQUIRE(!d || ((d->tile < 31 || d->tile > 37) && (d->tile < 51 || d->tile > 56)),
+                 "conv2d: the split-K tile ids 31..37 / 51..56 need pemp_conv2d_splitk_nhwc_f32 (workspace)");
     return conv2d_impl(d, x, w, y, scale, shift, residual, pad_value, nullptr, 0, stream);
 }
 
@@ -343,6 +344,15 @@ static int conv2d_impl(const pemp_conv_desc* d, const float* x, const float* w, 
         tile = 3;
     }
     hipStream_t st = (hipStream_t)stream;
+    if ((tile >= 41 && tile <= 46) || (tile >= 51 && tile <= 56)) {     // split3 family (conv_dma2.hip, S3): w from pemp_pack_split3_bf16
+        PEMP_REQUIRE(tile != 53, "conv2d: no split-K variant of the 64 x 64 tile");
+        PEMP_REQUIRE(tile != 45 && tile != 55, "conv2d: no split3 form of the 128 x 64 8-wave tile");
+        PEMP_REQUIRE(!stem && conv_dma2_supported(a) && (long long)a.Cout * a.Kpad * 6 < (1ll << 31),
+                     "conv2d: split3 tile %d needs a geometry of the buffer-addressed kernels (no stem, <= 32 taps, operands < 2 GiB)", tile);
+        const int t = tile > 50 ? tile - 50 : tile - 40;
+        PEMP_REQUIRE((t != 1 && t != 4 && t != 6) || a.Cout % 128 == 0, "conv2d: tile N=128 needs Cout %% 128 == 0");
+        return launch_conv_dma2_split3(t, a, ws, ws_bytes, tile > 50, st);
+    }
     if (tile >= 31 && tile <= 37) {      // conv_dma2.hip with the last round of tiles split along K (pemp_hip.h)
         PEMP_REQUIRE(tile != 33, "conv2d: no split-K variant of the 64 x 64 tile");
         if (conv_dma2_supported(a)) {
@@ -393,8 +403,9 @@ extern "C" int pemp_conv2d_group_nhwc_f32(int n, const pemp_conv_desc* d, const 
     ConvGroupArgs g;
     g.n = n;
     const int tile = d[0].tile;
-    PEMP_REQUIRE(tile >= 21 && tile <= 28, "conv2d_group: tile must be one of the buffer-addressed variants 21..28, got %d", tile);
-    const int t = tile - 20;
+    const bool s3 = tile >= 41 && tile <= 46 && tile != 45;
+    PEMP_REQUIRE((tile >= 21 && tile <= 28) || s3, "conv2d_group: tile must be one of the buffer-addressed variants 21..28 or 41..44, 46, got %d", tile);
+    const int t = s3 ? tile - 40 : tile - 20;
     for (int i = 0; i < n; ++i) {
         PEMP_REQUIRE(d[i].tile == tile, "conv2d_group: every member must name the same tile variant");
         PEMP_REQUIRE(!pad_value || (pad_value[i] != nullptr) == (pad_value[0] != nullptr), "conv2d_group: pad_value for every member or for none");
@@ -404,6 +415,7 @@ extern "C" int pemp_conv2d_group_nhwc_f32(int n, const pemp_conv_desc* d, const 
         PEMP_REQUIRE(conv_dma2_supported(g.a[i]), "conv2d_group: member %d lies outside the buffer-addressed kernels (stem / > 32 taps / 2 GiB operands / padding vector not behind the activations)", i);
         PEMP_REQUIRE((t != 1 && t != 4 && t != 6) || g.a[i].Cout % 128 == 0, "conv2d_group: tile N=128 needs Cout %% 128 == 0");
         PEMP_REQUIRE(t != 7 || g.a[i].Cout % 256 == 0, "conv2d_group: tile 256x256 needs Cout %% 256 == 0");
+        PEMP_REQUIRE(!s3 || (long long)g.a[i].Cout * g.a[i].Kpad * 6 < (1ll << 31), "conv2d_group: split3 weights of 2 GiB or more");
     }
     // members run beside each other in one grid: no member may write what another one writes or reads.  Two tensors that interleave
     // in one buffer (the ASPP branches write channel slices of the concat buffer: equal per-pixel stride, disjoint channel windows)
@@ -431,7 +443,13 @@ extern "C" int pemp_conv2d_group_nhwc_f32(int n, const pemp_conv_desc* d, const 
         }
     }
     for (int i = n; i < CONV_GROUP_MAX; ++i) g.a[i] = g.a[0];
-    return launch_conv_dma2_group(t, g, (hipStream_t)stream);
+    return s3 ? launch_conv_dma2_group_split3(t, g, (hipStream_t)stream) : launch_conv_dma2_group(t, g, (hipStream_t)stream);
+}
+
+extern "C" int pemp_pack_split3_bf16(const float* w, void* out, int cout, int kpad, void* stream) {
+    PEMP_REQUIRE(w && out && cout > 0 && kpad > 0 && kpad % 32 == 0, "pack_split3: null pointer or Kpad not a multiple of 32");
+    PEMP_REQUIRE((((uintptr_t)w | (uintptr_t)out) & 15) == 0, "pack_split3: pointers must be 16-byte aligned");
+    return pack_split3(w, out, cout, kpad, (hipStream_t)stream);
 }
 
 
@@ -538,12 +556,14 @@ extern "C" int pemp_conv2d_stats_rows(const pemp_conv_desc* d) {
 }
 
 extern "C" size_t pemp_conv2d_splitk_workspace_bytes(const pemp_conv_desc* d) {
-    if (!d || d->tile < 31 || d->tile > 37 || d->tile == 33 || d->N <= 0 || d->Ho <= 0 || d->Wo <= 0 || d->Cout <= 0 || d->Kpad < 32) return 0;
+    const int t = d ? (d->tile > 50 ? d->tile - 50 : d->tile - 30) : 0;     // 31..37: fp32 chain; 51..56: split3 (same plan)
+    if (!d || t < 1 || t > 7 || t == 3 || (d->tile > 50 && (t == 5 || t > 6)) || (d->tile > 37 && d->tile < 51) || d->N <= 0 || d->Ho <= 0 ||
+        d->Wo <= 0 || d->Cout <= 0 || d->Kpad < 32) return 0;
     ConvArgs a;
     a.M = d->N * d->Ho * d->Wo;
     a.Cout = d->Cout;
     a.nk = d->Kpad / 32;
-    return conv_dma2_splitk_plan(d->tile - 30, a).ws_bytes;
+    return conv_dma2_splitk_plan(t, a).ws_bytes;
 }
 
 extern "C" int pemp_conv2d_stats_nhwc_f32(const pemp_conv_desc* d, const float* x, const float* w, float* y, float* stats,

@@ -16,6 +16,20 @@ from .ops import ConvParams
 
 BN_EPS = 1e-5
 
+#: The inference engines' convs run on the split3 family (ops.SPLIT3_TILES: fp32 operands as three bf16 pieces on the bf16 MFMA
+#: pipe, fp32-accurate) wherever the layer's geometry admits it; False: the fp32-chain kernels.  Read when an engine is built
+#: (the models' ``precision("f32_chain")`` builds one with it off).  PEMP_SPLIT3=0 switches the default off.
+SPLIT3 = os.environ.get("PEMP_SPLIT3", "1") != "0"
+
+
+def with_split3(cp):
+    """Attach the split form of the weights (ConvParams.w3) to an fp32 layer whose geometry the split3 kernels take (no stem,
+    <= 32 taps, Cin % 32, Cout % 64) when SPLIT3 is on; the stem and every other layer stay on the fp32 chain."""
+    if (SPLIT3 and not cp.stem and cp.w.dtype == torch.float32 and cp.kh * cp.kw <= 32 and cp.cin % 32 == 0
+            and cp.cout % 64 == 0 and cp.kpad == cp.kh * cp.kw * cp.cin):
+        cp.w3 = ops.pack_split3(cp.w)
+    return cp
+
 
 def bn_affine(bn):
     """(alpha, beta) of an eval-mode BatchNorm2d, fp32, on the BN's device."""
@@ -40,8 +54,8 @@ def conv_params(conv, bn=None, relu=False, stem4=False, in_slice=None, dtype=tor
             shift = shift + conv.bias.detach().float() * scale
     elif conv.bias is not None:
         shift = conv.bias.detach().float().contiguous()
-    return ConvParams(packed.contiguous().to(dtype), scale, shift, 4 if stem4 else cin, cout, conv.kernel_size[0],
-                      conv.kernel_size[1], conv.stride[0], conv.padding[0], conv.dilation[0], kpad, stem4, relu)
+    return with_split3(ConvParams(packed.contiguous().to(dtype), scale, shift, 4 if stem4 else cin, cout, conv.kernel_size[0],
+                                  conv.kernel_size[1], conv.stride[0], conv.padding[0], conv.dilation[0], kpad, stem4, relu))
 
 
 #: Steps of at most this many feature rows (one or two episodes: 5202 rows per 1-shot episode) issue their INDEPENDENT convs
@@ -222,8 +236,8 @@ class VGG16CMEngine:
         wp = torch.zeros((co, kh, kw, ci - 2 + self.PADC), dtype=torch.float32, device=w.device)
         wp[..., :ci] = w.permute(0, 2, 3, 1)
         cin = ci - 2 + self.PADC
-        return ConvParams(wp.reshape(co, kh * kw * cin).contiguous(), None, conv.bias.detach().float().contiguous(), cin, co,
-                          kh, kw, 1, conv.padding[0], conv.dilation[0], kh * kw * cin, False, relu)
+        return with_split3(ConvParams(wp.reshape(co, kh * kw * cin).contiguous(), None, conv.bias.detach().float().contiguous(),
+                                      cin, co, kh, kw, 1, conv.padding[0], conv.dilation[0], kh * kw * cin, False, relu))
 
     def forward(self, x4, prior):
         """x4: NHWC4 input (RGB + prior); prior: [N,H,W] fp32 mask plane -> NHWC features [N,h,w,512]."""

@@ -88,7 +88,12 @@ class _HeadMixin:
         if eng is None or eng["device"] != device:
             arena = engine.Arena(device, torch.bfloat16 if prec == "bf16" else torch.float32)
             eng = {"device": device, "arena": arena}
-            self._build_engine(eng, arena)
+            split3 = engine.SPLIT3
+            engine.SPLIT3 = split3 and prec == "f32"       # "f32_chain" / "bf16": every conv on the fp32-chain kernels
+            try:
+                self._build_engine(eng, arena)
+            finally:
+                engine.SPLIT3 = split3
             engines[key] = eng
         if key == 0:
             self.__dict__["_engine"] = eng
@@ -98,9 +103,10 @@ class _HeadMixin:
         """Context manager: ``with model.precision("bf16"):`` runs the enclosed inference calls on the bf16-OPERAND variant of the
         encoder (bf16 activations and weights between the fp32 stem and the fp32 head, fp32 accumulation) -- the side figure of
         bench.py that shows what exact fp32 costs; stage-1 ResNet encoders only.  The default, and everything the parity
-        tests hold, is "f32"."""
-        if prec not in ("f32", "bf16"):
-            raise ValueError(f"precision must be 'f32' or 'bf16', got {prec!r}")
+        tests hold, is "f32" (its convs on the split3 family where engine.SPLIT3 is on); "f32_chain" runs the same fp32 encoder on the
+        fp32-chain conv kernels (A/B runs and tests)."""
+        if prec not in ("f32", "bf16", "f32_chain"):
+            raise ValueError(f"precision must be 'f32', 'f32_chain' or 'bf16', got {prec!r}")
         if prec == "bf16" and not (getattr(self, "_bf16_variant", False) and getattr(self, "backbone_name", "") != "vgg16"):
             raise ValueError("the bf16 variant exists for the stage-1 ResNet encoders only")
         model = self

@@ -53,10 +53,11 @@ def conv_out_size(i, k, s, p, d):
 
 class ConvParams:
     """Device-resident, pre-packed parameters of one conv (+ folded per-channel affine)."""
-    __slots__ = ("w", "scale", "shift", "cin", "cout", "kh", "kw", "stride", "pad", "dil", "kpad", "stem", "relu")
+    __slots__ = ("w", "scale", "shift", "cin", "cout", "kh", "kw", "stride", "pad", "dil", "kpad", "stem", "relu", "w3")
 
-    def __init__(self, w, scale, shift, cin, cout, kh, kw, stride, pad, dil, kpad, stem, relu):
-        self.w, self.scale, self.shift = w, scale, shift
+    def __init__(self, w, scale, shift, cin, cout, kh, kw, stride, pad, dil, kpad, stem, relu, w3=None):
+        # w3: the split form of w (pack_split3) -- when present, conv2d / conv2d_group run the split3 family (tile ids 41..56)
+        self.w, self.scale, self.shift, self.w3 = w, scale, shift, w3
         self.cin, self.cout, self.kh, self.kw = cin, cout, kh, kw
         self.stride, self.pad, self.dil, self.kpad, self.stem, self.relu = stride, pad, dil, kpad, stem, relu
 
@@ -73,6 +74,12 @@ TILE_VARIANTS = {13: (64, 64), 14: (128, 128), 12: (128, 64), 11: (128, 128), 15
                  # 29: hybrid launch for convs of a few rounds -- the rows that fill whole rounds of the chip on the 64 x 64 tile, the
                  # remaining rows on 16-row wave tiles, one grid (csrc/conv_dma2.hip); other geometries run as 23
                  29: (64, 64)}
+#: the split3 family (pemp_hip.h: fp32 operands split into three bf16 pieces on v_mfma_f32_32x32x16_bf16, fp32 accuracy; the
+#: shapes of 21..24 / 26): the variants of a layer that carries split weights (ConvParams.w3) -- bit-identical among themselves,
+#: not to the fp32-chain ids above.  51..56: their split-K forms (EVAL_SPLITK).
+SPLIT3_TILES = (43, 42, 41, 44, 46)
+SPLIT3_SPLITK_TILES = (51, 52, 54, 56)
+SPLIT3_DEFAULT_TILE = 43
 AUTOTUNE = True
 #: test hook: ``PICK_HOOK(kind, cands, key) -> one of cands`` decides every kernel-variant pick INSTEAD of timing (kind "conv":
 #: tile ids, "wgrad": block counts / (tile kind, block count) pairs), at any problem size.  Timing-based picks differ from box
@@ -176,7 +183,7 @@ def _pick_tile(launch, p, key, cout, only=None):
     if only is None:
         cands = [t for t, (bm, bn) in TILE_VARIANTS.items() if cout % bn == 0]
     else:
-        cands = [t for t in only if cout % TILE_VARIANTS[t - 10 if t > 30 else t][1] == 0]
+        cands = [t for t in only if cout % _tile_bn(t) == 0]
     if PICK_HOOK is not None:
         best = PICK_HOOK("conv", list(cands), key)
         if best not in cands:
@@ -203,6 +210,22 @@ def _pick_tile(launch, p, key, cout, only=None):
     _TILE_CACHE[key] = best
     save_picks()
     return best
+
+
+def _tile_bn(t):
+    """BN of tile id ``t``: the split-K ids (31..37, 51..56) and the split3 ids (41..46) have the shapes of 21..27."""
+    return TILE_VARIANTS[t - 30 if t > 50 else t - 20 if t > 40 else t - 10 if t > 30 else t][1]
+
+
+def pack_split3(w):
+    """KRSC [Cout, Kpad] fp32 (Kpad % 32 == 0) -> its split3 form (pemp_pack_split3_bf16): bf16 [Cout, Kpad / 32, 3, 32], per row
+    and 32-channel K step the planes h, m, l with w == h + m + l exactly."""
+    co, kpad = w.shape
+    if w.dtype != torch.float32 or not w.is_contiguous() or kpad % 32:
+        raise ValueError("pack_split3: a contiguous fp32 [Cout, Kpad] with Kpad % 32 == 0")
+    out = torch.empty((co, kpad // 32, 3, 32), dtype=torch.bfloat16, device=w.device)
+    _lib.check(_lib.load().pemp_pack_split3_bf16(_p(w), _p(out), co, kpad, _stream()), "pemp_pack_split3_bf16")
+    return out
 
 
 def hybrid_rows(n, ho, wo, cout):
@@ -269,6 +292,10 @@ def conv2d(x, p, out=None, residual=None, shift_override=None, per_image_shift=F
     if p.stem:
         flags |= CONV_STEM4
     splitk = ((splitk and SPLITK) or (EVAL_SPLITK and n * ho * wo <= EVAL_SPLITK_MAX_ROWS)) and not p.stem
+    # split3: the layer carries split weights (inference engines; the layer's geometry decided it) and plain epilogue.  A call
+    # outside the buffer-addressed kernels (an input of 2 GiB or more; a padding vector that does not sit far enough behind a
+    # small map under a large dilation) runs the fp32 chain, whose pointer-addressed fall-back takes it
+    s3 = p.w3 is not None and dropblock is None and dma2_supported(x, p) and _group_member_ok(x, p, pad_value)
 
     if dropblock is not None:
         dmask, dcnt = dropblock
@@ -283,32 +310,36 @@ def conv2d(x, p, out=None, residual=None, shift_override=None, per_image_shift=F
 
     def launch(t):
         d = ConvDesc(n, h, w, cin, ldx, ho, wo, p.cout, ldy, p.kh, p.kw, p.stride, p.pad, p.dil, ldr, p.kpad, flags, t)
+        pw = p.w3 if t > 40 else p.w
         if dropblock is not None:
             ws, ws_bytes = _splitk_ws(lib, d, x.device) if t > 30 else (None, 0)
-            _check_sk(lib, lib.pemp_conv2d_dropblock_nhwc_f32(C.byref(d), _p(x), _p(p.w), _p(out), _p(p.scale), _p(shift), _p(residual),
+            _check_sk(lib, lib.pemp_conv2d_dropblock_nhwc_f32(C.byref(d), _p(x), _p(pw), _p(out), _p(p.scale), _p(shift), _p(residual),
                                                               _p(dropblock[0]), _p(dropblock[1]), C.c_void_p(ws), ws_bytes, _stream()),
                       ws, "pemp_conv2d_dropblock_nhwc_f32")
             return
         if t > 30 and pad_value is not None:
             ws, ws_bytes = _splitk_ws(lib, d, x.device)
-            _check_sk(lib, lib.pemp_conv2d_padv_splitk_nhwc_f32(C.byref(d), _p(x), _p(p.w), _p(out), _p(p.scale), _p(shift), _p(residual),
+            _check_sk(lib, lib.pemp_conv2d_padv_splitk_nhwc_f32(C.byref(d), _p(x), _p(pw), _p(out), _p(p.scale), _p(shift), _p(residual),
                                                                 _p(pad_value), C.c_void_p(ws), ws_bytes, _stream()), ws,
                       "pemp_conv2d_padv_splitk_nhwc_f32")
         elif t > 30:
             ws, ws_bytes = _splitk_ws(lib, d, x.device)
-            _check_sk(lib, lib.pemp_conv2d_splitk_nhwc_f32(C.byref(d), _p(x), _p(p.w), _p(out), _p(p.scale), _p(shift), _p(residual),
+            _check_sk(lib, lib.pemp_conv2d_splitk_nhwc_f32(C.byref(d), _p(x), _p(pw), _p(out), _p(p.scale), _p(shift), _p(residual),
                                                            C.c_void_p(ws), ws_bytes, _stream()), ws, "pemp_conv2d_splitk_nhwc_f32")
         elif pad_value is None:
-            _lib.check(lib.pemp_conv2d_nhwc_f32(C.byref(d), _p(x), _p(p.w), _p(out), _p(p.scale), _p(shift),
+            _lib.check(lib.pemp_conv2d_nhwc_f32(C.byref(d), _p(x), _p(pw), _p(out), _p(p.scale), _p(shift),
                                                 _p(residual), _stream()), "pemp_conv2d_nhwc_f32")
         else:
-            _lib.check(lib.pemp_conv2d_padv_nhwc_f32(C.byref(d), _p(x), _p(p.w), _p(out), _p(p.scale), _p(shift),
+            _lib.check(lib.pemp_conv2d_padv_nhwc_f32(C.byref(d), _p(x), _p(pw), _p(out), _p(p.scale), _p(shift),
                                                      _p(residual), _p(pad_value), _stream()), "pemp_conv2d_padv_nhwc_f32")
 
     if tile == 0:
         key = (p.cin, p.cout, p.kh, p.kw, p.stride, p.pad, p.dil, (6 if dropblock is not None else 4) if splitk else int(p.stem) + (7 if dropblock is not None else 0),
-               n, h, w, int(residual is not None), int(pad_value is not None))
+               n, h, w, int(residual is not None), int(pad_value is not None)) + ((3,) if s3 else ())    # 3: split3 picks
         tile = _TILE_CACHE.get(key)
+        if tile is None and s3:
+            only = list(SPLIT3_TILES) + (list(SPLIT3_SPLITK_TILES) if splitk else [])
+            tile = _pick_tile(launch, p, key, p.cout, only=only) if _tunes(n * ho * wo) else SPLIT3_DEFAULT_TILE
         if tile is None:
             if dropblock is not None:
                 only = list(GROUP_TILES) + (list(SPLITK_TILES) if splitk else [])
@@ -439,14 +470,16 @@ def conv2d_group(xs, ps, outs, pad_values=None, residuals=None, tile=0):
                 raise ValueError("conv2d_group: residual shape mismatch")
         descs.append((nb, h, w, cin, ldx, ho, wo, p.cout, ldy, p.kh, p.kw, p.stride, p.pad, p.dil, ldr, p.kpad, CONV_RELU if p.relu else 0))
         keys += [p.cin, p.cout, p.kh, p.stride, p.pad, p.dil, nb, h, w, int(res is not None), int(pv is not None)]
-    if not all(_group_member_ok(x, p, pv) for x, p, pv in zip(xs, ps, pad_values)):
+    s3 = all(p.w3 is not None for p in ps)
+    if not all(_group_member_ok(x, p, pv) for x, p, pv in zip(xs, ps, pad_values)) or (not s3 and any(p.w3 is not None for p in ps)):
         # a member outside the buffer-addressed kernels (tiny maps under a large dilation: the padding vector is not far enough
-        # behind the activations; 2 GiB operands; > 32 taps): every member through its own launch -- same results
+        # behind the activations; 2 GiB operands; > 32 taps), or members of both the split3 and the fp32-chain family: every member
+        # through its own launch -- same results
         for x, p, out, pv, res in zip(xs, ps, outs, pad_values, residuals):
             conv2d(x, p, out=out, residual=res, pad_value=pv if p.kh * p.kw > 1 else None)
         return outs
     arr = lambda ts: (C.c_void_p * n)(*[(t.data_ptr() if t is not None else None) for t in ts])
-    xa, wa, ya = arr(xs), arr([p.w for p in ps]), arr(outs)
+    xa, wa, ya = arr(xs), arr([p.w3 if s3 else p.w for p in ps]), arr(outs)
     sa, ha, ra, pa = arr([p.scale for p in ps]), arr([p.shift for p in ps]), arr(residuals), arr(pad_values)
     ptr = lambda a: C.cast(a, C.POINTER(C.c_void_p))
 
@@ -456,8 +489,13 @@ def conv2d_group(xs, ps, outs, pad_values=None, residuals=None, tile=0):
                    "pemp_conv2d_group_nhwc_f32")
 
     if tile == 0:
-        key = (-7,) + tuple(keys)               # -7: a grouped launch (the cache file stores keys as integer lists)
+        key = (-8 if s3 else -7,) + tuple(keys)     # -7: a grouped launch, -8: of the split3 family (the cache file stores keys as integer lists)
         tile = _TILE_CACHE.get(key)
+        if tile is None and s3:
+            tile = SPLIT3_DEFAULT_TILE
+            if _tunes(max(d[0] * d[5] * d[6] for d in descs)):
+                tile = _pick_tile(launch, None, key, min(p.cout for p in ps),
+                                  only=[t for t in SPLIT3_TILES if all(p.cout % _tile_bn(t) == 0 for p in ps)])
         if tile is None:
             if _tunes(max(d[0] * d[5] * d[6] for d in descs)):
                 tile = _pick_tile(launch, None, key, min(p.cout for p in ps),
@@ -661,7 +699,8 @@ def fold_input_affine(p, s, t):
     if p.shift is not None:
         shift = shift + p.shift
     wf = (w * s.view(1, 1, -1)).reshape(p.cout, taps * p.cin).contiguous()
-    q = ConvParams(wf, None, shift.contiguous(), p.cin, p.cout, p.kh, p.kw, p.stride, p.pad, p.dil, p.kpad, False, p.relu)
+    q = ConvParams(wf, None, shift.contiguous(), p.cin, p.cout, p.kh, p.kw, p.stride, p.pad, p.dil, p.kpad, False, p.relu,
+                   pack_split3(wf) if p.w3 is not None else None)
     return q, (-t / s).contiguous()
 
 
