@@ -512,6 +512,34 @@ int pemp_episode_preprocess(const uint8_t* blob, const pemp_sample_desc* descs_h
                             const float* mean, const float* std, float* img_out, float* planes_out,
                             int64_t* label_out, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- PFENet inference (networks/pfenet.py) ---------------------------------------------------------------------------
+ * Prior mask (:201-226): q NHWC [B][HW][C] (pixel stride ldq), s NHWC [B*S][HW][C] (lds), mask [B*S][HW] (the support masks
+ * at feature resolution).  Per episode b and shot i: sim[q] = max_p dot(q, m_p s_p) / (|m_p s_p| |q| + 1e-7) on the fp32 MFMA,
+ * with fl(m_p * s_p) formed on operand load, the norms and the max over p fused into the GEMM epilogue (the HW x HW matrix
+ * never reaches memory: per 64-pixel support tile one partial max per query pixel, ws); then (sim - min) / (max - min + 1e-7)
+ * over q and the mean over the shots in order -> out [B][HW].  Deterministic: the maxima are exact, every sum in fixed
+ * order.  C % 32 == 0; any HW.                                                                                        */
+size_t pemp_prior_mask_workspace_bytes(int B, int S, int HW);
+int pemp_prior_mask_f32(const float* q, int ldq, const float* s, int lds, const float* mask, float* out, void* ws,
+                        size_t ws_bytes, int B, int S, int HW, int C, void* stream);
+/* nn.AdaptiveAvgPool2d((Ho, Wo)) on NHWC (pfenet.py:244-247): windows [floor(i H / Ho), ceil((i + 1) H / Ho)), also for
+ * Ho > H; x and y are channel slices with pixel strides ldx / ldy.                                                    */
+int pemp_adaptive_avgpool_nhwc_f32(const float* x, int ldx, float* y, int ldy, int N, int H, int W, int C, int Ho, int Wo,
+                                   void* stream);
+/* F.interpolate(mode="bilinear", align_corners=True) [N][hi][wi] -> [N][ho][wo] over C channels, any sizes (1-pixel sides
+ * included).  Element (n, pixel, c) of x lives at n * xn + pixel * ldx + c * xc (of y: n * yn + pixel * ldy + c * yc), so a
+ * channel slice, a mask plane or an NCHW output is addressed directly.  flags & 1: x is read as (x == 1) (pfenet.py:182). */
+int pemp_resize_bilinear_ac_nhwc_f32(const float* x, long long xn, int ldx, int xc, float* y, long long yn, int ldy, int yc,
+                                     int N, int C, int hi, int wi, int ho, int wo, int flags, void* stream);
+/* Weighted_GAP (pfenet.py:15-20) per support image, averaged over the S shots of an episode (:229-233): feat NHWC
+ * [B*S][h][w][C] (ldf), mask [B*S][h][w] -> out [B][C] = mean_i sum(f m) / (sum(m) + 5e-4) (as avg_pool2d * h * w).   */
+int pemp_weighted_gap_f32(const float* feat, int ldf, const float* mask, float* out, int B, int S, int h, int w, int C,
+                          void* stream);
+/* y[p][c] = x[p][c] * m[p] (m may be NULL) + r[p][c] (r may be NULL) over npix NHWC pixels: the masked layer-4 input of
+ * the supports (pfenet.py:193) and the FEM's "relu(conv(.)) + x" sums (:261,264,270), whose ReLU comes before the add.  */
+int pemp_scale_add_nhwc_f32(const float* x, int ldx, const float* m, const float* r, int ldr, float* y, int ldy,
+                            long long npix, int C, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -134,6 +134,14 @@ SYMBOLS = {
     "pemp_dgrad_mirror_f32": (c_int, [c_fp, c_fp, c_fp, c_int, c_int, c_fp]),
     "pemp_adam_clip_step_f32": (c_int, [c_fp, c_fp, c_fp, c_fp, C.c_longlong, C.c_float] + [C.c_double] * 5 + [C.c_longlong, C.c_float, c_fp, c_fp,
                                                                                                   c_size, c_fp]),
+    # PFENet inference
+    "pemp_prior_mask_workspace_bytes": (c_size, [c_int] * 3),
+    "pemp_prior_mask_f32": (c_int, [c_fp, c_int, c_fp, c_int, c_fp, c_fp, c_fp, c_size] + [c_int] * 4 + [c_fp]),
+    "pemp_adaptive_avgpool_nhwc_f32": (c_int, [c_fp, c_int, c_fp] + [c_int] * 7 + [c_fp]),
+    "pemp_resize_bilinear_ac_nhwc_f32": (c_int, [c_fp, C.c_longlong, c_int, c_int, c_fp, C.c_longlong, c_int, c_int] + [c_int] * 7
+                                         + [c_fp]),
+    "pemp_weighted_gap_f32": (c_int, [c_fp, c_int, c_fp, c_fp] + [c_int] * 5 + [c_fp]),
+    "pemp_scale_add_nhwc_f32": (c_int, [c_fp, c_int, c_fp, c_fp, c_int, c_fp, c_int, C.c_longlong, c_int, c_fp]),
 }
 
 ABI_VERSION = 2          # include/pemp_hip.h: PEMP_ABI_VERSION

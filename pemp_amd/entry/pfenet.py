@@ -1,0 +1,66 @@
+"""PFENet evaluation harness on MI355X (counterpart of the reference's entry/pfenet.py: config :27-45, ``Evaluator.test_step``
+:54-60, ``test`` :129-148).  The stage-1 evaluator (batching, sharding, hipGraph replay, fused upsample + CE + argmax +
+tp/fp/fn tail) runs the model's feature-resolution logits (``PFENet.lowres``).  Training is not ported: ``train`` raises."""
+from ..config import Experiment
+from ..networks.pfenet import WGEN_SEED, ModelClass  # noqa: F401
+from .pemp_stage1 import INGREDIENTS, SyntheticEpisodes, eval_episodes, get_val_labels, num_classes  # noqa: F401
+from .pemp_stage1 import Evaluator as _Evaluator
+
+NAME = "PEMP"
+ex = Experiment(name=NAME, ingredients=INGREDIENTS[1:])      # data, tr, te, g, d (the reference's PFENet has no net ingredient)
+
+
+@ex.config
+def ex_config():
+    tag = "pfenet"              # str, configuration tag
+    shot = 1                    # int, support samples per episode
+    query = 1                   # int, query samples per episode
+    split = -1                  # int, split number [0, 1, 2, 3], required
+    seed = 1234                 # int, random seed
+    ckpt = "bestckpt.pth"       # str, checkpoint file
+    exp_id = -1                 # experiment id to load checkpoint
+    loss = "ce"                 # str, loss type [ce/cedt]
+    sigma = 5.                  # float, sigma of the DT loss
+    loss_coef = 1.              # float, coefficient of the auxiliary loss
+    p = {"cls": -1, "sup": "", "qry": ""}
+
+
+class Evaluator(_Evaluator):
+    """The stage-1 evaluator on PFENet's feature-resolution logits (entry/pfenet.py:54-60: forward at the label size, CE,
+    argmax)."""
+
+    def _lowres(self, dev_in):
+        sup_img, sup_mask, qry_img = dev_in
+        self.model.check_inputs(sup_img, qry_img)          # before a graph is captured for a shape the model rejects
+        return super()._lowres(dev_in)
+
+
+@ex.command
+def test(_config, split, shot, query, exp_id, ckpt):
+    import logging
+    import numpy as np
+    logging.basicConfig(level=logging.INFO, format="%(message)s")
+    logger = logging.getLogger(NAME)
+    if split < 0:
+        raise ValueError("Argument `split` is required! For example: `python -m pemp_amd.entry.pfenet test with split=0`")
+    if query != 1:
+        raise ValueError("PFENet takes exactly one query per episode (query=1)")
+    from ..core.snapshots import load_for_eval
+    model = ModelClass(shot, logger)
+    load_for_eval(model, _config, exp_id, ckpt, logger, wgen_seed=WGEN_SEED)
+    model = model.cuda().eval()
+    ev = Evaluator(model)
+    d = _config["data"]
+    data = eval_episodes(d, shot, split)
+    loss, miou, biou = ev.start_eval_loop(data, num_classes(d["dataset"]), split, _config["te"]["epochs"], logger,
+                                          batch=d["test_bs"], dataset_name=d["dataset"])
+    return f"Loss: {loss:.4f}, mIoU: {np.mean(miou) * 100:.2f}, bIoU: {np.mean(biou) * 100:.2f}"
+
+
+@ex.command
+def train(_config):
+    raise NotImplementedError("PFENet is an inference path here: `test` runs it; training (entry/pfenet.py:63-126) is not ported")
+
+
+if __name__ == "__main__":
+    print(ex.run_commandline())

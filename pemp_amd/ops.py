@@ -962,3 +962,106 @@ def cm_bias(feat, group, wext, alpha=None, base=None):
     _lib.check(lib.pemp_cm_bias_f32(_p(feat), _p(group), _p(wext), wext.stride(0), _p(alpha), _p(base), _p(out), n, cout,
                                     _stream()), "cm_bias")
     return out
+
+
+# -- PFENet inference (csrc/pfenet.hip) ---------------------------------------------------------------------------------------
+def prior_mask(qry, sup, mask, S, out=None, ws_cache=None):
+    """PFENet's prior (networks/pfenet.py:201-227): qry NHWC [B,h,w,C], sup NHWC [B*S,h,w,C], mask fp32 [B*S,h,w] (support masks
+    at feature resolution) -> [B,h,w] (the min-max normalised max cosine, averaged over the S shots)."""
+    lib = _lib.load()
+    _chk_dev(qry, sup, mask, out)
+    ldq, lds = _nhwc(qry, "qry"), _nhwc(sup, "sup")
+    b, h, w, c = qry.shape
+    if tuple(sup.shape) != (b * S, h, w, c) or tuple(mask.shape) != (b * S, h, w) or not mask.is_contiguous() \
+            or mask.dtype != torch.float32:
+        raise ValueError(f"prior_mask: sup {tuple(sup.shape)} / mask {tuple(mask.shape)} do not match qry {tuple(qry.shape)} x S={S}")
+    if out is None:
+        out = torch.empty((b, h, w), dtype=torch.float32, device=qry.device)
+    if tuple(out.shape) != (b, h, w) or not out.is_contiguous():
+        raise ValueError("prior_mask: out must be contiguous [B,h,w]")
+    ws = _ws(lib.pemp_prior_mask_workspace_bytes(b, S, h * w), qry.device, ws_cache, ("prior", b, S, h * w))
+    _lib.check(lib.pemp_prior_mask_f32(_p(qry), ldq, _p(sup), lds, _p(mask), _p(out), _p(ws), ws.numel(), b, S, h * w, c,
+                                       _stream()), "prior_mask")
+    return out
+
+
+def adaptive_avgpool(x, size, out=None):
+    """nn.AdaptiveAvgPool2d(size) on an NHWC view (``out``: an NHWC view, e.g. a channel slice of a wider buffer)."""
+    lib = _lib.load()
+    _chk_dev(x, out)
+    ldx = _nhwc(x, "x")
+    n, h, w, c = x.shape
+    ho, wo = (size, size) if isinstance(size, int) else size
+    if out is None:
+        out = torch.empty((n, ho, wo, c), dtype=torch.float32, device=x.device)
+    if tuple(out.shape) != (n, ho, wo, c):
+        raise ValueError(f"adaptive_avgpool: out {tuple(out.shape)} != {(n, ho, wo, c)}")
+    _lib.check(lib.pemp_adaptive_avgpool_nhwc_f32(_p(x), ldx, _p(out), _nhwc(out, "out"), n, h, w, c, ho, wo, _stream()),
+               "adaptive_avgpool")
+    return out
+
+
+def _strides4(t, name):
+    """(image stride, pixel stride, channel stride) of a 4-D [N, H, W, C] fp32 view whose pixels are evenly spaced."""
+    if t.dim() != 4 or t.dtype != torch.float32:
+        raise ValueError(f"{name}: expected a 4-D fp32 [N,H,W,C] view, got {tuple(t.shape)} {t.dtype}")
+    n, h, w, c = t.shape
+    sn, sh, sw, sc = t.stride()
+    sp = sw if w > 1 else (sh if h > 1 else 1)
+    if (w > 1 and h > 1 and sh != w * sp) or sp <= 0 or sc <= 0 or sn < 0:
+        raise ValueError(f"{name}: pixels must be evenly spaced (strides {t.stride()})")
+    return sn, sp, sc
+
+
+def resize_bilinear_ac(x, size, out=None, binarize=False):
+    """F.interpolate(x, size, mode="bilinear", align_corners=True) on a [N,H,W,C] view with any strides of the form (image,
+    pixel, channel): NHWC channel slices, an [N,H,W,1] view of a mask plane, an NCHW result seen as [N,H,W,C].  ``binarize``:
+    read x as (x == 1).  ``out`` None: a new contiguous NHWC tensor."""
+    lib = _lib.load()
+    _chk_dev(x, out)
+    n, hi, wi, c = x.shape
+    ho, wo = (size, size) if isinstance(size, int) else size
+    if out is None:
+        out = torch.empty((n, ho, wo, c), dtype=torch.float32, device=x.device)
+    if tuple(out.shape) != (n, ho, wo, c):
+        raise ValueError(f"resize_bilinear_ac: out {tuple(out.shape)} != {(n, ho, wo, c)}")
+    xn, xp, xc = _strides4(x, "x")
+    yn, yp, yc = _strides4(out, "out")
+    _lib.check(lib.pemp_resize_bilinear_ac_nhwc_f32(_p(x), xn, xp, xc, _p(out), yn, yp, yc, n, c, hi, wi, ho, wo, int(binarize),
+                                                    _stream()), "resize_bilinear_ac")
+    return out
+
+
+def weighted_gap(feat, mask, S, out=None):
+    """PFENet's Weighted_GAP (networks/pfenet.py:15-20) averaged over the S shots (:229-233): feat NHWC [B*S,h,w,C], mask
+    [B*S,h,w] -> [B,C]."""
+    lib = _lib.load()
+    _chk_dev(feat, mask, out)
+    ldf = _nhwc(feat, "feat")
+    n, h, w, c = feat.shape
+    if n % S or tuple(mask.shape) != (n, h, w) or not mask.is_contiguous():
+        raise ValueError("weighted_gap: mask must be contiguous [B*S,h,w]")
+    if out is None:
+        out = torch.empty((n // S, c), dtype=torch.float32, device=feat.device)
+    if tuple(out.shape) != (n // S, c) or not out.is_contiguous():
+        raise ValueError("weighted_gap: out must be contiguous [B,C]")
+    _lib.check(lib.pemp_weighted_gap_f32(_p(feat), ldf, _p(mask), _p(out), n // S, S, h, w, c, _stream()), "weighted_gap")
+    return out
+
+
+def scale_add(x, mask=None, residual=None, out=None):
+    """out = x * mask[pixel] (+ residual) on NHWC views; ``mask`` contiguous [N,H,W] or None."""
+    lib = _lib.load()
+    _chk_dev(x, mask, residual, out)
+    ldx = _nhwc(x, "x")
+    n, h, w, c = x.shape
+    if out is None:
+        out = torch.empty((n, h, w, c), dtype=torch.float32, device=x.device)
+    if tuple(out.shape) != tuple(x.shape) or (residual is not None and tuple(residual.shape) != tuple(x.shape)):
+        raise ValueError("scale_add: shape mismatch")
+    if mask is not None and (mask.numel() != n * h * w or not mask.is_contiguous()):
+        raise ValueError("scale_add: mask must be contiguous [N,H,W]")
+    ldr = _nhwc(residual, "residual") if residual is not None else 0
+    _lib.check(lib.pemp_scale_add_nhwc_f32(_p(x), ldx, _p(mask), _p(residual), ldr, _p(out), _nhwc(out, "out"), n * h * w, c,
+                                           _stream()), "scale_add")
+    return out

@@ -1,0 +1,184 @@
+"""PFENet inference engine (reference: networks/pfenet.py:157-274, networks/pfe_resent.py:97-160): the deep-base dilated
+ResNet-50 trunk to layer 4, the prior mask and the feature enrichment module (FEM), as one chain of libpemp_hip.so launches
+on one stream from a static ``Arena`` (hipGraph capture works as for the other models).
+
+Layout choices:
+- layer 2's output is written into channels 1024..1535 and layer 3's into 0..1023 of one [n,h,w,1536] buffer: the
+  ``cat([feat_3, feat_2])`` of the 1x1 ``down_query`` / ``down_supp`` convs (:175,195) is never formed;
+- layer 4 runs once over supports and queries: its input is layer 3 times the support mask (:193), the queries' rows
+  times 1 (exact);
+- ``init_merge`` sees [query 256 | support 256 | prior 1] (:251): the support channels are constant over space, so their
+  1x1 conv is a per-image shift (CONV_SHIFT_PER_IMAGE); the prior is zero-padded into the conv's K (channel 256 of a
+  288-channel input, channels 257..287 zero: the conv engine takes Cin % 32 == 0);
+- ``relu(conv(.)) + x`` (:261,264,270) runs as the conv with its ReLU, then ``ops.scale_add``: the conv engine's residual
+  epilogue computes relu(conv + x), which is not the same function;
+- the 256 -> 2 classifier conv is packed with 62 zero output channels (Cout % 64), its two live channels resized into the
+  [B,2,h,w] logits in one pass;
+- ``inner_cls`` (:266) feeds only the training loss (:276-285): not run.
+"""
+import torch
+
+from . import ops
+from .engine import conv_params, with_split3
+from .ops import ConvParams
+
+PYRAMID_BINS = (60, 30, 15, 8)
+REDUCE = 256
+MERGE_CIN = REDUCE + 32                 # query channels + the prior channel, zero-padded to a multiple of 32
+
+
+class _DeepBlockPlan:
+    """One pfe_resent Bottleneck (v1.5: the stride sits on the 3x3 conv; layer 3 / 4 dilated with stride 1)."""
+
+    def __init__(self, blk):
+        self.c1 = conv_params(blk.conv1, blk.bn1, relu=True)
+        self.c2 = conv_params(blk.conv2, blk.bn2, relu=True)
+        self.c3 = conv_params(blk.conv3, blk.bn3, relu=True)      # relu after the residual add
+        self.ds = conv_params(blk.downsample[0], blk.downsample[1], relu=False) if blk.downsample is not None else None
+
+
+class DeepBaseResNetEngine:
+    """pfe_resent.ResNet(Bottleneck, [3, 4, 6, 3], deep_base=True) with PFENet's dilations (pfenet.py:68-77)."""
+
+    def __init__(self, model, arena):
+        self.arena = arena
+        l0 = model.layer0
+        self.stem = [conv_params(l0[0], l0[1], relu=True, stem4=True), conv_params(l0[3], l0[4], relu=True),
+                     conv_params(l0[6], l0[7], relu=True)]
+        self.stages = [[_DeepBlockPlan(b) for b in getattr(model, f"layer{i}")] for i in (1, 2, 3, 4)]
+
+    def _block(self, x, bp, out):
+        a = self.arena
+        n, h, w, _ = x.shape
+        ho = ops.conv_out_size(h, bp.c2.kh, bp.c2.stride, bp.c2.pad, bp.c2.dil)
+        wo = ops.conv_out_size(w, bp.c2.kw, bp.c2.stride, bp.c2.pad, bp.c2.dil)
+        y1 = ops.conv2d(x, bp.c1, out=a.get("pf_y1", (n, h, w, bp.c1.cout)))
+        y2 = ops.conv2d(y1, bp.c2, out=a.get("pf_y2", (n, ho, wo, bp.c2.cout)))
+        res = ops.conv2d(x, bp.ds, out=a.get("pf_res", (n, ho, wo, bp.ds.cout))) if bp.ds is not None else x
+        return ops.conv2d(y2, bp.c3, out=out, residual=res)
+
+    def _stage(self, x, si, final_out=None):
+        blocks = self.stages[si]
+        for bi, bp in enumerate(blocks):
+            n, h, w, _ = x.shape
+            ho = ops.conv_out_size(h, bp.c2.kh, bp.c2.stride, bp.c2.pad, bp.c2.dil)
+            wo = ops.conv_out_size(w, bp.c2.kw, bp.c2.stride, bp.c2.pad, bp.c2.dil)
+            out = final_out if (bi == len(blocks) - 1 and final_out is not None) else \
+                self.arena.get(("pf_blk", si, bi & 1), (n, ho, wo, bp.c3.cout))
+            x = self._block(x, bp, out)
+        return x
+
+    def forward_to_layer3(self, x4):
+        """x4 NHWC4 [n,H,W,4] -> [n,h,w,1536]: layer 3 in channels 0..1023, layer 2 in 1024..1535."""
+        a = self.arena
+        n, H, W, _ = x4.shape
+        x = x4
+        for i, cp in enumerate(self.stem):
+            h, w = x.shape[1:3]
+            ho, wo = ops.conv_out_size(h, 3, cp.stride, cp.pad, 1), ops.conv_out_size(w, 3, cp.stride, cp.pad, 1)
+            x = ops.conv2d(x, cp, out=a.get(("pf_stem", i & 1), (n, ho, wo, cp.cout)))
+        h, w = x.shape[1:3]
+        hp, wp = ops._pool_out(h, 3, 2, 1, False), ops._pool_out(w, 3, 2, 1, False)      # MaxPool2d(3, 2, 1), no ceil_mode
+        x = ops.maxpool2d(x, 3, 2, 1, out=a.get("pf_pool", (n, hp, wp, x.shape[3])))
+        x = self._stage(x, 0)
+        h2 = ops.conv_out_size(x.shape[1], 3, 2, 1, 1)
+        w2 = ops.conv_out_size(x.shape[2], 3, 2, 1, 1)
+        cat = a.get("pf_cat23", (n, h2, w2, 1536))
+        f2 = self._stage(x, 1, final_out=cat[..., 1024:])
+        self._stage(f2, 2, final_out=cat[..., :1024])
+        return cat
+
+    def layer4(self, x, out):
+        return self._stage(x, 3, final_out=out)
+
+
+class PFENetEngine:
+    """The whole eval forward: ``lowres(sup_img, sup_mask, qry_img)`` -> logits [B,2,h,w] at feature resolution."""
+
+    def __init__(self, model, arena):
+        self.arena = arena
+        self.trunk = DeepBaseResNetEngine(model, arena)
+        self.down_q = conv_params(model.down_query[0], None, relu=True)
+        self.down_s = conv_params(model.down_supp[0], None, relu=True)
+        self.merge, self.merge_s = [], []
+        for m in model.init_merge:
+            conv = m[0]
+            w = conv.weight.detach().float()[:, :, 0, 0]                        # [256, 513]: query | support | prior
+            wq = torch.zeros((REDUCE, MERGE_CIN), dtype=torch.float32, device=w.device)
+            wq[:, :REDUCE] = w[:, :REDUCE]
+            wq[:, REDUCE] = w[:, 2 * REDUCE]
+            self.merge.append(with_split3(ConvParams(wq.contiguous(), None, None, MERGE_CIN, REDUCE, 1, 1, 1, 0, 1, MERGE_CIN,
+                                                     False, True)))
+            self.merge_s.append(conv_params(conv, None, relu=False, in_slice=(REDUCE, 2 * REDUCE)))
+        self.alpha = [conv_params(m[0], None, relu=True) for m in model.alpha_conv]
+        self.beta = [(conv_params(m[0], None, relu=True), conv_params(m[2], None, relu=True)) for m in model.beta_conv]
+        self.res1 = conv_params(model.res1[0], None, relu=True)
+        self.res2 = (conv_params(model.res2[0], None, relu=True), conv_params(model.res2[2], None, relu=True))
+        self.cls0 = conv_params(model.cls[0], None, relu=True)
+        c3 = model.cls[3]
+        w = torch.zeros((64, REDUCE), dtype=torch.float32, device=c3.weight.device)
+        w[:2] = c3.weight.detach().float()[:, :, 0, 0]
+        b = torch.zeros(64, dtype=torch.float32, device=c3.weight.device)
+        b[:2] = c3.bias.detach().float()
+        self.cls3 = with_split3(ConvParams(w.contiguous(), None, b.contiguous(), REDUCE, 64, 1, 1, 1, 0, 1, REDUCE, False, False))
+        self._ones = set()
+
+    def lowres(self, sup_img, sup_mask, qry_img):
+        """sup_img [B,S,3,H,W], sup_mask [B,S,2,H,W] (plane 0: foreground), qry_img [B,1,3,H,W] on the device."""
+        a = self.arena
+        B, S, ch, H, W = sup_img.shape
+        ns, n = B * S, B * S + B
+        x4 = a.get("x4", (n, H, W, 4))
+        ops.pack_input(sup_img.reshape(ns, ch, H, W).contiguous(), out=x4[:ns])
+        ops.pack_input(qry_img.reshape(B, ch, H, W).contiguous(), out=x4[ns:])
+        cat23 = self.trunk.forward_to_layer3(x4)                                 # [n,h,w,1536]
+        h, w = cat23.shape[1:3]
+        # support masks at feature resolution (:182-185, == 1 then bilinear align_corners), the queries' rows = 1
+        mfeat = a.get("pf_mfeat", (n, h, w))
+        if mfeat.data_ptr() not in self._ones:
+            mfeat[ns:].fill_(1.0)
+            self._ones.add(mfeat.data_ptr())
+        fg = sup_mask.reshape(ns, 2, H, W)[:, 0].unsqueeze(-1)
+        ops.resize_bilinear_ac(fg, (h, w), out=mfeat[:ns].unsqueeze(-1), binarize=True)
+        # layer 4 over layer3 * mask (:193; the queries' layer 4 of :171 is the same chain on their unmasked rows)
+        x4in = ops.scale_add(cat23[..., :1024], mask=mfeat, out=a.get("pf_l4in", (n, h, w, 1024)))
+        f4 = self.trunk.layer4(x4in, a.get("pf_l4", (n, h, w, 2048)))
+        self.last_layer4 = f4
+        prior = ops.prior_mask(f4[ns:], f4[:ns], mfeat[:ns], S, out=a.get("pf_prior", (B, h, w)), ws_cache=a.ws)
+        self.last_prior = prior
+        # down_query / down_supp (:175-176,195-196) and the support vector (:197,229-233)
+        dq = ops.conv2d(cat23[ns:], self.down_q, out=a.get("pf_dq", (B, h, w, REDUCE)))
+        dsup = ops.conv2d(cat23[:ns], self.down_s, out=a.get("pf_ds", (ns, h, w, REDUCE)))
+        svec = ops.weighted_gap(dsup, mfeat[:ns], S, out=a.get("pf_svec", (B, REDUCE)))
+        self.last_supp_vec = svec
+        res1_in = a.get("pf_res1_in", (B, h, w, REDUCE * len(PYRAMID_BINS)))
+        self.last_bins = []
+        for idx, bn in enumerate(PYRAMID_BINS):                                  # FEM (:238-268)
+            inp = a.get(("pf_mrg_in", idx), (B, bn, bn, MERGE_CIN), zero=True)  # channels 257.. stay zero
+            ops.adaptive_avgpool(dq, bn, out=inp[..., :REDUCE])
+            ops.resize_bilinear_ac(prior.unsqueeze(-1), bn, out=inp[..., REDUCE:REDUCE + 1])
+            self.last_bins.append(inp[..., REDUCE])
+            shift = ops.conv2d(svec.view(B, 1, 1, REDUCE), self.merge_s[idx], out=a.get(("pf_mrg_s", idx), (B, 1, 1, REDUCE)))
+            rec = a.get(("pf_rec", idx), (B, bn, bn, 2 * REDUCE))
+            merge = ops.conv2d(inp, self.merge[idx], out=rec[..., :REDUCE], shift_override=shift.view(B, REDUCE),
+                               per_image_shift=True)
+            if idx >= 1:
+                prev = res1_in[..., (idx - 1) * REDUCE:idx * REDUCE]
+                ops.resize_bilinear_ac(prev, bn, out=rec[..., REDUCE:])
+                t = ops.conv2d(rec, self.alpha[idx - 1], out=a.get(("pf_t", idx), (B, bn, bn, REDUCE)))
+                merge = ops.scale_add(t, residual=merge, out=a.get(("pf_m2", idx), (B, bn, bn, REDUCE)))
+            b0, b1 = self.beta[idx]
+            t1 = ops.conv2d(merge, b0, out=a.get(("pf_b0", idx), (B, bn, bn, REDUCE)))
+            t2 = ops.conv2d(t1, b1, out=a.get(("pf_b1", idx), (B, bn, bn, REDUCE)))
+            merge = ops.scale_add(t2, residual=merge, out=a.get(("pf_m3", idx), (B, bn, bn, REDUCE)))
+            ops.resize_bilinear_ac(merge, (h, w), out=res1_in[..., idx * REDUCE:(idx + 1) * REDUCE])
+        self.last_res1_in = res1_in
+        q1 = ops.conv2d(res1_in, self.res1, out=a.get("pf_q1", (B, h, w, REDUCE)))
+        r = ops.conv2d(q1, self.res2[0], out=a.get("pf_r0", (B, h, w, REDUCE)))
+        r = ops.conv2d(r, self.res2[1], out=a.get("pf_r1", (B, h, w, REDUCE)))
+        q2 = ops.scale_add(r, residual=q1, out=a.get("pf_q2", (B, h, w, REDUCE)))
+        c = ops.conv2d(q2, self.cls0, out=a.get("pf_c0", (B, h, w, REDUCE)))
+        c = ops.conv2d(c, self.cls3, out=a.get("pf_c3", (B, h, w, 64)))
+        pred = a.get("pf_pred", (B, 2, h, w))
+        ops.resize_bilinear_ac(c[..., :2], (h, w), out=pred.permute(0, 2, 3, 1))    # NHWC -> NCHW (identity resize: exact)
+        return pred
