@@ -817,7 +817,12 @@ int launch_conv_dma2_splitk(int tile, ConvArgs a, void* ws, size_t ws_bytes, hip
 }
 
 // ---- split3 family: the S3 body on the shapes of tiles 1..4 and 6 (tile 5, 128 x 64 in 8 waves, has no whole B DMA rounds at
-// 192 bytes per row; tile 7, 256 x 256, would need all 160 KiB of LDS) ----
+// 192 bytes per row; tile 7, 256 x 256, would need all 160 KiB of LDS).
+// Wave grids: the A fragment is split (split3_bf16, ~9 VALU per element pair) by every wave that reads it, and the pieces feed
+// 6 TN MFMAs.  So ids 41, 42 and 46 give each wave a FULL-WIDTH strip (WGM = NW: 32 rows x BN columns, TN = BN / 32), and every
+// activation row of a block is split once instead of once per wave column: 41 / 46 go from ~4.0 to ~2.2 VALU per MFMA in the K
+// loop (scratch/s3_isa_mix.py).  43 (64 x 64, 4 waves) and 44 (128 x 128, 8 waves) have fewer 32-row strips than waves and keep
+// two wave columns.  The MFMA sequence each accumulator sees does not depend on the grid: every id stays bit-identical. ----
 template <int BM, int BN, int WGM, int NW, bool SK>
 static int launch_dma2_s3(const ConvArgs& a, int grid, hipStream_t st) {
     const size_t lds = (size_t)2 * (8 * BM + 12 * BN) * sizeof(v4f);
@@ -836,10 +841,10 @@ static int launch_dma2_s3(const ConvArgs& a, int grid, hipStream_t st) {
 
 template <bool SK>
 static int launch_s3_tile(int tile, const ConvArgs& a, int grid, hipStream_t st) {
-    if (tile == 6) return launch_dma2_s3<256, 128, 4, 8, SK>(a, grid, st);
+    if (tile == 6) return launch_dma2_s3<256, 128, 8, 8, SK>(a, grid, st);
     if (tile == 4) return launch_dma2_s3<128, 128, 4, 8, SK>(a, grid, st);
-    if (tile == 1) return launch_dma2_s3<128, 128, 2, 4, SK>(a, grid, st);
-    if (tile == 2) return launch_dma2_s3<128, 64, 2, 4, SK>(a, grid, st);
+    if (tile == 1) return launch_dma2_s3<128, 128, 4, 4, SK>(a, grid, st);
+    if (tile == 2) return launch_dma2_s3<128, 64, 4, 4, SK>(a, grid, st);
     return launch_dma2_s3<64, 64, 2, 4, SK>(a, grid, st);
 }
 
@@ -873,10 +878,10 @@ int launch_conv_dma2_group_split3(int tile, ConvGroupArgs& g, hipStream_t st) {
         return -1;
     }
     const bool padv = g.a[0].padv != nullptr;
-    if (tile == 6) return launch_dma2_group<256, 128, 4, 8, false, true>(g, padv, st);
+    if (tile == 6) return launch_dma2_group<256, 128, 8, 8, false, true>(g, padv, st);
     if (tile == 4) return launch_dma2_group<128, 128, 4, 8, false, true>(g, padv, st);
-    if (tile == 1) return launch_dma2_group<128, 128, 2, 4, false, true>(g, padv, st);
-    if (tile == 2) return launch_dma2_group<128, 64, 2, 4, false, true>(g, padv, st);
+    if (tile == 1) return launch_dma2_group<128, 128, 4, 4, false, true>(g, padv, st);
+    if (tile == 2) return launch_dma2_group<128, 64, 4, 4, false, true>(g, padv, st);
     return launch_dma2_group<64, 64, 2, 4, false, true>(g, padv, st);
 }
 
