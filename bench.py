@@ -7,6 +7,7 @@
     python bench.py --dataset COCO                                     COCO-20i-shaped episodes, configs[4]
     python bench.py --model baseline --batch 12                        Baseline VGG-16, configs[0]
     python bench.py ... --dump-outputs DIR                             + what the last timed step computed, DIR/<name>.npy
+    python bench.py ... --full                                         + every figure beside the headline (list below)
 
 A "step" is one pass of the hot path over ``--batch`` synthetic episodes already resident in HBM: for eval the device
 work of Evaluator.test_step (encoder, meta-prototype module, cosine map, upsample + argmax + CE + IoU counts; reference
@@ -14,22 +15,30 @@ entry/pemp_stage1.py:48-53), for train the whole Trainer.train_step (entry/pemp_
 in eval (episodes shard; no data-path collective) and data-parallel in training (gradient all-reduce over RCCL); scaling
 is weak.  ``--gpus N`` without a launcher around it (no WORLD_SIZE in the environment) starts the N ranks itself.
 
-Rank 0 prints ONE JSON line (contract in the task statement) with these extra objects:
+Rank 0 prints ONE JSON line: the headline (metric, value, unit, ms_per_step, ...), its `config`, and
+  comm            what the ranks exchanged inside the timed region and how evenly they ran: backend, world, RCCL version,
+                  bytes all-reduced, the gradient buckets with their element ranges (train), exposed communication time,
+                  every rank's own ms_per_step; eval: the round's metric table is all-reduced INSIDE the timed region and
+                  checked against the sum of the rank shards (``miou`` for N > 1, ``round_miou`` for N = 1, from the
+                  reduced table)
+A plain run does nothing else: it sets up, warms up, times the K steps, writes --dump-outputs and prints the line.
+``--full`` adds the objects below, each measured after the timed region in the same process (``--no-roofline``,
+``--no-single``, ``--no-e2e``, ``--no-sides`` and ``--cpu-episodes 0`` leave single ones out of a full line):
   roofline        the dominant kernel class (the fp32-MFMA implicit-GEMM convs) against the 157.3 TFLOP/s dense fp32
                   matrix peak: algorithmic flops of every conv launch of a step / their durations, taken live with HIP
                   events on the stream each kernel is launched on (an instrumented pass over the C ABI, eager, same
                   workload); ``by_class`` splits the step over conv / weight-gradient / BatchNorm / head / optimizer
   single_episode  (eval, N = 1) the reference's own protocol, one episode per test_step (data_kits/datasets.py:23)
-  comm            what the ranks exchanged inside the timed region and how evenly they ran: backend, world, RCCL version,
-                  bytes all-reduced, the gradient buckets with their element ranges (train), exposed communication time,
-                  every rank's own ms_per_step; eval: the round's metric table is all-reduced INSIDE the timed region and
-                  checked against the sum of the rank shards (``miou`` is printed from the reduced table)
-  cedt            (default line) the eval step and the train step with loss=cedt (CELossDT on the device), next to loss=ce
-  protocol_5x1000 (default line) the reference's evaluation protocol: 5 rounds x 1000 episodes, one episode per test_step
-  bf16_variant    (default line; SIDE FIGURE, never `value` / `roofline`) the eval step with bf16 operands in the encoder: episodes/s,
-                  and the mIoU / arg-max pixels it moves on one round over the resident episodes
+  end_to_end      (N = 1) episodes/s including input staging (uint8 host samples -> device preprocessing -> the step)
   cpu_baseline    the CPU oracle (oracle/ref_cpu.py, bit-equal to the reference here) timed on the host cores in child
-                  processes: 1 thread and all cores of the box's share, bounded samples of the same workload
+                  processes: 1 thread and all cores of the box's share, bounded samples of the same workload; ``miou``
+                  (stage 1, N = 1): the mIoU of the episodes it evaluated, on the device and on the CPU
+  protocol_5x1000 (headline line) the reference's evaluation protocol: 5 rounds x 1000 episodes, one episode per test_step
+  cedt            (headline line) the eval step and the train step with loss=cedt (CELossDT on the device), next to loss=ce
+  train, stage2_5shot, coco, baseline_vgg16
+                  (headline line) the other BASELINE.json configurations, each with a roofline fraction of its own
+  bf16_variant    (with --bf16-side; SIDE FIGURE, never `value` / `roofline`) the eval step with bf16 operands in the
+                  encoder: episodes/s, and the mIoU / arg-max pixels it moves on one round over the resident episodes
 """
 import argparse
 import json
@@ -68,13 +77,17 @@ def parse():
                     help="cedt: CELossDT (core/losses.py:17-43; what the reference's scripts train with) -- boundary + exact "
                          "distance transform + weighted CE on the device, inside the timed region")
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--cpu-episodes", type=int, default=12, help="bounded CPU-baseline sample (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure every other figure of the line: roofline, CPU baseline, "
+                         "single-episode and staging-inclusive figures, the other configurations (see the module docstring)")
+    ap.add_argument("--cpu-episodes", type=int, default=12, help="--full: bounded CPU-baseline sample (0 = skip)")
     ap.add_argument("--train-graph", action="store_true", help="--mode train: replay forward/backward from a hipGraph")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the staging-inclusive end_to_end figure")
-    ap.add_argument("--no-single", action="store_true", help="skip the one-episode-per-step figure")
-    ap.add_argument("--no-sides", action="store_true", help="default line: skip the `train` / `stage2_5shot` / `coco` / `baseline_vgg16` objects")
-    ap.add_argument("--bf16-side", action="store_true", help="default line: also measure the bf16-operand side figure")
+    ap.add_argument("--no-roofline", action="store_true", help="--full: skip the roofline pass")
+    ap.add_argument("--no-e2e", action="store_true", help="--full: skip the staging-inclusive end_to_end figure")
+    ap.add_argument("--no-single", action="store_true", help="--full: skip the one-episode-per-step figure")
+    ap.add_argument("--no-sides", action="store_true", help="--full, headline line: skip the `protocol_5x1000` / `cedt` / `train` / "
+                                                            "`stage2_5shot` / `coco` / `baseline_vgg16` objects")
+    ap.add_argument("--bf16-side", action="store_true", help="--full, headline line: also measure the bf16-operand side figure")
     ap.add_argument("--dump-outputs", metavar="DIR", default="",
                     help="write what the last timed step computed (rank 0's share) as DIR/<name>.npy: eval -> qry_pred (arg-max "
                          "class per pixel) and stats (ce_sum, n_valid, tp/fp/fn bg, tp/fp/fn fg per episode); train -> loss "
@@ -1264,6 +1277,9 @@ def main_train(args, world, rank, dev):
     if os.environ.get("PEMP_BENCH_STUB"):
         out["config"]["stub_weight"] = float(tr.eng.flat.data[0])      # before the rank-local roofline pass
         out["process_group_alive_at_roofline"] = bool(dist.is_initialized())
+    if not args.full:               # a plain run ends with the headline
+        print(json.dumps(out))
+        return
 
     def guarded(key, fn):
         try:
@@ -1651,9 +1667,12 @@ def main():
         "comm": comm,
     }
     if world > 1:
-        out["miou"] = round_miou      # N = 1 prints `miou` against the CPU oracle below; `round_miou` holds this table there
+        out["miou"] = round_miou      # N = 1: `round_miou` holds this table; --full adds `miou` against the CPU oracle
     else:
         out["round_miou"] = round_miou
+    if not args.full:               # a plain run ends with the headline
+        print(json.dumps(out))
+        return
 
     # the auxiliary measurements must never cost the headline line: a failure is reported in place
     def guarded(key, fn):

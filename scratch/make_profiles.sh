@@ -10,18 +10,18 @@ export PEMP_ROUND=$R
 O=gpurun_out/$R; mkdir -p $O
 B="--cpu-episodes 0 --no-e2e --no-single --no-sides"
 if [ $PART = bench ] || [ $PART = all ]; then
-# 1. bench lines: the default command (headline + comm / cedt / protocol_5x1000 / train / stage2_5shot / miou objects), then every other
-#    BASELINE.json config
-timeout -k 10 500 python3 bench.py --steps 20 --warmup 5 > $O/bench_default.json 2> $O/err.log && echo default ok
-timeout -k 10 500 python3 bench.py --mode train --steps 20 --warmup 5 > $O/bench_train_b4.json 2>> $O/err.log && echo train ok
-timeout -k 10 500 python3 bench.py --mode train --loss cedt --steps 20 --warmup 5 --cpu-episodes 0 > $O/bench_train_cedt_b4.json 2>> $O/err.log && echo train cedt ok
-timeout -k 10 500 python3 bench.py --loss cedt --steps 20 --warmup 5 --cpu-episodes 0 > $O/bench_eval_cedt_b25.json 2>> $O/err.log && echo eval cedt ok
-timeout -k 10 500 python3 bench.py --mode train --model stage2 --steps 20 --warmup 5 > $O/bench_train_stage2_b4.json 2>> $O/err.log && echo train2 ok
-timeout -k 10 500 python3 bench.py --model stage2 --shot 5 --batch 8 --steps 10 --warmup 3 > $O/bench_stage2_5shot_b8.json 2>> $O/err.log && echo stage2 ok
-timeout -k 10 500 python3 bench.py --dataset COCO --steps 10 --warmup 3 --cpu-episodes 4 > $O/bench_eval_coco_b25.json 2>> $O/err.log && echo coco ok
-timeout -k 10 500 python3 bench.py --model baseline --batch 12 --steps 10 --warmup 3 > $O/bench_baseline_vgg16_b12.json 2>> $O/err.log && echo baseline ok
-PEMP_EVAL_SPLITK=1 timeout -k 10 500 python3 bench.py --batch 1 --steps 100 --warmup 10 $B > $O/bench_eval_b1.json 2>> $O/err.log && echo b1 ok
-timeout -k 10 500 python3 bench.py --batch 1 --steps 100 --warmup 10 $B > $O/bench_eval_b1_exact.json 2>> $O/err.log && echo b1 exact ok
+# 1. full bench lines: the default command with --full (headline + comm / cedt / protocol_5x1000 / train / stage2_5shot / miou
+#    objects), then every other BASELINE.json config
+timeout -k 10 500 python3 bench.py --full --steps 20 --warmup 5 > $O/bench_default.json 2> $O/err.log && echo default ok
+timeout -k 10 500 python3 bench.py --full --mode train --steps 20 --warmup 5 > $O/bench_train_b4.json 2>> $O/err.log && echo train ok
+timeout -k 10 500 python3 bench.py --full --mode train --loss cedt --steps 20 --warmup 5 --cpu-episodes 0 > $O/bench_train_cedt_b4.json 2>> $O/err.log && echo train cedt ok
+timeout -k 10 500 python3 bench.py --full --loss cedt --steps 20 --warmup 5 --cpu-episodes 0 > $O/bench_eval_cedt_b25.json 2>> $O/err.log && echo eval cedt ok
+timeout -k 10 500 python3 bench.py --full --mode train --model stage2 --steps 20 --warmup 5 > $O/bench_train_stage2_b4.json 2>> $O/err.log && echo train2 ok
+timeout -k 10 500 python3 bench.py --full --model stage2 --shot 5 --batch 8 --steps 10 --warmup 3 > $O/bench_stage2_5shot_b8.json 2>> $O/err.log && echo stage2 ok
+timeout -k 10 500 python3 bench.py --full --dataset COCO --steps 10 --warmup 3 --cpu-episodes 4 > $O/bench_eval_coco_b25.json 2>> $O/err.log && echo coco ok
+timeout -k 10 500 python3 bench.py --full --model baseline --batch 12 --steps 10 --warmup 3 > $O/bench_baseline_vgg16_b12.json 2>> $O/err.log && echo baseline ok
+PEMP_EVAL_SPLITK=1 timeout -k 10 500 python3 bench.py --full --batch 1 --steps 100 --warmup 10 $B > $O/bench_eval_b1.json 2>> $O/err.log && echo b1 ok
+timeout -k 10 500 python3 bench.py --full --batch 1 --steps 100 --warmup 10 $B > $O/bench_eval_b1_exact.json 2>> $O/err.log && echo b1 exact ok
 fi
 if [ $PART = trace ] || [ $PART = all ]; then
 # 2. kernel traces (rocprofv3 --kernel-trace --stats) of the eval and train commands.  The eval command runs with ONE engine lane

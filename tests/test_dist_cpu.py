@@ -293,7 +293,7 @@ def test_bench_train_control_flow_two_ranks_with_the_rank0_roofline_pass():
     `roofline`, and the weights after the timed steps are the data-parallel result."""
     import json
     r = _run_bench({"PEMP_BENCH_STUB": "1", "PEMP_BENCH_DRYRUN": "", "PEMP_BENCH_SILENCE_S": "60"},
-                   "--gpus", "2", "--steps", "3", "--warmup", "2", "--mode", "train")
+                   "--gpus", "2", "--steps", "3", "--warmup", "2", "--mode", "train", "--full")
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout
@@ -315,6 +315,26 @@ def test_bench_train_control_flow_two_ranks_with_the_rank0_roofline_pass():
     # every rank's host time per step, next to its step time: what tells an enqueue-bound rank from a communication-bound one
     he = comm["host_enqueue_ms_per_step"]
     assert len(he["all"]) == 2 and he["max"] == max(he["all"]) > 0 and 0 < he["of_step"] <= 1.05
+
+
+def test_bench_plain_line_stops_at_the_headline():
+    """Without ``--full`` the line is the headline alone: no roofline pass, CPU baseline or staging figure after the timed steps
+    (the stub's loss counts its calls: warm-up 2 + steps 3, nothing more), and the timed result is the one a full line reports."""
+    import json
+    lines = {}
+    for extra in ((), ("--full",)):
+        r = _run_bench({"PEMP_BENCH_STUB": "1", "PEMP_BENCH_DRYRUN": ""}, "--gpus", "1", "--steps", "3", "--warmup", "2",
+                       "--mode", "train", *extra)
+        assert r.returncode == 0, r.stderr[-2000:]
+        out = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(out) == 1, r.stdout
+        lines[extra] = json.loads(out[0])
+    plain, full = lines[()], lines[("--full",)]
+    assert not {"roofline", "end_to_end", "cpu_baseline"} & set(plain) and "roofline" in full
+    for k in ("metric", "unit", "higher_is_better", "dtype", "steps", "warmup"):
+        assert plain[k] == full[k], k
+    assert plain["config"]["last_loss"] == full["config"]["last_loss"] == 5.0
+    assert plain["config"]["stub_weight"] == full["config"]["stub_weight"]
 
 
 def test_bench_train_graph_flag_two_ranks():
@@ -359,7 +379,7 @@ def test_bench_dump_outputs_hold_the_last_timed_step(tmp_path):
     loss counts its calls and every step moves each weight by -0.1, so --warmup 2 --steps 3 leave loss 5 and weights -0.5."""
     import json
     r = _run_bench({"PEMP_BENCH_STUB": "1", "PEMP_BENCH_DRYRUN": ""}, "--gpus", "1", "--steps", "3", "--warmup", "2",
-                   "--mode", "train", "--dump-outputs", str(tmp_path))
+                   "--mode", "train", "--full", "--dump-outputs", str(tmp_path))
     assert r.returncode == 0, r.stderr[-2000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
     assert out["steps"] == 3 and out["config"]["last_loss"] == 5.0
