@@ -51,7 +51,8 @@ typedef struct pemp_conv_desc {
                                v_mfma_f32_16x16x4_f32 (few-row launches: finer granularity); 29 = hybrid of 23
                                and 28 in one grid for launches of a few rounds (other geometries: 23)
                                -- all bit-identical results; 31..37: split-K forms of 21..27 (see below);
-                               41..44, 46 / 51, 52, 54, 56: the split3 family (see pemp_pack_split3_bf16) */
+                               41..44, 46 / 51, 52, 54, 56: the split3 family (see pemp_pack_split3_bf16);
+                               47, 49: persistent forms of 43, 46 (same family, same results) */
 } pemp_conv_desc;
 
 const char* pemp_last_error(void);
@@ -104,6 +105,10 @@ int pemp_conv2d_group_nhwc_f32(int n, const pemp_conv_desc* d, const float* cons
  * [Cout][Kpad] fp32 weight but its split form from pemp_pack_split3_bf16.  Entries: pemp_conv2d_nhwc_f32, _padv_, _splitk_,
  * _padv_splitk_, _group_ (41..44, 46).  Plain epilogue only (no stats / bnbwd / dropblock / bf16 forms); buffer-addressed geometries
  * only (no stem, <= 32 taps): an error, never a fall-back, elsewhere.
+ * Ids 47 and 49 (pemp_conv2d_nhwc_f32 / _padv_ / _splitk_ / _padv_splitk_ with no workspace; not _group_): the persistent forms
+ * of 43 (64 x 64) and 46 (256 x 128).  The grid is the number of blocks resident at once (at most the tile count) and each block
+ * walks a fixed sequence of tiles, issuing the next tile's first operand DMA before the current tile's epilogue; same tiles, same
+ * K order, same epilogue arithmetic: bit-identical to 41..46.  (41's shape has no such form: it would spill at 2 waves / SIMD.)
  * pemp_pack_split3_bf16: [Cout][Kpad] fp32 (Kpad % 32 == 0) -> [Cout][Kpad / 32][3][32] bf16 (Cout * Kpad * 6 bytes): per row and
  * 32-channel K step the h, m and l planes, channel order unchanged.                                                           */
 int pemp_pack_split3_bf16(const float* w, void* out, int cout, int kpad, void* stream);

@@ -320,6 +320,9 @@ int launch_conv_dma2_splitk(int tile, ConvArgs a, void* ws, size_t ws_bytes, hip
 // split-K form (ws as for launch_conv_dma2_splitk)
 int launch_conv_dma2_split3(int tile, ConvArgs a, void* ws, size_t ws_bytes, bool split, hipStream_t st);
 int launch_conv_dma2_group_split3(int tile, ConvGroupArgs& g, hipStream_t st);
+// persistent forms (ids 47, 49: tile = 7 -> the 64 x 64 shape of 43, 9 -> 46's 256 x 128): a resident grid walks the tiles
+int launch_conv_dma2_split3_persist(int tile, const ConvArgs& a, hipStream_t st);
+int conv_dma2_simds();                                                     // SIMDs of the current device (4 per CU)
 int pack_split3(const float* w, void* out, int cout, int kpad, hipStream_t st);
 
 }  // namespace pemp

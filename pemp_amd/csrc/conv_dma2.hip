@@ -339,7 +339,10 @@ __device__ __forceinline__ void conv_dma2_body(const ConvArgs& a, const int bid,
     // One K step.  DMA_: issue the LDS-DMA of step kt+2 (into the buffer this step frees); NEXT_: read the first
     // fragments of step kt+1.  The steady-state body has both and no branch, so that the scheduler can place the reads
     // and the DMA issue between the MFMAs of the last quarter; the last two steps are peeled.
-#define PEMP_STEP(buf_, DMA_, NEXT_)                                                                              \
+#define PEMP_STEP(buf_, DMA_, NEXT_) PEMP_STEP_X(buf_, DMA_, NEXT_, true, true)
+    // (PEMP_STEP_X: ADV_ false = the DMA_ issue is the NEXT tile's step 0, its K state already reset -- the persistent S3
+    // kernel below; WVM_ false = the barrier waits for LDS reads only, not for the vector memory counter)
+#define PEMP_STEP_X(buf_, DMA_, NEXT_, ADV_, WVM_)                                                                \
     do {                                                                                                          \
         PEMP_READ(1, buf_, 1);                                                                                    \
         __builtin_amdgcn_sched_barrier(0);                                                                        \
@@ -356,13 +359,18 @@ __device__ __forceinline__ void conv_dma2_body(const ConvArgs& a, const int bid,
             __builtin_amdgcn_sched_barrier(0);                                                                    \
         }                                                                                                         \
         /* every LDS read of `buf` by this wave has returned; this wave's DMA pieces of step kt+1 have landed */  \
-        __builtin_amdgcn_s_waitcnt(0x0070);          /* vmcnt(0) lgkmcnt(0), visible to hipcc's own wait bookkeeping */ \
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   /* (the LDS-DMA loads are not in that bookkeeping) */    \
+        if (WVM_) {                                                                                               \
+            __builtin_amdgcn_s_waitcnt(0x0070);      /* vmcnt(0) lgkmcnt(0), visible to hipcc's own wait bookkeeping */ \
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   /* (the LDS-DMA loads are not in that bookkeeping) */ \
+        } else {                                                                                                  \
+            __builtin_amdgcn_s_waitcnt(0xC07F);      /* lgkmcnt(0) only (vmcnt 63 = no wait) */                   \
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                    \
+        }                                                                                                         \
         __builtin_amdgcn_s_barrier();   /* ... everybody's: `buf` is free for step kt+2, `buf^1` holds step kt+1 */ \
         __builtin_amdgcn_sched_barrier(0);                                                                        \
         if (NEXT_) PEMP_READ(0, (buf_) ^ 1, 0);                                                                   \
         if (DMA_) {                                                                                               \
-            PEMP_ADVANCE2();                                                                                      \
+            if (ADV_) PEMP_ADVANCE2();                                                                            \
             PEMP_DMA2(buf_);                                                                                      \
         }                                                                                                         \
         PEMP_MMA(1);                    /* the last quarter of step kt covers the reads / DMA issue above */      \
@@ -414,11 +422,7 @@ __device__ __forceinline__ void conv_dma2_body(const ConvArgs& a, const int bid,
         const int buf = kt & 1;
         PEMP_STEP(buf, false, false);
     }
-#undef PEMP_STEP
-#undef PEMP_DMA2
-#undef PEMP_ADVANCE2
-#undef PEMP_READ
-#undef PEMP_MMA
+    // (the K-loop macros stay defined for conv_dma2_s3p_body below)
 
     if constexpr (SK) {
         if (sk_r >= 0) {
@@ -543,6 +547,298 @@ __global__ __launch_bounds__(NW * 64) void conv_dma2_kernel(ConvArgs a) {
     conv_dma2_body<BM, BN, WGM, NW, PADV, EPI, SK, BF16, DB, R16, S3>(a, blockIdx.x, gridDim.x);
 }
 
+// ---- persistent split3 form (tile ids 47, 49 = the shapes of 43, 46; pemp_hip.h).  (41's shape, 128 x 128 in 4 waves, needs
+// scratch at 2 waves per SIMD in this form: no id.)  The grid is the number of blocks
+// that are resident at once (occupancy x CUs, at most the tile count), and every block walks a fixed sequence of tiles: the
+// blocks of XCD x (block ids = x mod 8) share XCD x's contiguous range of the M-major tile order (xcd_tile_order's ranges), block
+// 8 i + x takes tiles i, i + gx, i + 2 gx, ... of it (gx = the XCD's block count).  No counter, no flag, no atomic: which block
+// computes a tile, and when, is all that changes -- each accumulator sees the same MFMAs in the same order as in ids 41..46, and
+// the epilogue does the same arithmetic: bit-identical.
+// What the loop buys: one block per tile starts cold (two DMA stages issued and waited for in full before its first MFMA) and
+// ends with a serial epilogue (residual loads in series with the LDS transpose and the stores).  Here, inside a block,
+//  * the NEXT tile's step-0 DMA is issued at the barrier of this tile's second-to-last K step, into the stage buffer that step
+//    frees, slotted between the MFMAs of its last quarter like a steady-state step's DMA (the per-row offsets and tap masks of
+//    the next tile are computed in front of that step: the current tile's last DMA is behind it);
+//  * the last K step's barrier waits for the LDS reads only (not for that DMA), and the waves' transpose patches go to the
+//    buffer the last step read (the other stage buffer): no extra LDS;
+//  * the residual quads of the wave tile and the scale / shift quads are requested in one batch after the last K step (behind
+//    its last quarter's MFMAs, not under them: registers), so the epilogue waits once (not once per 32 x 32 sub-tile), and its
+//    stores then issue back to back;
+//  * the next tile's step-1 DMA follows the epilogue's stores, and the wait before its first MFMA is counted past the stores
+//    (vector memory operations retire in order: stage 0 -> residual / scale loads -> stores -> stage 1).
+// Epilogue of the persistent form: conv_epilogue_lds_pre (EPI 0, no DropBlock) statement for statement, with the scale / shift
+// quads of every column group loaded by the caller together with the residual quads.
+template <int TM, int TN>
+__device__ __forceinline__ void conv_epilogue_s3p(const ConvArgs& a, f32x16 (&acc)[TM][TN], float* S, int m_base, int n_base,
+                                                  int lane, const v4f (&pre)[TM * TN * 4], const v4f (&scv)[TN], const v4f (&shv)[TN]) {
+    const bool relu = a.flags & PEMP_CONV_RELU;
+    const bool per_img = a.flags & PEMP_CONV_SHIFT_PER_IMAGE;
+    const int lr = lane & 31, lh = lane >> 5;
+    const int rr = lane >> 3, c4 = (lane & 7) * 4;
+#pragma unroll
+    for (int ni = 0; ni < TN; ++ni) {
+        const int n = n_base + ni * 32 + c4;
+        const v4f sc = scv[ni], sh = shv[ni];
+#pragma unroll
+        for (int mi = 0; mi < TM; ++mi) {
+#pragma unroll
+            for (int e = 0; e < 16; ++e) S[((e & 3) + 8 * (e >> 2) + 4 * lh) * 32 + lr] = acc[mi][ni][e];
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // this wave's writes have landed (DS is in-order per wave)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int row = rr + 8 * i;
+                const int m = m_base + mi * 32 + row;
+                const v4f v = *(const v4f*)(S + row * 32 + c4);
+                if (m < a.M) {
+                    v4f add = sh;
+                    if (per_img) add += *(const v4f*)(a.shift + (size_t)(m / a.HoWo) * a.Cout + n);
+                    if (a.res) add += pre[(mi * TN + ni) * 4 + i];
+                    v4f o;
+                    o.x = __builtin_fmaf(v.x, sc.x, add.x);      // explicit: every epilogue variant must round identically
+                    o.y = __builtin_fmaf(v.y, sc.y, add.y);
+                    o.z = __builtin_fmaf(v.z, sc.z, add.z);
+                    o.w = __builtin_fmaf(v.w, sc.w, add.w);
+                    if (relu) {
+                        o.x = fmaxf(o.x, 0.f);
+                        o.y = fmaxf(o.y, 0.f);
+                        o.z = fmaxf(o.z, 0.f);
+                        o.w = fmaxf(o.w, 0.f);
+                    }
+                    store_quad(a.y, (size_t)m * a.ldy + n, o, a.flags & PEMP_CONV_BF16_IO);
+                }
+            }
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // reads done before the patch is rewritten
+        }
+    }
+}
+
+template <int BM, int BN, int WGM, int NW, bool PADV>
+__device__ __forceinline__ void conv_dma2_s3p_body(const ConvArgs& a) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    constexpr bool S3 = true, R16 = false, BF16 = false;       // the K-loop macros' switches
+    constexpr int WGN = NW / WGM;
+    constexpr int RPI = NW * 8;
+    constexpr int WM = BM / WGM, WN = BN / WGN;
+    constexpr int TM = WM / 32, TN = WN / 32;
+    constexpr int BQ = 12;
+    static_assert((BN * BQ) % (NW * 64) == 0, "S3: whole B DMA rounds");
+    constexpr int AL = BM / RPI, BL = BN * BQ / (NW * 64);
+    constexpr int NMF = 6 * TM * TN, NDS = 2 * TM + 3 * TN, NDMA = AL + BL;
+    constexpr int PER = (NDS + NDMA + NMF - 1) / NMF;
+    constexpr int NST = TM * TN * 4;            // epilogue stores per thread of a wave tile inside the output
+    static_assert(NDMA + NST <= 63, "vmcnt range");
+    static_assert(NW <= BM / 32 + 3 * BN / 64, "one 4 KB transpose patch per wave inside ONE stage buffer");
+
+    extern __shared__ __attribute__((aligned(16))) v4f smem[];
+    v4f* As = smem;                      // [2][BM][8]
+    v4f* Bs = smem + 2 * BM * 8;         // [2][BN][BQ]
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wm0 = (wave / WGN) * WM;
+    const int wn0 = (wave % WGN) * WN;
+    const int lr = lane & 31, lh = lane >> 5;
+
+    // the block's tile sequence: tiles [t_first + j] of its XCD's range, j = idx, idx + gx, ... < t_cnt
+    const int ntn = a.Cout / BN;
+    const int T = (a.M + BM - 1) / BM * ntn;
+    const int xcd = (int)blockIdx.x & 7, idx = (int)blockIdx.x >> 3;
+    const int q8 = T >> 3, r8 = T & 7;
+    const int t_first = xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8;
+    const int t_cnt = q8 + (xcd < r8 ? 1 : 0);
+    const int gx = ((int)gridDim.x - xcd + 7) >> 3;
+    if (idx >= t_cnt) return;                   // (the launch clamps the grid to the tile count: not expected)
+    int j = idx;
+    int m0 = (a.bm_first + (t_first + j) / ntn) * BM, n0 = ((t_first + j) % ntn) * BN;
+
+    const int p = tid & 7;
+    const int r = tid >> 3;
+    const int sq = p ^ ((r >> 1) & 7);
+    const int bias_pix = a.pad * a.W + a.pad;
+    const __amdgpu_buffer_rsrc_t rx =
+        __builtin_amdgcn_make_buffer_rsrc((void*)(a.x - (ptrdiff_t)bias_pix * a.ldx), 0, 0x80000000u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void*)a.w, 0, 0x80000000u, 0x00020000);
+    const unsigned padv_off = PADV ? (unsigned)((const char*)a.padv - (const char*)(a.x - (ptrdiff_t)bias_pix * a.ldx)) + sq * 16 : 0x80000000u;
+    unsigned a_voff[AL], a_inv[AL], b_voff[BL];
+    // per-row byte offsets and tap masks of the tile at (m0_, n0_): conv_dma2_body's, expression for expression
+    auto offsets = [&](const int m0_, const int n0_) {
+#pragma unroll
+        for (int i = 0; i < AL; ++i) {
+            const int m = m0_ + r + RPI * i;
+            const bool ok = m < a.M;
+            const int mm = ok ? m : 0;
+            const int img = mm / a.HoWo;
+            const int rem = mm - img * a.HoWo;
+            const int ho = rem / a.Wo;
+            const int wo = rem - ho * a.Wo;
+            const int hi0 = ho * a.stride - a.pad;
+            const int wi0 = wo * a.stride - a.pad;
+            a_voff[i] = (unsigned)(((img * a.H + hi0) * a.W + wi0 + bias_pix) * a.ldx + sq * 4) * 4u;
+            unsigned mask = 0;
+            int kh = 0, kw = 0;
+            for (int t = 0; t < a.ntaps; ++t) {
+                const int hi = hi0 + kh * a.dil, wi = wi0 + kw * a.dil;
+                if (ok && (unsigned)hi < (unsigned)a.H && (unsigned)wi < (unsigned)a.W) mask |= 1u << t;
+                if (++kw == a.KW) {
+                    kw = 0;
+                    ++kh;
+                }
+            }
+            a_inv[i] = ~mask;
+        }
+#pragma unroll
+        for (int i = 0; i < BL; ++i) {
+            const int q = i * NW * 64 + tid, row = q / 12, pos = q - row * 12;
+            const int src = (pos & ~3) | ((pos & 3) ^ ((row >> 2) & 3));
+            b_voff[i] = (unsigned)((n0_ + row) * a.Kpad * 6 + src * 16);
+        }
+    };
+    offsets(m0, n0);
+
+    int tap = 0, cb = 0, kh_i = 0, kw_i = 0;
+    const int tapw = a.dil * a.ldx * 4, taph = a.dil * a.W * a.ldx * 4;
+    int multi, s_kw, s_ntaps;
+    asm volatile("s_nop 0\n\tv_readfirstlane_b32 %0, %3\n\tv_readfirstlane_b32 %1, %4\n\tv_readfirstlane_b32 %2, %5\n\ts_nop 4"
+                 : "=s"(multi), "=s"(s_kw), "=s"(s_ntaps)
+                 : "v"(a.ntaps > 1 ? 1 : 0), "v"(a.KW), "v"(a.ntaps));
+    const int nkl = a.nk;
+
+    PEMP_DMA2(0);
+    if (nkl > 1) {
+        PEMP_ADVANCE2();
+        PEMP_DMA2(1);
+        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NDMA) : "memory");
+    } else {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_sched_barrier(0);
+
+    const int rsw = (lr >> 1) & 7;
+    const int arow = (wm0 + lr) * 8, brow = (wn0 + lr) * 8;
+    v4f af[2][1], bf[2][1];                      // (the macros' other variants: never used here)
+    const int r16 = lane & 15, g16 = lane >> 4;
+    const int rsw16 = (r16 >> 1) & 7;
+    const int arow16 = (wm0 + r16) * 32 + (g16 >> 1), brow16 = (wn0 + r16) * 32 + (g16 >> 1);
+    float a16[2][2], b16[2][1][2];
+    v4f acc16[1];
+    v4f af3[2][TM][2], bf3[2][TN][3];
+    const int brow3 = (wn0 + lr) * 12, bsw3 = (lr >> 2) & 3;
+    const int rr_ = lane >> 3, c4_ = (lane & 7) * 4;
+
+    int pb = 0;                                  // stage buffer of the tile's K step 0
+    for (;;) {
+        f32x16 acc[TM][TN];
+#pragma unroll
+        for (int mi = 0; mi < TM; ++mi)
+#pragma unroll
+            for (int ni = 0; ni < TN; ++ni)
+#pragma unroll
+                for (int e = 0; e < 16; ++e) acc[mi][ni][e] = 0.f;
+        const int jn = j + gx;
+        const bool more = jn < t_cnt;
+        const int m0n = more ? (a.bm_first + (t_first + jn) / ntn) * BM : m0, n0n = more ? ((t_first + jn) % ntn) * BN : n0;
+
+        int kt = 0;
+        PEMP_READ(0, pb, 0);
+        for (; kt + 2 < nkl; ++kt) {
+            const int buf = (kt + pb) & 1;
+            PEMP_STEP(buf, true, true);
+        }
+        // every DMA of this tile is issued: the offsets and the K state become the next tile's.  After the block's last tile the
+        // step-0 DMA below still goes out (ONE form of the step: two would hold two sets of accumulators), with every offset
+        // past the 2 GiB range: the hardware writes zeros into the free buffer and reads no memory
+        if (more) {
+            offsets(m0n, n0n);
+        } else {
+#pragma unroll
+            for (int i = 0; i < AL; ++i) {
+                a_voff[i] = 0x80000000u;
+                a_inv[i] = 0u;
+            }
+#pragma unroll
+            for (int i = 0; i < BL; ++i) b_voff[i] = 0x80000000u;
+        }
+        tap = 0;
+        cb = 0;
+        kh_i = 0;
+        kw_i = 0;
+        if (kt + 1 < nkl) {
+            const int buf = (kt + pb) & 1;
+            PEMP_STEP_X(buf, true, true, false, true);       // + the next tile's step 0, into `buf`
+            ++kt;
+        }
+        const int bl = (kt + pb) & 1;            // the last step's buffer: the transpose patches go there
+        v4f rres[TM * TN * 4], scv[TN], shv[TN];
+        auto epi_loads = [&]() {
+            const bool per_img = a.flags & PEMP_CONV_SHIFT_PER_IMAGE;
+#pragma unroll
+            for (int ni = 0; ni < TN; ++ni) {
+                const int n = n0 + wn0 + ni * 32 + c4_;
+                scv[ni] = a.scale ? *(const v4f*)(a.scale + n) : v4f{1.f, 1.f, 1.f, 1.f};
+                shv[ni] = (a.shift && !per_img) ? *(const v4f*)(a.shift + n) : v4f{0.f, 0.f, 0.f, 0.f};
+            }
+#pragma unroll
+            for (int i = 0; i < TM * TN * 4; ++i) rres[i] = v4f{0.f, 0.f, 0.f, 0.f};
+            if (a.res) {
+#pragma unroll
+                for (int mi = 0; mi < TM; ++mi)
+#pragma unroll
+                    for (int ni = 0; ni < TN; ++ni)
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) {
+                            const int m = m0 + wm0 + mi * 32 + rr_ + 8 * i, n = n0 + wn0 + ni * 32 + c4_;
+                            rres[(mi * TN + ni) * 4 + i] = m < a.M ? load_quad(a.res, (size_t)m * a.ldr + n, a.flags & PEMP_CONV_BF16_IO)
+                                                                   : v4f{0.f, 0.f, 0.f, 0.f};
+                        }
+            }
+        };
+        PEMP_STEP_X(bl, false, false, true, false);      // the barrier waits for LDS reads only: the next tile's DMA flies on
+        epi_loads();             // behind the last step's MFMAs: in front of that step they would cost 64 x 64 its fourth wave per
+                                 // SIMD (scratch at 128 VGPRs), and 256 x 128 has no registers left under them
+
+        float* patch = wave < BM / 32 ? (float*)(As + bl * BM * 8 + wave * 256) : (float*)(Bs + bl * BN * BQ + (wave - BM / 32) * 256);
+        conv_epilogue_s3p<TM, TN>(a, acc, patch, m0 + wm0, n0 + wn0, lane, rres, scv, shv);
+        if (!more) {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // no LDS-DMA outlives the block
+            break;
+        }
+
+        // the next tile: its step 1 goes into `bl` once every wave is done with its patch
+        const int pbn = (pb + nkl) & 1;
+        __builtin_amdgcn_s_barrier();
+        if (nkl > 1) {
+            PEMP_ADVANCE2();
+            PEMP_DMA2(bl);
+            if (m0 + wm0 + WM <= a.M) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NDMA + NST) : "memory");   // step 0 has landed
+            else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NDMA) : "memory");     // (fewer stores than NST: do not count them)
+        } else {
+            PEMP_DMA2(pbn);
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
+        __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_sched_barrier(0);
+        j = jn;
+        m0 = m0n;
+        n0 = n0n;
+        pb = pbn;
+    }
+#endif
+}
+
+// (waves per SIMD: 43's shape is held to 4 by its LDS -- the registers must not take that below 4)
+template <int BM, int BN, int WGM, int NW, bool PADV>
+__global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(BM == 64 ? 4 : 2))) void conv_dma2_s3p_kernel(ConvArgs a) {
+    conv_dma2_s3p_body<BM, BN, WGM, NW, PADV>(a);
+}
+#undef PEMP_STEP_X
+#undef PEMP_STEP
+#undef PEMP_DMA2
+#undef PEMP_ADVANCE2
+#undef PEMP_READ
+#undef PEMP_MMA
+
 // Several INDEPENDENT convs of the same tile shape in ONE launch: member i owns the blocks [first[i], first[i] + nblk[i]) (the
 // first[] are multiples of 8, so that a block's XCD is the same function of its index inside the member as in a launch of its
 // own; the few blocks in between return at once).  A one-episode step has 5202 feature rows -- 41 to 82 tiles per conv on 256
@@ -598,8 +894,8 @@ __global__ __launch_bounds__(256) void conv_dma2_hybrid_kernel(ConvGroupArgs g) 
     }
 }
 
-// rows of an M x Cout conv that go to the 64 x 64 tile in the hybrid launch (the rest: 16-row tiles); 0 = no such split
-int conv_dma2_hybrid_rows(int M, int Cout) {
+// SIMDs of the current device (4 per CU; filled on first use)
+int conv_dma2_simds() {
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 63;        // no device (CPU-side query): the MI355X count
     if (!g_simds_of[dev]) {
@@ -607,7 +903,12 @@ int conv_dma2_hybrid_rows(int M, int Cout) {
         if (dev == 63 || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
         g_simds_of[dev] = 4 * cus;
     }
-    const int g_simds = g_simds_of[dev];
+    return g_simds_of[dev];
+}
+
+// rows of an M x Cout conv that go to the 64 x 64 tile in the hybrid launch (the rest: 16-row tiles); 0 = no such split
+int conv_dma2_hybrid_rows(int M, int Cout) {
+    const int g_simds = conv_dma2_simds();
     if (M <= 0 || Cout < 64 || Cout % 64) return 0;
     const int per32 = Cout / 32;                                 // 32 x 32 wave tiles per 32 output rows
     const int rounds = (int)(((long long)M / 32 * per32) / g_simds);        // whole rounds the 32-row tiles fill
@@ -870,6 +1171,46 @@ int launch_conv_dma2_split3(int tile, ConvArgs a, void* ws, size_t ws_bytes, boo
         }
     }
     return launch_s3_tile<false>(tile, a, cdiv(a.M, bm) * (a.Cout / bn), st);
+}
+
+// persistent forms (ids 47, 49): grid = resident blocks (occupancy of the instantiation x CUs, taken once), at most the tile count
+template <int BM, int BN, int WGM, int NW>
+static int launch_dma2_s3p(const ConvArgs& a, hipStream_t st) {
+    const size_t lds = (size_t)2 * (8 * BM + 12 * BN) * sizeof(v4f);
+    auto kern = a.padv ? conv_dma2_s3p_kernel<BM, BN, WGM, NW, true> : conv_dma2_s3p_kernel<BM, BN, WGM, NW, false>;
+    if (lds > 64 * 1024) {
+        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) {
+            set_error("hipFuncSetAttribute(lds=%zu): %s", lds, hipGetErrorString(e));
+            return (int)e;
+        }
+    }
+    static int occ[2] = {0, 0};          // blocks per CU of the two instantiations (racing fills write the same value)
+    int& o = occ[a.padv ? 1 : 0];
+    if (!o) {
+        int v = 0;
+        hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, (const void*)kern, NW * 64, lds);
+        if (e != hipSuccess || v <= 0) {
+            set_error("conv split3 persistent: occupancy query failed (%s, %d blocks)", hipGetErrorString(e), v);
+            return -1;
+        }
+        o = v;
+    }
+    const long long tiles = (long long)cdiv(a.M, BM) * (a.Cout / BN);
+    long long grid = (long long)o * (conv_dma2_simds() / 4);
+    if (grid < 8) grid = 8;              // every XCD's range needs a block
+    if (grid > tiles) grid = tiles;
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(NW * 64), lds, st, a);
+    return launch_status("conv_dma2/split3/persistent");
+}
+
+int launch_conv_dma2_split3_persist(int tile, const ConvArgs& a, hipStream_t st) {
+    if (a.stats || a.rowmask || (a.flags & PEMP_CONV_BF16_IO)) {
+        set_error("conv split3: tile %d / epilogue outside the family", tile);
+        return -1;
+    }
+    if (tile == 9) return launch_dma2_s3p<256, 128, 8, 8>(a, st);
+    return launch_dma2_s3p<64, 64, 2, 4>(a, st);
 }
 
 int launch_conv_dma2_group_split3(int tile, ConvGroupArgs& g, hipStream_t st) {

@@ -344,11 +344,16 @@ static int conv2d_impl(const pemp_conv_desc* d, const float* x, const float* w, 
         tile = 3;
     }
     hipStream_t st = (hipStream_t)stream;
-    if ((tile >= 41 && tile <= 46) || (tile >= 51 && tile <= 56)) {     // split3 family (conv_dma2.hip, S3): w from pemp_pack_split3_bf16
+    if ((tile >= 41 && tile <= 49) || (tile >= 51 && tile <= 56)) {     // split3 family (conv_dma2.hip, S3): w from pemp_pack_split3_bf16
         PEMP_REQUIRE(tile != 53, "conv2d: no split-K variant of the 64 x 64 tile");
         PEMP_REQUIRE(tile != 45 && tile != 55, "conv2d: no split3 form of the 128 x 64 8-wave tile");
+        PEMP_REQUIRE(tile != 48, "conv2d: no persistent split3 form of the 128 x 128 4-wave tile");
         PEMP_REQUIRE(!stem && conv_dma2_supported(a) && (long long)a.Cout * a.Kpad * 6 < (1ll << 31),
                      "conv2d: split3 tile %d needs a geometry of the buffer-addressed kernels (no stem, <= 32 taps, operands < 2 GiB)", tile);
+        if (tile == 47 || tile == 49) {    // persistent forms of 43 and 46 (same results)
+            PEMP_REQUIRE(tile == 47 || a.Cout % 128 == 0, "conv2d: tile N=128 needs Cout %% 128 == 0");
+            return launch_conv_dma2_split3_persist(tile - 40, a, st);
+        }
         const int t = tile > 50 ? tile - 50 : tile - 40;
         PEMP_REQUIRE((t != 1 && t != 4 && t != 6) || a.Cout % 128 == 0, "conv2d: tile N=128 needs Cout %% 128 == 0");
         return launch_conv_dma2_split3(t, a, ws, ws_bytes, tile > 50, st);

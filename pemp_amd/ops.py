@@ -76,8 +76,10 @@ TILE_VARIANTS = {13: (64, 64), 14: (128, 128), 12: (128, 64), 11: (128, 128), 15
                  29: (64, 64)}
 #: the split3 family (pemp_hip.h: fp32 operands split into three bf16 pieces on v_mfma_f32_32x32x16_bf16, fp32 accuracy; the
 #: shapes of 21..24 / 26): the variants of a layer that carries split weights (ConvParams.w3) -- bit-identical among themselves,
-#: not to the fp32-chain ids above.  51..56: their split-K forms (EVAL_SPLITK).
-SPLIT3_TILES = (43, 42, 41, 44, 46)
+#: not to the fp32-chain ids above.  51..56: their split-K forms (EVAL_SPLITK).  47 / 49: persistent forms of 43 / 46 (a resident
+#: grid that walks the tiles and overlaps one tile's epilogue with the next one's operand DMA; single convs only, no grouped form).
+SPLIT3_TILES = (43, 42, 41, 44, 46, 47, 49)
+SPLIT3_PERSISTENT = {47: 43, 49: 46}
 SPLIT3_SPLITK_TILES = (51, 52, 54, 56)
 SPLIT3_DEFAULT_TILE = 43
 AUTOTUNE = True
@@ -214,6 +216,7 @@ def _pick_tile(launch, p, key, cout, only=None):
 
 def _tile_bn(t):
     """BN of tile id ``t``: the split-K ids (31..37, 51..56) and the split3 ids (41..46) have the shapes of 21..27."""
+    t = SPLIT3_PERSISTENT.get(t, t)
     return TILE_VARIANTS[t - 30 if t > 50 else t - 20 if t > 40 else t - 10 if t > 30 else t][1]
 
 
@@ -495,7 +498,7 @@ def conv2d_group(xs, ps, outs, pad_values=None, residuals=None, tile=0):
             tile = SPLIT3_DEFAULT_TILE
             if _tunes(max(d[0] * d[5] * d[6] for d in descs)):
                 tile = _pick_tile(launch, None, key, min(p.cout for p in ps),
-                                  only=[t for t in SPLIT3_TILES if all(p.cout % _tile_bn(t) == 0 for p in ps)])
+                                  only=[t for t in SPLIT3_TILES if t not in SPLIT3_PERSISTENT and all(p.cout % _tile_bn(t) == 0 for p in ps)])
         if tile is None:
             if _tunes(max(d[0] * d[5] * d[6] for d in descs)):
                 tile = _pick_tile(launch, None, key, min(p.cout for p in ps),

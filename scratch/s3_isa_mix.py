@@ -16,9 +16,12 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-# tile id -> (BM, BN, NW); the wave grid (WGM) is read from the kernel's name
-TILES = {43: (64, 64, 4), 42: (128, 64, 4), 41: (128, 128, 4), 44: (128, 128, 8), 46: (256, 128, 8)}
+# tile id -> (BM, BN, NW); the wave grid (WGM) is read from the kernel's name.  47 / 49: the persistent forms of 43 / 46
+# (conv_dma2_s3p_kernel: no split-K instantiation)
+TILES = {43: (64, 64, 4), 42: (128, 64, 4), 41: (128, 128, 4), 44: (128, 128, 8), 46: (256, 128, 8), 47: (64, 64, 4), 49: (256, 128, 8)}
+PERSISTENT = (47, 49)
 NAME = re.compile(r"^(_ZN4pemp16conv_dma2_kernelILi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELb([01])ELi0ELb([01])ELb0ELb0ELb0ELb1EEEvNS_8ConvArgsE):")
+NAME_P = re.compile(r"^(_ZN4pemp20conv_dma2_s3p_kernelILi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELb([01])()EEEvNS_8ConvArgsE):")
 NOT_SALU = ("s_waitcnt", "s_barrier", "s_nop", "s_cbranch", "s_branch", "s_setprio", "s_endpgm", "s_sleep")
 
 
@@ -51,7 +54,7 @@ def kernels(asm):
     out, cur, blocks = {}, None, None
     with open(asm) as f:
         for line in f:
-            m = NAME.match(line)
+            m = NAME.match(line) or NAME_P.match(line)
             if m:
                 cur = m.group(1)
                 blocks = out[cur] = [("entry", [])]
@@ -105,8 +108,12 @@ def main():
           f" {'VGPR+AGPR':>9} {'scratch':>7} {'occ':>4}")
     for tid, (bm, bn, nw) in TILES.items():
         for name, blocks in ks.items():
-            m = NAME.match(name + ":")
-            if (int(m.group(2)), int(m.group(3)), int(m.group(5))) != (bm, bn, nw) or m.group(6) != str(int(padv)) or m.group(7) != str(int(sk)):
+            m = (NAME_P if tid in PERSISTENT else NAME).match(name + ":")
+            if not m or (int(m.group(2)), int(m.group(3)), int(m.group(5))) != (bm, bn, nw) or m.group(6) != str(int(padv)):
+                continue
+            if tid in PERSISTENT and sk:
+                continue
+            if tid not in PERSISTENT and m.group(7) != str(int(sk)):
                 continue
             wgm = int(m.group(4))
             wm, wn = bm // wgm, bn // (nw // wgm)

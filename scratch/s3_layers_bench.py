@@ -15,7 +15,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from pemp_amd import ops  # noqa: E402
 
-UNSPLIT = (43, 42, 41, 44, 46)
+UNSPLIT = (43, 42, 41, 44, 46, 47, 49)     # 47 / 49: persistent forms of 43 / 46
 SPLIT = (52, 51, 54, 56)
 # (cin, cout, k, dil, residual, padding value): the six geometries that carry ~81 % of the step's conv time, and the 3 x 3 layer
 # once more with a padding value (the PADV instantiation)
