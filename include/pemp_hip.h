@@ -545,6 +545,30 @@ int pemp_weighted_gap_f32(const float* feat, int ldf, const float* mask, float* 
 int pemp_scale_add_nhwc_f32(const float* x, int ldx, const float* m, const float* r, int ldr, float* y, int ldy,
                             long long npix, int C, void* stream);
 
+/* ---- CANet inference (networks/canet.py, entry/canet.py) --------------------------------------------------------------
+ * Support vector of the dense comparison (canet.py:175-178): feat NHWC [B*S][h][w][C] (ldf), mask [B*S][2][H][W] (plane 0
+ * is read, sampled nearest to h x w with ATen's rule min(floor(dst * (float)H / h), H - 1)) ->
+ * out[b][c] = mean_s( sum_p f m / (sum_p m + 1e-5) ).  C % 4 == 0; fixed summation order.                               */
+int pemp_canet_support_vector_f32(const float* feat, int ldf, const float* mask, float* out, int B, int S, int h, int w,
+                                  int H, int W, int C, void* stream);
+/* The z half of layer55 (canet.py:179-181: a 3x3, dilation dil, zero padding dil conv over cat(query, z broadcast)):
+ * T[b][tap][co] = sum_ci wz[tap][co][ci] z[b][ci] (T: [B][9][Cout] scratch of the caller), then
+ * R[b][y][x][co] = sum of T[b][tap][co] over the taps whose source pixel lies inside the image, in tap order (NHWC, pixel
+ * stride ldr).  R is the `residual` of the conv over the query channels: relu(conv + bias + R) = relu(layer55(cat)).    */
+int pemp_canet_zterm_f32(const float* wz, const float* z, float* T, float* R, int ldr, int B, int h, int w, int Cin,
+                         int Cout, int dil, void* stream);
+/* Input of a pre-activation residual block (the leading nn.ReLU of canet.py:103-104 and the cat of :193):
+ * y[b][p][0..C) = relu(x[b][p][:]); nhist == 2: also y[b][p][C..C+2) = relu(history), read from row b of hist [B][2][HW]
+ * (slot == NULL), from row slot[b] of a table hist [nslots][2][HW] (slot: device int32 [B]; a slot outside 0..nslots-1:
+ * zeros, "no history yet", data_kits/pascal_voc.py:423-424), or zeros (hist == NULL).  nhist == 0: the ReLU copy only.  C, ldx, ldy multiples of 4; ldx >= C, ldy >= C + nhist.         */
+int pemp_canet_block_input_f32(const float* x, int ldx, const float* hist, const int* slot, int nslots, float* y, int ldy,
+                               int B, int HW, int C, int nhist, void* stream);
+/* F.softmax(pred, dim=1) of the low-resolution logits [B][2][HW] and its write-back (entry/canet.py:52,77-80): into row
+ * slot[b] of table [nslots][2][HW] for every b with 0 <= slot[b] < nslots (table, slot may be NULL together) and / or into
+ * out [B][2][HW] (may be NULL).  The caller names no slot twice in one call.                                             */
+int pemp_canet_history_update_f32(const float* logits, float* table, const int* slot, int nslots, float* out, int B,
+                                  int HW, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -142,6 +142,11 @@ SYMBOLS = {
                                          + [c_fp]),
     "pemp_weighted_gap_f32": (c_int, [c_fp, c_int, c_fp, c_fp] + [c_int] * 5 + [c_fp]),
     "pemp_scale_add_nhwc_f32": (c_int, [c_fp, c_int, c_fp, c_fp, c_int, c_fp, c_int, C.c_longlong, c_int, c_fp]),
+    # CANet inference
+    "pemp_canet_support_vector_f32": (c_int, [c_fp, c_int, c_fp, c_fp] + [c_int] * 7 + [c_fp]),
+    "pemp_canet_zterm_f32": (c_int, [c_fp, c_fp, c_fp, c_fp] + [c_int] * 7 + [c_fp]),
+    "pemp_canet_block_input_f32": (c_int, [c_fp, c_int, c_fp, c_fp, c_int, c_fp] + [c_int] * 5 + [c_fp]),
+    "pemp_canet_history_update_f32": (c_int, [c_fp, c_fp, c_fp, c_int, c_fp, c_int, c_int, c_fp]),
 }
 
 ABI_VERSION = 2          # include/pemp_hip.h: PEMP_ABI_VERSION

@@ -163,12 +163,36 @@ class OneExampleLoader(PascalVOCEpisodes):
         return self
 
 
+class PascalVOCCaNetEpisodes(PascalVOCEpisodes):
+    """``PascalVOCTestCaNet`` of the reference (pascal_voc.py:434-459): the evaluation episodes of CANet.  The sampler makes the
+    same two ``RandomState`` calls per task as ``PascalVOCEpisodes`` (pascal_voc.py:318-323, ``one_cls`` is not read there) and
+    also keeps the query's index in its class list: ``history_key(i)`` = (class, query index), the key under which the
+    reference stores the query's last softmax (``history_mask_list[cls][index]``, :324,422; entry/canet.py:77-80)."""
+
+    def __init__(self, cfg, split, shot, query=1):
+        self.keys = []
+        super().__init__(cfg, split, shot, query, train=False, one_cls=0)
+
+    def sample_tasks(self):
+        self.tasks, self.keys = [], []
+        for _ in range(len(self)):
+            cls = self.sampler.choice(self.classes)
+            indices = self.sampler.choice(self.idx_by_class[cls], size=self.shot + self.query, replace=False)
+            self.tasks.append((int(cls), [self.sample_by_class[cls][j] for j in indices]))
+            self.keys.append((int(cls), int(indices[self.shot])))
+
+    def history_key(self, i):
+        return self.keys[i]
+
+
 def load(cfg, train_mode, split, shot, query=1, one_cls=0):
     """``pascal_voc.load`` / ``datasets.load`` of the reference (data_kits/datasets.py:53-72, pascal_voc.py:462-531) for the modes
-    this build runs: -> (dataset, num_classes).  ``train_mode``: "train" | "test" | "eval_online"."""
+    this build runs: -> (dataset, num_classes).  ``train_mode``: "train" | "test" | "eval_online" | "test_canet"."""
     if cfg.get("dataset", "PASCAL") != "PASCAL":
         raise NotImplementedError("COCO-20i from disk needs pycocotools (data_kits/coco.py:7), which this image does not have; "
                                   "COCO-shaped SYNTHETIC episodes run without data.base_dir")
+    if train_mode == "test_canet":
+        return PascalVOCCaNetEpisodes(cfg, split, shot, query), 20
     if train_mode not in ("train", "test", "eval_online"):
-        raise ValueError(f"Not support training mode `{train_mode}`. Selected from [train, test, eval_online]")
+        raise ValueError(f"Not support training mode `{train_mode}`. Selected from [train, test, eval_online, test_canet]")
     return PascalVOCEpisodes(cfg, split, shot, query, train=train_mode == "train", one_cls=one_cls), 20

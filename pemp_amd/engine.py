@@ -114,17 +114,21 @@ class ResNetEngine:
         for name in ("layer1", "layer2", "layer3"):
             self.stages.append([_BlockPlan(b, dtype=arena.dtype) for b in getattr(prm, name)])
 
-    def _block(self, x, bp, tag, c1_shift=None, ds_shift=None):
+    def _block(self, x, bp, tag, c1_shift=None, ds_shift=None, out=None):
+        """``out``: where the block's result goes (an NHWC view, e.g. a channel slice of a wider buffer); None: the arena's
+        ping-pong buffer of ``tag``."""
         a = self.arena
         n, h, w, _ = x.shape
         ho = ops.conv_out_size(h, 1, bp.c1.stride, 0, 1)
         wo = ops.conv_out_size(w, 1, bp.c1.stride, 0, 1)
+        if out is None:
+            out = a.get(("blk", tag), (n, ho, wo, bp.c3.cout))
         if bp.ds is not None and c1_shift is None and ds_shift is None and 0 < n * ho * wo <= GROUP_MAX_ROWS and x.dtype == torch.float32:
             # small step: conv1 and the downsample conv read the same x -- one grouped launch
             y1, res = ops.conv2d_group([x, x], [bp.c1, bp.ds], [a.get("y1", (n, ho, wo, bp.c1.cout)),
                                                                 a.get("res", (n, ho, wo, bp.ds.cout))])
             y2 = ops.conv2d(y1, bp.c2, out=a.get("y2", (n, ho, wo, bp.c2.cout)))
-            return ops.conv2d(y2, bp.c3, out=a.get(("blk", tag), (n, ho, wo, bp.c3.cout)), residual=res)
+            return ops.conv2d(y2, bp.c3, out=out, residual=res)
         y1 = ops.conv2d(x, bp.c1, out=a.get("y1", (n, ho, wo, bp.c1.cout)),
                         shift_override=c1_shift, per_image_shift=c1_shift is not None)
         y2 = ops.conv2d(y1, bp.c2, out=a.get("y2", (n, ho, wo, bp.c2.cout)))
@@ -133,7 +137,7 @@ class ResNetEngine:
                              shift_override=ds_shift, per_image_shift=ds_shift is not None)
         else:
             res = x
-        return ops.conv2d(y2, bp.c3, out=a.get(("blk", tag), (n, ho, wo, bp.c3.cout)), residual=res)
+        return ops.conv2d(y2, bp.c3, out=out, residual=res)
 
     def stem_forward(self, x4):
         a = self.arena
@@ -146,11 +150,14 @@ class ResNetEngine:
             x = ops.convert(x, a.get("pool16", (n, hp, wp, 64)))
         return x
 
-    def forward(self, x4):
+    def forward(self, x4, stage_outs=None):
+        """``stage_outs`` {stage index: NHWC view}: the last block of that stage writes there (CANet: layer2 and layer3 into
+        the channel slices of one buffer, so that their concatenation is never formed)."""
         x = self.stem_forward(x4)
         for si, blocks in enumerate(self.stages):
             for bi, bp in enumerate(blocks):
-                x = self._block(x, bp, (si, bi & 1))
+                out = stage_outs.get(si) if stage_outs and bi == len(blocks) - 1 else None
+                x = self._block(x, bp, (si, bi & 1), out=out)
         return x
 
 
@@ -333,14 +340,15 @@ class ASPPV2Engine:
 
 
 class ASPPEngine:
-    """purifier.6 of stage 2: conv -> ReLU per branch, no BN (reference: backbones.py:310-321)."""
+    """purifier.6 of stage 2: conv -> ReLU per branch, no BN (reference: backbones.py:310-321).  ``out_relu``: a ReLU behind
+    ``layer6`` (CANet's ASPP, networks/canet.py:96-100)."""
 
-    def __init__(self, prm, arena):
+    def __init__(self, prm, arena, out_relu=False):
         self.arena = arena
         self.br = [conv_params(getattr(prm, f"aspp_{i}")[0], None, relu=True) for i in range(5)]
         midc = self.br[0].cout
         self.l6_global = conv_params(prm.layer6, None, relu=False, in_slice=(0, midc))
-        self.l6_main = conv_params(prm.layer6, None, relu=False, in_slice=(midc, 5 * midc))
+        self.l6_main = conv_params(prm.layer6, None, relu=out_relu, in_slice=(midc, 5 * midc))
         self.l6_main.shift = None
         self.midc = midc
 

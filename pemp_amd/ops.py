@@ -1068,3 +1068,109 @@ def scale_add(x, mask=None, residual=None, out=None):
     _lib.check(lib.pemp_scale_add_nhwc_f32(_p(x), ldx, _p(mask), _p(residual), ldr, _p(out), _nhwc(out, "out"), n * h * w, c,
                                            _stream()), "scale_add")
     return out
+
+
+# -- CANet inference (csrc/canet.hip) -----------------------------------------------------------------------------------------
+def canet_support_vector(feat, sup_mask, S, out=None):
+    """CANet's support vector (networks/canet.py:175-178): feat NHWC [B*S,h,w,C], sup_mask contiguous fp32 [B*S,2,H,W] (plane 0
+    is sampled nearest to h x w) -> [B,C] = mean over the shots of sum(f m) / (sum(m) + 1e-5)."""
+    lib = _lib.load()
+    _chk_dev(feat, sup_mask, out)
+    ldf = _nhwc(feat, "feat")
+    n, h, w, c = feat.shape
+    if sup_mask.dim() != 4 or n % S or sup_mask.shape[0] != n or sup_mask.shape[1] != 2 or not sup_mask.is_contiguous() \
+            or sup_mask.dtype != torch.float32:
+        raise ValueError(f"canet_support_vector: sup_mask must be contiguous fp32 [B*S,2,H,W] for feat {tuple(feat.shape)}, S={S}")
+    H, W = sup_mask.shape[-2:]
+    if out is None:
+        out = torch.empty((n // S, c), dtype=torch.float32, device=feat.device)
+    if tuple(out.shape) != (n // S, c) or not out.is_contiguous() or out.dtype != torch.float32:
+        raise ValueError("canet_support_vector: out must be contiguous fp32 [B,C]")
+    _lib.check(lib.pemp_canet_support_vector_f32(_p(feat), ldf, _p(sup_mask), _p(out), n // S, S, h, w, H, W, c, _stream()),
+               "canet_support_vector")
+    return out
+
+
+def pack_canet_zweights(w_oihw):
+    """The z slice of layer55's weight [Cout,Cin_z,3,3] -> contiguous fp32 [9,Cout,Cin_z] (tap-major, Cin contiguous): the
+    operand of ``canet_zterm``.  Packed once, when the engine is built."""
+    co, ci, kh, kw = w_oihw.shape
+    if (kh, kw) != (3, 3):
+        raise ValueError("pack_canet_zweights: a 3x3 kernel is expected")
+    return w_oihw.detach().float().permute(2, 3, 0, 1).reshape(9, co, ci).contiguous()
+
+
+def canet_zterm(wz, z, h, w, dil, out=None, taps=None):
+    """The support half of CANet's layer55 (canet.py:179-181) without the broadcast: wz [9,Cout,Cin] (pack_canet_zweights),
+    z [B,Cin] -> R NHWC [B,h,w,Cout], the sum over the in-image taps of W_z[tap] z: the ``residual`` of the conv over the query
+    channels.  ``taps``: the [B,9,Cout] intermediate (a scratch buffer; returned values are the per-tap products)."""
+    lib = _lib.load()
+    _chk_dev(wz, z, out, taps)
+    if wz.dim() != 3 or wz.shape[0] != 9 or not wz.is_contiguous() or wz.dtype != torch.float32:
+        raise ValueError("canet_zterm: wz must be contiguous fp32 [9,Cout,Cin]")
+    _, cout, cin = wz.shape
+    if z.dim() != 2 or z.shape[1] != cin or not z.is_contiguous() or z.dtype != torch.float32:
+        raise ValueError(f"canet_zterm: z must be contiguous fp32 [B,{cin}]")
+    b = z.shape[0]
+    if taps is None:
+        taps = torch.empty((b, 9, cout), dtype=torch.float32, device=z.device)
+    if tuple(taps.shape) != (b, 9, cout) or not taps.is_contiguous() or taps.dtype != torch.float32:
+        raise ValueError("canet_zterm: taps must be contiguous fp32 [B,9,Cout]")
+    if out is None:
+        out = torch.empty((b, h, w, cout), dtype=torch.float32, device=z.device)
+    if tuple(out.shape) != (b, h, w, cout):
+        raise ValueError(f"canet_zterm: out {tuple(out.shape)} != {(b, h, w, cout)}")
+    if len({t.data_ptr() for t in (wz, z, taps, out)}) != 4:
+        raise ValueError("canet_zterm: wz, z, taps and out must be four different buffers")
+    _lib.check(lib.pemp_canet_zterm_f32(_p(wz), _p(z), _p(taps), _p(out), _nhwc(out, "out"), b, h, w, cin, cout, int(dil), _stream()),
+               "canet_zterm")
+    return out
+
+
+def canet_block_input(x, out, history=None, slot=None, with_history=None):
+    """Input of a CANet residual block (canet.py:103-104,193): out[..., :C] = relu(x); with a history also out[..., C:C+2] =
+    relu(history), from ``history`` [B,2,h,w] (slot None) or from row ``slot[b]`` (device int32 [B]; < 0: zeros) of a table
+    ``history`` [nslots,2,h,w].  ``with_history`` True with ``history`` None writes zeros (the loader's first history)."""
+    lib = _lib.load()
+    _chk_dev(x, out, history, slot)
+    ldx, ldy = _nhwc(x, "x"), _nhwc(out, "out")
+    n, h, w, c = x.shape
+    nhist = 2 if (history is not None or with_history) else 0
+    if tuple(out.shape[:3]) != (n, h, w) or out.shape[3] < c + nhist:
+        raise ValueError(f"canet_block_input: out {tuple(out.shape)} does not take {c} + {nhist} channels of {tuple(x.shape)}")
+    nslots = 0
+    if history is not None:
+        if history.dim() != 4 or tuple(history.shape[1:]) != (2, h, w) or not history.is_contiguous() or history.dtype != torch.float32:
+            raise ValueError(f"canet_block_input: history must be contiguous fp32 [rows,2,{h},{w}], got {tuple(history.shape)}")
+        nslots = history.shape[0]
+        if slot is None and nslots != n:
+            raise ValueError(f"canet_block_input: a history tensor has one row per image ({n}), got {nslots}")
+    if slot is not None and (history is None or slot.dtype != torch.int32 or tuple(slot.shape) != (n,) or not slot.is_contiguous()):
+        raise ValueError("canet_block_input: slot must be a contiguous int32 [B] beside a history table")
+    _lib.check(lib.pemp_canet_block_input_f32(_p(x), ldx, _p(history), _p(slot), nslots, _p(out), ldy, n, h * w, c, nhist, _stream()),
+               "canet_block_input")
+    return out
+
+
+def canet_history_update(logits, table=None, slot=None, out=None):
+    """softmax over the two channels of ``logits`` [B,2,h,w] (entry/canet.py:52) -> row ``slot[b]`` of ``table`` [nslots,2,h,w]
+    for every slot[b] >= 0 (entry/canet.py:77-80) and / or ``out`` [B,2,h,w].  No slot may be named twice in one call."""
+    lib = _lib.load()
+    _chk_dev(logits, table, slot, out)
+    if logits.dim() != 4 or logits.shape[1] != 2 or not logits.is_contiguous() or logits.dtype != torch.float32:
+        raise ValueError("canet_history_update: logits must be contiguous fp32 [B,2,h,w]")
+    b, _, h, w = logits.shape
+    if (table is None) != (slot is None) or (table is None and out is None):
+        raise ValueError("canet_history_update: a table comes with its slots; a table or ``out`` is needed")
+    nslots = 0
+    if table is not None:
+        if table.dim() != 4 or tuple(table.shape[1:]) != (2, h, w) or not table.is_contiguous() or table.dtype != torch.float32:
+            raise ValueError(f"canet_history_update: table must be contiguous fp32 [nslots,2,{h},{w}]")
+        if slot.dtype != torch.int32 or tuple(slot.shape) != (b,) or not slot.is_contiguous():
+            raise ValueError("canet_history_update: slot must be a contiguous int32 [B]")
+        nslots = table.shape[0]
+    if out is not None and (tuple(out.shape) != tuple(logits.shape) or not out.is_contiguous() or out.dtype != torch.float32):
+        raise ValueError("canet_history_update: out must be contiguous fp32 [B,2,h,w]")
+    _lib.check(lib.pemp_canet_history_update_f32(_p(logits), _p(table), _p(slot), nslots, _p(out), b, h * w, _stream()),
+               "canet_history_update")
+    return out if out is not None else table
