@@ -2,7 +2,13 @@
 pieces on v_mfma_f32_32x32x16_bf16.  Held here: the weight pack is exact and laid out as stated; every variant is exact on integer
 probes (zero padding, padding values, whole and split tiles); on random data its error against float64 stays within 1.5 x the
 fp32-chain kernel's; the unsplit variants and the grouped launch are bit-identical among themselves; the stage-1 model on the
-family (the default) moves its logits by no more than the end-to-end tolerance against the fp32 chain."""
+family (the default) moves its logits by no more than the end-to-end tolerance against the fp32 chain.
+
+What the integer probes here do not reach: their weights are 1..3 and their activations integers below 1021, so the weight planes m
+and l and the activation plane l are all zero, and of the six kept products (lh, hl, mm, mh, hm, hh; activation piece first) only
+hh and mh are ever non-zero.  A kernel that read a wrong weight plane or lost one of hl, lh, hm, mm would pass them.  The probes of
+tests/test_conv_split3_fuzz_gpu.py exercise each product on its own, and that file measures the random-data error against float64
+with torch's CPU fp32 conv2d as the yardstick, at strides, kernel sizes and paddings this file does not use."""
 import pytest
 import torch
 import torch.nn.functional as F
@@ -10,6 +16,7 @@ import torch.nn.functional as F
 from tests import util
 from tests.test_conv_probe_gpu import GEOMS, _problem, _reference
 from tests.test_conv_split3_cpu import _cases, split3_reference
+from tests.test_conv_split3_fuzz_cpu import conv_f64, errors, ratio_bound
 
 pytestmark = pytest.mark.gpu
 
@@ -68,6 +75,14 @@ def test_split3_error_is_within_the_fp32_chain_error(hip_lib, dev, N, HW, Cin, C
     assert e3.max().item() <= 1.5 * e_chain.max().item(), (e3.max().item(), e_chain.max().item())
     rms = lambda e: e.pow(2).mean().sqrt().item()
     assert rms(e3) <= 1.5 * rms(e_chain), (rms(e3), rms(e_chain))
+    # and against a yardstick that is no kernel of this library: torch's CPU fp32 conv2d, errors relative to conv(|x|, |w|)
+    mag = conv_f64(x.abs(), w.abs(), 1, pad, dil)
+    y_cpu = F.conv2d(x.permute(0, 3, 1, 2), w, None, 1, pad, dil).permute(0, 2, 3, 1)
+    (m3, r3), (mc, rc) = errors(y3, ref, mag), errors(y_cpu, ref, mag)
+    print(f"split3 id 43 vs CPU fp32 {N}x{HW}x{HW}x{Cin}x{Cout}x{k}x{dil} | K {Cin * k * k} | max {m3:.2e} = x{m3 / mc:.2f} | "
+          f"rms {r3:.2e} = x{r3 / rc:.2f} | yardstick max {mc:.2e} rms {rc:.2e}")
+    bound = ratio_bound(Cin * k * k)
+    assert m3 <= bound * mc and r3 <= bound * rc, (bound, m3, mc, r3, rc)
 
 
 def test_split3_variants_and_the_grouped_launch_are_bit_identical(hip_lib, dev):
