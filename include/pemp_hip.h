@@ -33,6 +33,8 @@ extern "C" {
 #define PEMP_CONV_RELU 1u          /* y = max(y, 0) after affine (+ residual)            */
 #define PEMP_CONV_SHIFT_PER_IMAGE 2u /* shift is [N][Cout] instead of [Cout]              */
 #define PEMP_CONV_STEM4 4u         /* input is NHWC4, K axis = taps x 4 channels (7x7 stem) */
+#define PEMP_CONV_POOL3S2 8u       /* y = max_pool2d(act(...), 3, stride 2, pad 1, ceil_mode) of the 7x7 / 2 / 3 stem, in one
+                                      launch (pemp_conv2d_nhwc_f32 only; see "Fused stem" below)                              */
 
 typedef struct pemp_conv_desc {
     int32_t N, H, W;        /* input images, input spatial size                                  */
@@ -104,7 +106,13 @@ int pemp_conv2d_group_nhwc_f32(int n, const pemp_conv_desc* d, const float* cons
  * bit-identical among 41..44, 46 and their grouped launches (ascending K order, fixed product order).  With these ids `w` is NOT the
  * [Cout][Kpad] fp32 weight but its split form from pemp_pack_split3_bf16.  Entries: pemp_conv2d_nhwc_f32, _padv_, _splitk_,
  * _padv_splitk_, _group_ (41..44, 46).  Plain epilogue only (no stats / bnbwd / dropblock / bf16 forms); buffer-addressed geometries
- * only (no stem, <= 32 taps): an error, never a fall-back, elsewhere.
+ * only (<= 32 taps; no stem except the fused form below): an error, never a fall-back, elsewhere.
+ * Fused stem (flag PEMP_CONV_POOL3S2, pemp_conv2d_nhwc_f32 only): the 7x7 / stride 2 / pad 3 PEMP_CONV_STEM4 conv with split3
+ * arithmetic (`w` = pemp_pack_split3_bf16 of the stem's [Cout][224] pack; any split3 tile id 41..49 names it, the kernel has one
+ * shape) + affine + ReLU + the 3x3 / stride 2 / pad 1 ceil-mode max-pool behind it (networks/backbones.py:89-92).  The descriptor
+ * keeps the CONVOLUTION's Ho, Wo; y is the pooled [N][Hp][Wp][Cout] tensor (Hp = Ho / 2 + 1, per-pixel stride ldy): the conv's
+ * own output is never written.  A block computes the 17 x 17 conv pixels of an 8 x 8 patch of pool outputs; conv pixels outside
+ * Ho x Wo take no part in a maximum.  No residual, padding value or per-image shift; anything else is an error.
  * Ids 47 and 49 (pemp_conv2d_nhwc_f32 / _padv_ / _splitk_ / _padv_splitk_ with no workspace; not _group_): the persistent forms
  * of 43 (64 x 64) and 46 (256 x 128).  The grid is the number of blocks resident at once (at most the tile count) and each block
  * walks a fixed sequence of tiles, issuing the next tile's first operand DMA before the current tile's epilogue; same tiles, same

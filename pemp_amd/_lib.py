@@ -34,6 +34,7 @@ class SampleDesc(C.Structure):
 CONV_RELU = 1
 CONV_SHIFT_PER_IMAGE = 2
 CONV_STEM4 = 4
+CONV_POOL3S2 = 8
 
 #: every symbol include/pemp_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {

@@ -324,5 +324,8 @@ int launch_conv_dma2_group_split3(int tile, ConvGroupArgs& g, hipStream_t st);
 int launch_conv_dma2_split3_persist(int tile, const ConvArgs& a, hipStream_t st);
 int conv_dma2_simds();                                                     // SIMDs of the current device (4 per CU)
 int pack_split3(const float* w, void* out, int cout, int kpad, hipStream_t st);
+// conv_stem_pool.hip: the 7x7 / 2 / 3 NHWC4 stem (split3 weights) + its 3 / 2 / 1 ceil-mode max-pool in one launch (PEMP_CONV_POOL3S2)
+int launch_conv_stem_pool(const ConvArgs& a, hipStream_t st);
+int conv_stem_pool_out(int i);
 
 }  // namespace pemp

@@ -17,7 +17,7 @@
 //    step and the LDS-DMA of the step after that in the shadow of those 4*TM*TN MFMAs, instead of starting every
 //    step with address arithmetic + a dozen LDS reads + a full wait while the matrix pipe drains.
 //
-// Not handled here (conv_dma.hip keeps them): the NHWC4 stem (a K step spans 8 taps, the tap differs per lane), more
+// Not handled here (conv_dma.hip keeps them; conv_stem_pool.hip has the split3 stem fused with its max-pool): the NHWC4 stem (a K step spans 8 taps, the tap differs per lane), more
 // than 32 taps, operands of 2 GiB or more, and a per-channel padding VALUE (padv) that does not lie behind the
 // activations in the same 2 GiB window: the in-image and the out-of-image lanes of a piece must come through ONE
 // descriptor (an exec-masked LDS-DMA does not leave the inactive lanes' 16-byte slots alone -- tried: two masked DMAs per

@@ -285,8 +285,9 @@ extern "C" int pemp_conv2d_padv_splitk_nhwc_f32(const pemp_conv_desc* d, const f
 
 // argument checks of one conv + its ConvArgs (``any_taps``: a padding value may accompany a 1x1 conv -- it is never read)
 static int conv_fill(const pemp_conv_desc* d, const float* x, const float* w, float* y, const float* scale, const float* shift,
-                     const float* residual, const float* pad_value, ConvArgs& a, bool any_taps = false) {
+                     const float* residual, const float* pad_value, ConvArgs& a, bool any_taps = false, bool pooled = false) {
     PEMP_REQUIRE(d && x && w && y, "conv2d: null pointer");
+    PEMP_REQUIRE(pooled || !(d->flags & PEMP_CONV_POOL3S2), "conv2d: PEMP_CONV_POOL3S2 belongs to pemp_conv2d_nhwc_f32 (no grouped / dropblock / statistics / bf16 form)");
     PEMP_REQUIRE(!pad_value || (!(d->flags & PEMP_CONV_STEM4) && (any_taps || d->KH * d->KW > 1) && ((uintptr_t)pad_value & 15) == 0),
                  "conv2d: pad_value needs a multi-tap non-stem conv and a 16-byte aligned [Cin] vector");
     PEMP_REQUIRE(d->N > 0 && d->H > 0 && d->W > 0 && d->Cin > 0 && d->Cout > 0, "conv2d: bad dims");
@@ -333,10 +334,15 @@ static int conv_fill(const pemp_conv_desc* d, const float* x, const float* w, fl
 static int conv2d_impl(const pemp_conv_desc* d, const float* x, const float* w, float* y, const float* scale, const float* shift,
                        const float* residual, const float* pad_value, void* ws, size_t ws_bytes, void* stream) {
     ConvArgs a;
-    const int rc = conv_fill(d, x, w, y, scale, shift, residual, pad_value, a);
+    const int rc = conv_fill(d, x, w, y, scale, shift, residual, pad_value, a, false, true);
     if (rc) return rc;
     const bool stem = d->flags & PEMP_CONV_STEM4;
     int tile = d->tile;
+    if (d->flags & PEMP_CONV_POOL3S2) {     // the fused stem (conv_stem_pool.hip): y is the pooled tensor
+        PEMP_REQUIRE(stem && tile >= 41 && tile <= 49 && !residual && !pad_value,
+                     "conv2d: PEMP_CONV_POOL3S2 needs PEMP_CONV_STEM4 with split3 weights (a tile id 41..49), no residual, no padding value");
+        return launch_conv_stem_pool(a, (hipStream_t)stream);
+    }
     if (tile == 0) {
         // Measured on MI355X (scratch/conv_tune.py): at these problem sizes (M <= ~80k rows) the 64x64
         // tile wins or ties everywhere -- waves per SIMD matter more than operand reuse for the
@@ -485,7 +491,7 @@ extern "C" int pemp_conv2d_dropblock_nhwc_f32(const pemp_conv_desc* d, const flo
 extern "C" int pemp_conv2d_bf16_nhwc(const pemp_conv_desc* d, const void* x, const void* w, void* y, const float* scale,
                                      const float* shift, const void* residual, const void* pad_value, int out_f32, void* stream) {
     PEMP_REQUIRE(d && x && w && y, "conv2d_bf16: null pointer");
-    PEMP_REQUIRE(!(d->flags & (PEMP_CONV_STEM4 | PEMP_CONV_BF16_IO)), "conv2d_bf16: no stem variant; unknown flags");
+    PEMP_REQUIRE(!(d->flags & (PEMP_CONV_STEM4 | PEMP_CONV_BF16_IO | PEMP_CONV_POOL3S2)), "conv2d_bf16: no stem variant; unknown flags");
     PEMP_REQUIRE(d->Cin % 64 == 0 && d->ldx % 8 == 0 && d->ldx >= d->Cin && d->Kpad == d->KH * d->KW * d->Cin,
                  "conv2d_bf16: Cin must be a multiple of 64, ldx of 8 (bf16 elements), Kpad = KH*KW*Cin");
     PEMP_REQUIRE(!residual || !out_f32, "conv2d_bf16: a residual comes with a bf16 output");
@@ -509,7 +515,7 @@ extern "C" int pemp_conv2d_bf16_nhwc(const pemp_conv_desc* d, const void* x, con
 
 
 static int conv_stats_fill(const char* what, const pemp_conv_desc* d, ConvArgs& a) {
-    PEMP_REQUIRE(!(d->flags & (PEMP_CONV_STEM4 | PEMP_CONV_RELU | PEMP_CONV_SHIFT_PER_IMAGE)), "%s: plain conv only (no stem / ReLU / per-image shift)", what);
+    PEMP_REQUIRE(!(d->flags & (PEMP_CONV_STEM4 | PEMP_CONV_RELU | PEMP_CONV_SHIFT_PER_IMAGE | PEMP_CONV_POOL3S2)), "%s: plain conv only (no stem / ReLU / per-image shift)", what);
     PEMP_REQUIRE(d->N > 0 && d->H > 0 && d->W > 0 && d->Cin > 0 && d->Cout > 0 && d->KH > 0 && d->KW > 0 && d->stride > 0 && d->dil > 0 && d->pad >= 0,
                  "%s: bad geometry", what);
     const int ho = (d->H + 2 * d->pad - d->dil * (d->KH - 1) - 1) / d->stride + 1;

@@ -23,10 +23,16 @@ SPLIT3 = os.environ.get("PEMP_SPLIT3", "1") != "0"
 
 
 def with_split3(cp):
-    """Attach the split form of the weights (ConvParams.w3) to an fp32 layer whose geometry the split3 kernels take (no stem,
-    <= 32 taps, Cin % 32, Cout % 64) when SPLIT3 is on; the stem and every other layer stay on the fp32 chain."""
-    if (SPLIT3 and not cp.stem and cp.w.dtype == torch.float32 and cp.kh * cp.kw <= 32 and cp.cin % 32 == 0
-            and cp.cout % 64 == 0 and cp.kpad == cp.kh * cp.kw * cp.cin):
+    """Attach the split form of the weights when SPLIT3 is on: as ConvParams.w3 to an fp32 layer whose geometry the split3 kernels
+    take (<= 32 taps, Cin % 32, Cout % 64), and as ConvParams.w3pool to the 7x7 / stride 2 / pad 3 NHWC4 stem, which then runs
+    fused with its max-pool (ops.stem_pool; a stem launched on its own by ops.conv2d stays on the fp32 chain, its w3 stays None).
+    Every other layer stays on the fp32 chain."""
+    if not SPLIT3 or cp.w.dtype != torch.float32:
+        return cp
+    if cp.stem:
+        if (cp.kh, cp.kw, cp.stride, cp.pad, cp.dil) == (7, 7, 2, 3, 1) and cp.kpad == 224 and cp.cout % 64 == 0:
+            cp.w3pool = ops.pack_split3(cp.w)
+    elif cp.kh * cp.kw <= 32 and cp.cin % 32 == 0 and cp.cout % 64 == 0 and cp.kpad == cp.kh * cp.kw * cp.cin:
         cp.w3 = ops.pack_split3(cp.w)
     return cp
 
@@ -143,6 +149,10 @@ class ResNetEngine:
         a = self.arena
         n, h, w, _ = x4.shape
         ho, wo = ops.conv_out_size(h, 7, 2, 3, 1), ops.conv_out_size(w, 7, 2, 3, 1)
+        if a.dtype == torch.float32 and ops.stem_pool_supported(self.stem):
+            # split3 engines: conv + pool in one launch, only the pooled tensor is written (no "stem" buffer)
+            hp, wp = ops._pool_out(ho, 3, 2, 1, True), ops._pool_out(wo, 3, 2, 1, True)
+            return ops.stem_pool(x4, self.stem, out=a.get("pool", (n, hp, wp, 64), torch.float32))
         y = ops.conv2d(x4, self.stem, out=a.get("stem", (n, ho, wo, 64), torch.float32))
         hp, wp = ops._pool_out(ho, 3, 2, 1, True), ops._pool_out(wo, 3, 2, 1, True)
         x = ops.maxpool2d(y, 3, 2, 1, ceil_mode=True, out=a.get("pool", (n, hp, wp, 64), torch.float32))

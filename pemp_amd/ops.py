@@ -12,7 +12,7 @@ import os
 import torch
 
 from . import _lib
-from ._lib import ConvDesc, CONV_RELU, CONV_SHIFT_PER_IMAGE, CONV_STEM4  # noqa: F401
+from ._lib import ConvDesc, CONV_RELU, CONV_SHIFT_PER_IMAGE, CONV_STEM4, CONV_POOL3S2  # noqa: F401
 
 
 def _stream():
@@ -53,11 +53,13 @@ def conv_out_size(i, k, s, p, d):
 
 class ConvParams:
     """Device-resident, pre-packed parameters of one conv (+ folded per-channel affine)."""
-    __slots__ = ("w", "scale", "shift", "cin", "cout", "kh", "kw", "stride", "pad", "dil", "kpad", "stem", "relu", "w3")
+    __slots__ = ("w", "scale", "shift", "cin", "cout", "kh", "kw", "stride", "pad", "dil", "kpad", "stem", "relu", "w3", "w3pool")
 
-    def __init__(self, w, scale, shift, cin, cout, kh, kw, stride, pad, dil, kpad, stem, relu, w3=None):
+    def __init__(self, w, scale, shift, cin, cout, kh, kw, stride, pad, dil, kpad, stem, relu, w3=None, w3pool=None):
         # w3: the split form of w (pack_split3) -- when present, conv2d / conv2d_group run the split3 family (tile ids 41..56)
-        self.w, self.scale, self.shift, self.w3 = w, scale, shift, w3
+        # w3pool: the split form of a 7x7 / 2 / 3 NHWC4 stem's w, for the fused stem + max-pool launch (stem_pool); conv2d never
+        # reads it: a stem on its own stays on the fp32 chain, w3 stays None
+        self.w, self.scale, self.shift, self.w3, self.w3pool = w, scale, shift, w3, w3pool
         self.cin, self.cout, self.kh, self.kw = cin, cout, kh, kw
         self.stride, self.pad, self.dil, self.kpad, self.stem, self.relu = stride, pad, dil, kpad, stem, relu
 
@@ -357,6 +359,38 @@ def conv2d(x, p, out=None, residual=None, shift_override=None, per_image_shift=F
             else:
                 tile = DEFAULT_TILE + (10 if dropblock is not None else 0)
     launch(tile)
+    return out
+
+
+def stem_pool_supported(p):
+    """Whether ``p`` is a stem the fused launch of ``stem_pool`` takes: 7x7 / stride 2 / pad 3 on NHWC4 with split weights."""
+    return (p.stem and p.w3pool is not None and (p.kh, p.kw, p.stride, p.pad, p.dil) == (7, 7, 2, 3, 1) and p.kpad == 224
+            and p.cout % 64 == 0)
+
+
+def stem_pool(x, p, out=None):
+    """max_pool2d(act(scale * conv(x, w) + shift), 3, stride 2, pad 1, ceil_mode) of the 7x7 / 2 / 3 NHWC4 stem in ONE launch
+    (pemp_conv2d_nhwc_f32 with CONV_POOL3S2; split3 arithmetic on ``p.w3pool``): the conv's own output is never written.  x: NHWC4;
+    returns the pooled NHWC tensor / view ``out`` (a channel window of a wider buffer is fine)."""
+    lib = _lib.load()
+    if not stem_pool_supported(p):
+        raise ValueError("stem_pool: a 7x7 / stride 2 / pad 3 NHWC4 stem with split weights (ConvParams.w3pool)")
+    _chk_dev(x, p.w3pool, out)
+    ldx = _nhwc(x, "x")
+    n, h, w, cin = x.shape
+    if cin != p.cin or x.dtype != torch.float32:
+        raise ValueError(f"stem_pool: fp32 NHWC4 input expected, got {cin} channels of {x.dtype}")
+    ho, wo = conv_out_size(h, 7, 2, 3, 1), conv_out_size(w, 7, 2, 3, 1)
+    hp, wp = _pool_out(ho, 3, 2, 1, True), _pool_out(wo, 3, 2, 1, True)
+    if out is None:
+        out = torch.empty((n, hp, wp, p.cout), dtype=torch.float32, device=x.device)
+    ldy = _nhwc(out, "out")
+    if tuple(out.shape) != (n, hp, wp, p.cout) or out.dtype != torch.float32:
+        raise ValueError(f"stem_pool: out shape {tuple(out.shape)} != {(n, hp, wp, p.cout)} (fp32)")
+    flags = CONV_STEM4 | CONV_POOL3S2 | (CONV_RELU if p.relu else 0)
+    d = ConvDesc(n, h, w, cin, ldx, ho, wo, p.cout, ldy, 7, 7, 2, 3, 1, 0, p.kpad, flags, SPLIT3_DEFAULT_TILE)
+    _lib.check(lib.pemp_conv2d_nhwc_f32(C.byref(d), _p(x), _p(p.w3pool), _p(out), _p(p.scale), _p(p.shift), None, _stream()),
+               "pemp_conv2d_nhwc_f32")
     return out
 
 
