@@ -46,19 +46,33 @@ typedef struct pemp_conv_desc {
     int32_t ldr;            /* residual per-pixel stride (ignored when residual == NULL)         */
     int32_t Kpad;           /* weight row length in floats (>= KH*KW*Cin, multiple of 32)        */
     uint32_t flags;
-    int32_t tile;           /* 0 = auto; 1 = 128x128, 2 = 128x64, 3 = 64x64 block tile (register staging);
-                               11..13 the same with LDS-DMA staging; 14/15 = 128x128 / 128x64, 8 waves;
-                               16/17 = 256x128 / 256x256, 8 waves; 21..27 = the shapes of 11..17 on the
-                               buffer-addressed kernels; 28 = 32x64 blocks of 16-row wave tiles on
-                               v_mfma_f32_16x16x4_f32 (few-row launches: finer granularity); 29 = hybrid of 23
-                               and 28 in one grid for launches of a few rounds (other geometries: 23)
-                               -- all bit-identical results; 31..37: split-K forms of 21..27 (see below);
-                               41..44, 46 / 51, 52, 54, 56: the split3 family (see pemp_pack_split3_bf16);
-                               47, 49: persistent forms of 43, 46 (same family, same results) */
+    int32_t tile;           /* kernel variant: 0 = the entry's own choice, else a tile id (pemp_conv2d_tile_shape)   */
 } pemp_conv_desc;
 
 const char* pemp_last_error(void);
 int pemp_abi_version(void);
+
+/* TILE IDS.  id = 10 x family + shape; every conv entry point decodes pemp_conv_desc.tile through this one scheme.
+ *   shape (last digit)    block BM x BN, waves
+ *     1  128 x 128, 4       2  128 x 64, 4       3  64 x 64, 4
+ *     4  128 x 128, 8       5  128 x 64, 8       6  256 x 128, 8       7  256 x 256, 8
+ *     8  32 x 64, 4: 16-row wave tiles on v_mfma_f32_16x16x4_f32 (finer granularity for launches of a few rounds)
+ *     9  the hybrid launch: shape 3 for the rows that fill whole rounds + 16-row wave tiles for the rest (pemp_conv2d_hybrid_rows)
+ *   family (decade)
+ *     0x  1..3          fp32 chain (v_mfma_f32_32x32x2_f32), operands staged through registers
+ *     1x  11..17        ... staged by LDS-DMA, pointer-addressed: takes every geometry
+ *     2x  21..29        ... buffer-addressed LDS-DMA, barrier inside the MFMA stream: <= 32 taps, operands < 2 GiB, no stem
+ *     3x  31..37, no 33 the 2x kernel with the LAST, partly filled round of tiles split along K (workspace: see
+ *                       pemp_conv2d_stats_nhwc_f32); not bit-identical to 0x..2x
+ *     4x  41..44, 46    split3: fp32 operands as three bf16 pieces on v_mfma_f32_32x32x16_bf16 (pemp_pack_split3_bf16);
+ *         47, 49        persistent forms of 43 and 46: a resident grid walks the tiles
+ *     5x  51, 52, 54, 56  split3 with the last round split along K
+ *   0x, 1x and 2x are bit-identical to each other, and so are 4x among themselves.  Where an id's own kernels do not take a
+ *   geometry, pemp_conv2d_nhwc_f32 and its _padv_ / _splitk_ forms fall back in this order, with the same results: 3x -> 2x,
+ *   29 -> 23 (no hybrid split), 2x -> 1x (28 -> 13); 4x / 5x never fall back (an error instead).  Which ids an entry takes is
+ *   said at the entry.
+ * Returns 1 and the block shape of `id` (bm, bn: optional), 0 for an id that no entry point takes (0 itself included). */
+int pemp_conv2d_tile_shape(int id, int* bm, int* bn);
 
 /* Convolution + per-channel affine (+ residual) (+ ReLU) as one implicit GEMM on
  * v_mfma_f32_32x32x2_f32:   y[n,ho,wo,co] = act( scale[co] * sum_{kh,kw,ci} x[...] * w[co,kh,kw,ci]
@@ -85,7 +99,7 @@ int pemp_conv2d_padv_nhwc_f32(const pemp_conv_desc* d, const float* x, const flo
  * 256-channel convs: 1304 tiles on 1024 SIMDs -- reference networks/backbones.py:42-77 at the reference's own data.test_bs = 1,
  * data_kits/datasets.py:23), the rows that fill WHOLE rounds run on the 64 x 64 tile and the remaining rows on 16-row wave tiles
  * in the same grid; bit-identical to every other exact variant.  Returns how many output rows of `d` go to the 64 x 64 part
- * (0: this geometry has no such split -- pemp_conv2d_nhwc_f32 then runs tile 29 as tile 23).                                */
+ * (0: this geometry has no such split -- pemp_conv2d_nhwc_f32 then runs tile 29 as tile 23).  The tile id of `d` is not read. */
 int pemp_conv2d_hybrid_rows(const pemp_conv_desc* d);
 
 /* Up to 4 INDEPENDENT convolutions in ONE launch (arrays of n descriptors / operand pointers; scale, shift, residual,
@@ -99,8 +113,8 @@ int pemp_conv2d_group_nhwc_f32(int n, const pemp_conv_desc* d, const float* cons
                                float* const* y, const float* const* scale, const float* const* shift,
                                const float* const* residual, const float* const* pad_value, void* stream);
 
-/* Split3 family (tile ids 41..44, 46 = the shapes of 21..24, 26; 51, 52, 54, 56 = their split-K forms, through the split-K entries and
- * workspace like 31..36): the same convolution with fp32 operands on v_mfma_f32_32x32x16_bf16.  Every fp32 value is split exactly
+/* Split3 family (tile ids 4x / 5x; the 5x through the split-K entries and workspace like 3x): the same convolution with fp32
+ * operands on v_mfma_f32_32x32x16_bf16.  Every fp32 value is split exactly
  * into three bf16 pieces h + m + l (round to nearest at each stage); a product is taken as its six pieces' products above one
  * fp32 rounding (hl, lh, mm, mh, hm, hh), accumulated in fp32: fp32-accurate, not bit-identical to the fp32-chain ids 21..37, and
  * bit-identical among 41..44, 46 and their grouped launches (ascending K order, fixed product order).  With these ids `w` is NOT the

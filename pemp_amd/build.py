@@ -33,7 +33,7 @@ def csrc_digest():
     return h.hexdigest()[:12]
 
 
-CONV_ENGINE = ("common.h", "conv_common.h", "conv_igemm.hip", "conv_dma.hip", "conv_dma2.hip", "conv_stem_pool.hip")
+CONV_ENGINE = ("common.h", "conv_common.h", "conv_tiles.h", "conv_igemm.hip", "conv_dma.hip", "conv_dma2.hip", "conv_stem_pool.hip")
 
 
 def conv_digest():

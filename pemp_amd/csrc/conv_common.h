@@ -300,28 +300,27 @@ __device__ __forceinline__ void conv_epilogue_r16(const ConvArgs& a, v4f (&acc)[
     }
 }
 
+// The launch entries below take a SHAPE index 1..9 (conv_tiles.h: the table and decode_tile, which turns a tile id into one).
 // conv_dma.hip
-int launch_conv_dma(int tile, const ConvArgs& a, hipStream_t st);
+int launch_conv_dma(int shape, const ConvArgs& a, hipStream_t st);
 // conv_dma2.hip
 bool conv_dma2_supported(const ConvArgs& a);
-int launch_conv_dma2(int tile, const ConvArgs& a, hipStream_t st);
-int launch_conv_dma2_group(int tile, ConvGroupArgs& g, hipStream_t st);      // fills g.first / g.nblk
-int launch_conv_dma2_hybrid(const ConvArgs& a, hipStream_t st);             // tile id 29; -2: the geometry has no hybrid split
+int launch_conv_dma2(int shape, const ConvArgs& a, hipStream_t st);
+int launch_conv_dma2_group(int shape, ConvGroupArgs& g, hipStream_t st);      // fills g.first / g.nblk
+int launch_conv_dma2_hybrid(const ConvArgs& a, hipStream_t st);             // shape 9; -2: the geometry has no hybrid split
 int conv_dma2_hybrid_rows(int M, int Cout);                               // rows on the 64 x 64 tile in that launch (0: no split)
-int launch_conv_dma2_bf16(int tile, const ConvArgs& a, hipStream_t st);      // bf16 operands (Cin / ldx / Kpad in dwords)
-int launch_conv_dma2_db(int tile, ConvArgs a, void* ws, size_t ws_bytes, bool split, hipStream_t st);   // + DropBlock row scaling
-int conv_dma2_tile_rows(int tile);
-// split-K plan of tile variant `tile` (1..7) for this geometry: number of unsplit tiles, split tiles, pieces per split tile
-// (pieces == 1: the variant runs unsplit) and the workspace the launch needs (counters first, then the partial tiles)
+int launch_conv_dma2_bf16(int shape, const ConvArgs& a, hipStream_t st);     // bf16 operands (Cin / ldx / Kpad in dwords)
+int launch_conv_dma2_db(int shape, ConvArgs a, void* ws, size_t ws_bytes, bool split, hipStream_t st);   // + DropBlock row scaling
+// split-K plan of a shape for this geometry: number of unsplit tiles, split tiles, pieces per split tile (pieces == 1: the
+// variant runs unsplit) and the workspace the launch needs (counters first, then the partial tiles)
 struct SplitKPlan { int full, split, pieces; size_t ws_bytes; };
-SplitKPlan conv_dma2_splitk_plan(int tile, const ConvArgs& a);
-int launch_conv_dma2_splitk(int tile, ConvArgs a, void* ws, size_t ws_bytes, hipStream_t st);
-// split3 family (tile ids 41..46, split-K 51..56; a.w = the weights from pemp_pack_split3_bf16): tile = 1..6, split: the
-// split-K form (ws as for launch_conv_dma2_splitk)
-int launch_conv_dma2_split3(int tile, ConvArgs a, void* ws, size_t ws_bytes, bool split, hipStream_t st);
-int launch_conv_dma2_group_split3(int tile, ConvGroupArgs& g, hipStream_t st);
-// persistent forms (ids 47, 49: tile = 7 -> the 64 x 64 shape of 43, 9 -> 46's 256 x 128): a resident grid walks the tiles
-int launch_conv_dma2_split3_persist(int tile, const ConvArgs& a, hipStream_t st);
+SplitKPlan conv_dma2_splitk_plan(int shape, const ConvArgs& a);
+int launch_conv_dma2_splitk(int shape, ConvArgs a, void* ws, size_t ws_bytes, hipStream_t st);
+// split3 family (a.w = the weights from pemp_pack_split3_bf16); split: the split-K form (ws as for launch_conv_dma2_splitk)
+int launch_conv_dma2_split3(int shape, ConvArgs a, void* ws, size_t ws_bytes, bool split, hipStream_t st);
+int launch_conv_dma2_group_split3(int shape, ConvGroupArgs& g, hipStream_t st);
+// its persistent forms (shapes 3 and 6): a resident grid walks the tiles
+int launch_conv_dma2_split3_persist(int shape, const ConvArgs& a, hipStream_t st);
 int conv_dma2_simds();                                                     // SIMDs of the current device (4 per CU)
 int pack_split3(const float* w, void* out, int cout, int kpad, hipStream_t st);
 // conv_stem_pool.hip: the 7x7 / 2 / 3 NHWC4 stem (split3 weights) + its 3 / 2 / 1 ceil-mode max-pool in one launch (PEMP_CONV_POOL3S2)

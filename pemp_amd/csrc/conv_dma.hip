@@ -12,7 +12,7 @@
 //   is untouched) and the reader looks quad Q up at position Q ^ ((r>>1)&7).
 //
 //   Out-of-image taps (zero padding) are fetched from a 16-byte zero block.
-#include "conv_common.h"
+#include "conv_tiles.h"
 
 namespace pemp {
 
@@ -212,31 +212,12 @@ __global__ __launch_bounds__(NW * 64) void conv_dma_kernel(ConvArgs a) {
     conv_epilogue_lds<TM, TN>(a, acc, (float*)smem + wave * 1024, m0 + wm0, n0 + wn0, lane);
 }
 
-template <int BM, int BN, int WGM, bool STEM, int NW = 4>
-static int launch_dma(const ConvArgs& a, hipStream_t st) {
-    const size_t lds = (size_t)2 * 8 * (BM + BN) * sizeof(v4f);
-    auto kern = conv_dma_kernel<BM, BN, WGM, STEM, NW>;
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) {
-            set_error("hipFuncSetAttribute(lds=%zu): %s", lds, hipGetErrorString(e));
-            return (int)e;
-        }
-    }
-    const int grid = cdiv(a.M, BM) * (a.Cout / BN);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), lds, st, a);
-    return launch_status("conv_dma");
-}
-
-int launch_conv_dma(int tile, const ConvArgs& a, hipStream_t st) {
-    const bool stem = a.flags & PEMP_CONV_STEM4;
-    if (tile == 7) return stem ? launch_dma<256, 256, 4, true, 8>(a, st) : launch_dma<256, 256, 4, false, 8>(a, st);
-    if (tile == 6) return stem ? launch_dma<256, 128, 4, true, 8>(a, st) : launch_dma<256, 128, 4, false, 8>(a, st);
-    if (tile == 4) return stem ? launch_dma<128, 128, 4, true, 8>(a, st) : launch_dma<128, 128, 4, false, 8>(a, st);
-    if (tile == 5) return stem ? launch_dma<128, 64, 4, true, 8>(a, st) : launch_dma<128, 64, 4, false, 8>(a, st);
-    if (tile == 1) return stem ? launch_dma<128, 128, 2, true>(a, st) : launch_dma<128, 128, 2, false>(a, st);
-    if (tile == 2) return stem ? launch_dma<128, 64, 2, true>(a, st) : launch_dma<128, 64, 2, false>(a, st);
-    return stem ? launch_dma<64, 64, 2, true>(a, st) : launch_dma<64, 64, 2, false>(a, st);
+int launch_conv_dma(int shape, const ConvArgs& a, hipStream_t st) {
+    return with_tile<FamFp32>(shape, [&](auto t) {
+        using T = decltype(t);
+        auto kern = (a.flags & PEMP_CONV_STEM4) ? conv_dma_kernel<T::BM, T::BN, T::WGM, true, T::NW> : conv_dma_kernel<T::BM, T::BN, T::WGM, false, T::NW>;
+        return launch_with_lds(kern, tile_grid<T>(a), T::NW * 64, tile_lds<T>(), st, a, "conv_dma");
+    });
 }
 
 }  // namespace pemp

@@ -22,7 +22,7 @@
 // activations in the same 2 GiB window: the in-image and the out-of-image lanes of a piece must come through ONE
 // descriptor (an exec-masked LDS-DMA does not leave the inactive lanes' 16-byte slots alone -- tried: two masked DMAs per
 // piece give wrong data -- so a piece cannot be assembled from two).
-#include "conv_common.h"
+#include "conv_tiles.h"
 
 #ifndef PEMP_SK_ACQUIRE
 #define PEMP_SK_ACQUIRE 1     // 0: round 4's hand-off without the consumer acquire (A/B builds only)
@@ -855,26 +855,32 @@ __global__ __launch_bounds__(NW * 64) void conv_dma2_group_kernel(ConvGroupArgs 
     conv_dma2_body<BM, BN, WGM, NW, PADV, 0, false, false, false, R16, S3>(g.a[which], bid, g.nblk[which]);
 }
 
-template <int BM, int BN, int WGM, int NW, bool R16 = false, bool S3 = false>
-static int launch_dma2_group(ConvGroupArgs& g, bool padv, hipStream_t st) {
-    const size_t lds = (size_t)2 * (8 * BM + (S3 ? 12 : 8) * BN) * sizeof(v4f);
-    auto kern = padv ? conv_dma2_group_kernel<BM, BN, WGM, NW, true, R16, S3> : conv_dma2_group_kernel<BM, BN, WGM, NW, false, R16, S3>;
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) {
-            set_error("hipFuncSetAttribute(lds=%zu): %s", lds, hipGetErrorString(e));
-            return (int)e;
-        }
-    }
+// ---- host side.  Every launch entry takes a SHAPE index (a row of conv_tiles.h's table), picks its kernel through
+// with_tile<family> and launches it through launch_with_lds. ----
+
+// the kernel of shape T with the variant switches of conv_dma2_kernel
+template <class T, bool PADV, int EPI = 0, bool SK = false, bool BF16 = false, bool DB = false, bool R16 = false, bool S3 = false>
+constexpr auto dma2_kernel = conv_dma2_kernel<T::BM, T::BN, T::WGM, T::NW, PADV, EPI, SK, BF16, DB, R16, S3>;
+
+// fp32 chain: statistics / BatchNorm-backward epilogue, padding vector or plain
+template <class T, bool SK>
+static auto dma2_fp32_kernel(const ConvArgs& a) {
+    return a.stats ? (a.bz ? dma2_kernel<T, false, 2, SK> : dma2_kernel<T, false, 1, SK>)
+                   : a.padv ? dma2_kernel<T, true, 0, SK> : dma2_kernel<T, false, 0, SK>;
+}
+
+template <class T, bool R16 = false, bool S3 = false>
+static int launch_dma2_group(ConvGroupArgs& g, hipStream_t st) {
+    auto kern = g.a[0].padv ? conv_dma2_group_kernel<T::BM, T::BN, T::WGM, T::NW, true, R16, S3>
+                            : conv_dma2_group_kernel<T::BM, T::BN, T::WGM, T::NW, false, R16, S3>;
     int grid = 0;
     for (int i = 0; i < g.n; ++i) {
         g.first[i] = grid;
-        g.nblk[i] = cdiv(g.a[i].M, BM) * (g.a[i].Cout / BN);
+        g.nblk[i] = tile_grid<T>(g.a[i]);
         grid += (g.nblk[i] + 7) & ~7;
     }
     g.first[g.n] = grid;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), lds, st, g);
-    return launch_status("conv_dma2/group");
+    return launch_with_lds(kern, grid, T::NW * 64, S3 ? tile_lds_s3<T>() : tile_lds<T>(), st, g, "conv_dma2/group");
 }
 
 // Hybrid launch (tile id 29) for convs of a FEW rounds: 32 x 32 wave tiles are the efficient shape, but T of them on 1024 SIMDs
@@ -936,136 +942,30 @@ int launch_conv_dma2_hybrid(const ConvArgs& a, hipStream_t st) {
     g.first[0] = 0;
     g.first[1] = (g.nblk[0] + 7) & ~7;
     g.first[2] = g.first[1] + g.nblk[1];
-    const size_t lds = (size_t)2 * 8 * (64 + 64) * sizeof(v4f);
     auto kern = a.padv ? conv_dma2_hybrid_kernel<true> : conv_dma2_hybrid_kernel<false>;
-    hipLaunchKernelGGL(kern, dim3(g.first[2]), dim3(256), lds, st, g);
-    return launch_status("conv_dma2/hybrid");
+    return launch_with_lds(kern, g.first[2], 256, tile_lds<Tile<3>>(), st, g, "conv_dma2/hybrid");
 }
 
-int launch_conv_dma2_group(int tile, ConvGroupArgs& g, hipStream_t st) {
-    const bool padv = g.a[0].padv != nullptr;
-    if (tile == 8) return launch_dma2_group<32, 64, 2, 4, true>(g, padv, st);
-    if (tile == 7) return launch_dma2_group<256, 256, 4, 8>(g, padv, st);
-    if (tile == 6) return launch_dma2_group<256, 128, 4, 8>(g, padv, st);
-    if (tile == 4) return launch_dma2_group<128, 128, 4, 8>(g, padv, st);
-    if (tile == 5) return launch_dma2_group<128, 64, 4, 8>(g, padv, st);
-    if (tile == 1) return launch_dma2_group<128, 128, 2, 4>(g, padv, st);
-    if (tile == 2) return launch_dma2_group<128, 64, 2, 4>(g, padv, st);
-    return launch_dma2_group<64, 64, 2, 4>(g, padv, st);
+int launch_conv_dma2_group(int shape, ConvGroupArgs& g, hipStream_t st) {
+    return with_tile<FamGroup>(shape, [&](auto t) { return launch_dma2_group<decltype(t), decltype(t)::BM == 32>(g, st); });
 }
 
-template <int BM, int BN, int WGM, int NW>
-static int launch_dma2(const ConvArgs& a, hipStream_t st) {
-    const size_t lds = (size_t)2 * 8 * (BM + BN) * sizeof(v4f);
-    auto kern = a.stats ? (a.bz ? conv_dma2_kernel<BM, BN, WGM, NW, false, 2> : conv_dma2_kernel<BM, BN, WGM, NW, false, 1>)
-                        : a.padv ? conv_dma2_kernel<BM, BN, WGM, NW, true> : conv_dma2_kernel<BM, BN, WGM, NW, false>;
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) {
-            set_error("hipFuncSetAttribute(lds=%zu): %s", lds, hipGetErrorString(e));
-            return (int)e;
-        }
-    }
-    const int grid = cdiv(a.M, BM) * (a.Cout / BN);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), lds, st, a);
-    return launch_status("conv_dma2");
-}
-
-template <int BM, int BN, int WGM, int NW>
-static int launch_dma2_bf16(const ConvArgs& a, hipStream_t st) {
-    const size_t lds = (size_t)2 * 8 * (BM + BN) * sizeof(v4f);
-    auto kern = a.padv ? conv_dma2_kernel<BM, BN, WGM, NW, true, 0, false, true> : conv_dma2_kernel<BM, BN, WGM, NW, false, 0, false, true>;
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) {
-            set_error("hipFuncSetAttribute(lds=%zu): %s", lds, hipGetErrorString(e));
-            return (int)e;
-        }
-    }
-    const int grid = cdiv(a.M, BM) * (a.Cout / BN);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), lds, st, a);
-    return launch_status("conv_dma2/bf16");
-}
-
-int launch_conv_dma2_bf16(int tile, const ConvArgs& a, hipStream_t st) {
-    if (tile == 7) return launch_dma2_bf16<256, 256, 4, 8>(a, st);
-    if (tile == 6) return launch_dma2_bf16<256, 128, 4, 8>(a, st);
-    if (tile == 4) return launch_dma2_bf16<128, 128, 4, 8>(a, st);
-    if (tile == 5) return launch_dma2_bf16<128, 64, 4, 8>(a, st);
-    if (tile == 1) return launch_dma2_bf16<128, 128, 2, 4>(a, st);
-    if (tile == 2) return launch_dma2_bf16<128, 64, 2, 4>(a, st);
-    return launch_dma2_bf16<64, 64, 2, 4>(a, st);
-}
-
-// conv + DropBlock2D's row scaling in the epilogue (pemp_conv2d_dropblock_nhwc_f32): DB instantiations, unsplit and split-K
-template <int BM, int BN, int WGM, int NW, bool SK>
-static int launch_dma2_db(const ConvArgs& a, int grid, hipStream_t st) {
-    const size_t lds = (size_t)2 * 8 * (BM + BN) * sizeof(v4f);
-    auto kern = conv_dma2_kernel<BM, BN, WGM, NW, false, 0, SK, false, true>;
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) {
-            set_error("hipFuncSetAttribute(lds=%zu): %s", lds, hipGetErrorString(e));
-            return (int)e;
-        }
-    }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), lds, st, a);
-    return launch_status("conv_dma2/dropblock");
-}
-
-template <bool SK>
-static int launch_db_tile(int tile, const ConvArgs& a, int grid, hipStream_t st) {
-    if (tile == 7) return launch_dma2_db<256, 256, 4, 8, SK>(a, grid, st);
-    if (tile == 6) return launch_dma2_db<256, 128, 4, 8, SK>(a, grid, st);
-    if (tile == 4) return launch_dma2_db<128, 128, 4, 8, SK>(a, grid, st);
-    if (tile == 5) return launch_dma2_db<128, 64, 4, 8, SK>(a, grid, st);
-    if (tile == 1) return launch_dma2_db<128, 128, 2, 4, SK>(a, grid, st);
-    if (tile == 2) return launch_dma2_db<128, 64, 2, 4, SK>(a, grid, st);
-    return launch_dma2_db<64, 64, 2, 4, SK>(a, grid, st);
-}
-
-static void tile_shape(int tile, int& bm, int& bn);
-
-int launch_conv_dma2_db(int tile, ConvArgs a, void* ws, size_t ws_bytes, bool split, hipStream_t st) {
-    int bm, bn;
-    tile_shape(tile, bm, bn);
-    if (split) {
-        const SplitKPlan p = conv_dma2_splitk_plan(tile, a);
-        if (p.pieces >= 2) {
-            if (!ws || ws_bytes < p.ws_bytes || ((uintptr_t)ws & 15)) {
-                set_error("conv split-K: workspace of %zu bytes needed (16-byte aligned), got %zu", p.ws_bytes, ws_bytes);
-                return -1;
-            }
-            a.sk_cnt = (int*)ws;
-            a.sk_ws = (float*)((char*)ws + 1024);
-            a.sk_full = p.full;
-            a.sk_S = p.pieces;
-            return launch_db_tile<true>(tile, a, p.full + p.split * p.pieces, st);
-        }
-    }
-    return launch_db_tile<false>(tile, a, cdiv(a.M, bm) * (a.Cout / bn), st);
-}
-
-int conv_dma2_tile_rows(int tile) {        // BM of tile variant 1..8
-    static const int bm[9] = {0, 128, 128, 64, 128, 128, 256, 256, 32};
-    return tile >= 1 && tile <= 8 ? bm[tile] : 0;
-}
-
-static void tile_shape(int tile, int& bm, int& bn) {
-    static const int shapes[9][2] = {{0, 0}, {128, 128}, {128, 64}, {64, 64}, {128, 128}, {128, 64}, {256, 128}, {256, 256}, {32, 64}};
-    bm = shapes[tile][0];
-    bn = shapes[tile][1];
+int launch_conv_dma2_bf16(int shape, const ConvArgs& a, hipStream_t st) {
+    return with_tile<FamFp32>(shape, [&](auto t) {
+        using T = decltype(t);
+        auto kern = a.padv ? dma2_kernel<T, true, 0, false, true> : dma2_kernel<T, false, 0, false, true>;
+        return launch_with_lds(kern, tile_grid<T>(a), T::NW * 64, tile_lds<T>(), st, a, "conv_dma2/bf16");
+    });
 }
 
 // The tiles of a launch are dealt to the 256 CUs in rounds; T mod 256 tiles are left for a last, partly filled round (8 images
 // of 51 x 51 pixels: 326 tiles of 128 x 128 for 256 output channels -- the chip is busy for two rounds and does the work
 // of 1.27).  Those remainder tiles are split along K into as many pieces as keep the piece count <= 256, so that the last
 // round is short instead of partly filled.
-SplitKPlan conv_dma2_splitk_plan(int tile, const ConvArgs& a) {
+SplitKPlan conv_dma2_splitk_plan(int shape, const ConvArgs& a) {
     SplitKPlan p = {0, 0, 1, 0};
-    if (tile < 1 || tile > 7 || tile == 3) return p;
-    int bm, bn;
-    tile_shape(tile, bm, bn);
+    if (!in_family<FamSplitK>(shape)) return p;
+    const int bm = kTileShapes[shape].bm, bn = kTileShapes[shape].bn;
     const int T = cdiv(a.M, bm) * (a.Cout / bn);
     const int rem = T % 256;
     p.full = T;
@@ -1081,149 +981,92 @@ SplitKPlan conv_dma2_splitk_plan(int tile, const ConvArgs& a) {
     return p;
 }
 
-template <int BM, int BN, int WGM, int NW>
-static int launch_dma2_sk(const ConvArgs& a, int grid, hipStream_t st) {
-    const size_t lds = (size_t)2 * 8 * (BM + BN) * sizeof(v4f);
-    auto kern = a.stats ? (a.bz ? conv_dma2_kernel<BM, BN, WGM, NW, false, 2, true> : conv_dma2_kernel<BM, BN, WGM, NW, false, 1, true>)
-                        : a.padv ? conv_dma2_kernel<BM, BN, WGM, NW, true, 0, true> : conv_dma2_kernel<BM, BN, WGM, NW, false, 0, true>;
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) {
-            set_error("hipFuncSetAttribute(lds=%zu): %s", lds, hipGetErrorString(e));
-            return (int)e;
-        }
-    }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), lds, st, a);
-    return launch_status("conv_dma2/splitk");
+// conv + DropBlock2D's row scaling in the epilogue (pemp_conv2d_dropblock_nhwc_f32): DB instantiations, unsplit and split-K
+int launch_conv_dma2_db(int shape, ConvArgs a, void* ws, size_t ws_bytes, bool split, hipStream_t st) {
+    const SplitKPlan p = split ? conv_dma2_splitk_plan(shape, a) : SplitKPlan{0, 0, 1, 0};
+    const int sk_grid = p.pieces >= 2 ? bind_splitk(a, p, ws, ws_bytes) : 0;
+    if (sk_grid < 0) return -1;
+    return with_tile<FamFp32>(shape, [&](auto t) {
+        using T = decltype(t);
+        auto kern = sk_grid ? dma2_kernel<T, false, 0, true, false, true> : dma2_kernel<T, false, 0, false, false, true>;
+        return launch_with_lds(kern, sk_grid ? sk_grid : tile_grid<T>(a), T::NW * 64, tile_lds<T>(), st, a, "conv_dma2/dropblock");
+    });
 }
 
-int launch_conv_dma2_splitk(int tile, ConvArgs a, void* ws, size_t ws_bytes, hipStream_t st) {
-    const SplitKPlan p = conv_dma2_splitk_plan(tile, a);
-    if (p.pieces < 2 || (a.padv && a.stats)) return launch_conv_dma2(tile, a, st);       // nothing to split: the plain variant
-    if (!ws || ws_bytes < p.ws_bytes || ((uintptr_t)ws & 15)) {
-        set_error("conv split-K: workspace of %zu bytes needed (16-byte aligned), got %zu", p.ws_bytes, ws_bytes);
-        return -1;
-    }
-    a.sk_cnt = (int*)ws;
-    a.sk_ws = (float*)((char*)ws + 1024);
-    a.sk_full = p.full;
-    a.sk_S = p.pieces;
-    const int grid = p.full + p.split * p.pieces;
-    if (tile == 7) return launch_dma2_sk<256, 256, 4, 8>(a, grid, st);
-    if (tile == 6) return launch_dma2_sk<256, 128, 4, 8>(a, grid, st);
-    if (tile == 4) return launch_dma2_sk<128, 128, 4, 8>(a, grid, st);
-    if (tile == 5) return launch_dma2_sk<128, 64, 4, 8>(a, grid, st);
-    if (tile == 1) return launch_dma2_sk<128, 128, 2, 4>(a, grid, st);
-    return launch_dma2_sk<128, 64, 2, 4>(a, grid, st);
+int launch_conv_dma2_splitk(int shape, ConvArgs a, void* ws, size_t ws_bytes, hipStream_t st) {
+    const SplitKPlan p = conv_dma2_splitk_plan(shape, a);
+    if (p.pieces < 2 || (a.padv && a.stats)) return launch_conv_dma2(shape, a, st);       // nothing to split: the plain variant
+    const int grid = bind_splitk(a, p, ws, ws_bytes);
+    if (grid < 0) return -1;
+    return with_tile<FamSplitK>(shape, [&](auto t) {
+        using T = decltype(t);
+        return launch_with_lds(dma2_fp32_kernel<T, true>(a), grid, T::NW * 64, tile_lds<T>(), st, a, "conv_dma2/splitk");
+    });
 }
 
-// ---- split3 family: the S3 body on the shapes of tiles 1..4 and 6 (tile 5, 128 x 64 in 8 waves, has no whole B DMA rounds at
-// 192 bytes per row; tile 7, 256 x 256, would need all 160 KiB of LDS).
-// Wave grids: the A fragment is split (split3_bf16, ~9 VALU per element pair) by every wave that reads it, and the pieces feed
-// 6 TN MFMAs.  So ids 41, 42 and 46 give each wave a FULL-WIDTH strip (WGM = NW: 32 rows x BN columns, TN = BN / 32), and every
-// activation row of a block is split once instead of once per wave column: 41 / 46 go from ~4.0 to ~2.2 VALU per MFMA in the K
-// loop (scratch/s3_isa_mix.py).  43 (64 x 64, 4 waves) and 44 (128 x 128, 8 waves) have fewer 32-row strips than waves and keep
+// ---- split3 family: the S3 body on the shapes 1..4 and 6 (shape 5, 128 x 64 in 8 waves, has no whole B DMA rounds at
+// 192 bytes per row; shape 7, 256 x 256, would need all 160 KiB of LDS).
+// Wave grids (the table's wgm3): the A fragment is split (split3_bf16, ~9 VALU per element pair) by every wave that reads it, and
+// the pieces feed 6 TN MFMAs.  So ids 41, 42 and 46 give each wave a FULL-WIDTH strip (WGM = NW: 32 rows x BN columns, TN = BN / 32),
+// and every activation row of a block is split once instead of once per wave column: 41 / 46 go from ~4.0 to ~2.2 VALU per MFMA in
+// the K loop (scratch/s3_isa_mix.py).  43 (64 x 64, 4 waves) and 44 (128 x 128, 8 waves) have fewer 32-row strips than waves and keep
 // two wave columns.  The MFMA sequence each accumulator sees does not depend on the grid: every id stays bit-identical. ----
-template <int BM, int BN, int WGM, int NW, bool SK>
-static int launch_dma2_s3(const ConvArgs& a, int grid, hipStream_t st) {
-    const size_t lds = (size_t)2 * (8 * BM + 12 * BN) * sizeof(v4f);
-    auto kern = a.padv ? conv_dma2_kernel<BM, BN, WGM, NW, true, 0, SK, false, false, false, true>
-                       : conv_dma2_kernel<BM, BN, WGM, NW, false, 0, SK, false, false, false, true>;
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) {
-            set_error("hipFuncSetAttribute(lds=%zu): %s", lds, hipGetErrorString(e));
-            return (int)e;
-        }
-    }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), lds, st, a);
-    return launch_status(SK ? "conv_dma2/split3/splitk" : "conv_dma2/split3");
+static int split3_check(bool shape_ok, int shape, const ConvArgs& a) {       // a shape of the family, the plain epilogue
+    if (shape_ok && !a.stats && !a.rowmask && !(a.flags & PEMP_CONV_BF16_IO)) return 0;
+    set_error("conv split3: tile %d / epilogue outside the family", shape);
+    return -1;
 }
 
-template <bool SK>
-static int launch_s3_tile(int tile, const ConvArgs& a, int grid, hipStream_t st) {
-    if (tile == 6) return launch_dma2_s3<256, 128, 8, 8, SK>(a, grid, st);
-    if (tile == 4) return launch_dma2_s3<128, 128, 4, 8, SK>(a, grid, st);
-    if (tile == 1) return launch_dma2_s3<128, 128, 4, 4, SK>(a, grid, st);
-    if (tile == 2) return launch_dma2_s3<128, 64, 4, 4, SK>(a, grid, st);
-    return launch_dma2_s3<64, 64, 2, 4, SK>(a, grid, st);
-}
-
-int launch_conv_dma2_split3(int tile, ConvArgs a, void* ws, size_t ws_bytes, bool split, hipStream_t st) {
-    if (tile < 1 || tile > 6 || tile == 5 || a.stats || a.rowmask || (a.flags & PEMP_CONV_BF16_IO)) {
-        set_error("conv split3: tile %d / epilogue outside the family", tile);
-        return -1;
-    }
-    int bm, bn;
-    tile_shape(tile, bm, bn);
-    if (split) {
-        const SplitKPlan p = conv_dma2_splitk_plan(tile, a);
-        if (p.pieces >= 2) {
-            if (!ws || ws_bytes < p.ws_bytes || ((uintptr_t)ws & 15)) {
-                set_error("conv split-K: workspace of %zu bytes needed (16-byte aligned), got %zu", p.ws_bytes, ws_bytes);
-                return -1;
-            }
-            a.sk_cnt = (int*)ws;
-            a.sk_ws = (float*)((char*)ws + 1024);
-            a.sk_full = p.full;
-            a.sk_S = p.pieces;
-            return launch_s3_tile<true>(tile, a, p.full + p.split * p.pieces, st);
-        }
-    }
-    return launch_s3_tile<false>(tile, a, cdiv(a.M, bm) * (a.Cout / bn), st);
+int launch_conv_dma2_split3(int shape, ConvArgs a, void* ws, size_t ws_bytes, bool split, hipStream_t st) {
+    if (split3_check(in_family<FamSplit3>(shape), shape, a)) return -1;
+    const SplitKPlan p = split ? conv_dma2_splitk_plan(shape, a) : SplitKPlan{0, 0, 1, 0};
+    const int sk_grid = p.pieces >= 2 ? bind_splitk(a, p, ws, ws_bytes) : 0;
+    if (sk_grid < 0) return -1;
+    return with_tile<FamSplit3>(shape, [&](auto t) {
+        using T = decltype(t);
+        auto kern = sk_grid ? (a.padv ? dma2_kernel<T, true, 0, true, false, false, false, true> : dma2_kernel<T, false, 0, true, false, false, false, true>)
+                            : (a.padv ? dma2_kernel<T, true, 0, false, false, false, false, true> : dma2_kernel<T, false, 0, false, false, false, false, true>);
+        return launch_with_lds(kern, sk_grid ? sk_grid : tile_grid<T>(a), T::NW * 64, tile_lds_s3<T>(), st, a,
+                               sk_grid ? "conv_dma2/split3/splitk" : "conv_dma2/split3");
+    });
 }
 
 // persistent forms (ids 47, 49): grid = resident blocks (occupancy of the instantiation x CUs, taken once), at most the tile count
-template <int BM, int BN, int WGM, int NW>
+template <class T>
 static int launch_dma2_s3p(const ConvArgs& a, hipStream_t st) {
-    const size_t lds = (size_t)2 * (8 * BM + 12 * BN) * sizeof(v4f);
-    auto kern = a.padv ? conv_dma2_s3p_kernel<BM, BN, WGM, NW, true> : conv_dma2_s3p_kernel<BM, BN, WGM, NW, false>;
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) {
-            set_error("hipFuncSetAttribute(lds=%zu): %s", lds, hipGetErrorString(e));
-            return (int)e;
-        }
-    }
+    constexpr size_t lds = tile_lds_s3<T>();
+    auto kern = a.padv ? conv_dma2_s3p_kernel<T::BM, T::BN, T::WGM, T::NW, true> : conv_dma2_s3p_kernel<T::BM, T::BN, T::WGM, T::NW, false>;
     static int occ[2] = {0, 0};          // blocks per CU of the two instantiations (racing fills write the same value)
     int& o = occ[a.padv ? 1 : 0];
     if (!o) {
+        const int rc = allow_lds(kern, lds);       // the occupancy query wants what the launch will have
+        if (rc) return rc;
         int v = 0;
-        hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, (const void*)kern, NW * 64, lds);
+        hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, (const void*)kern, T::NW * 64, lds);
         if (e != hipSuccess || v <= 0) {
             set_error("conv split3 persistent: occupancy query failed (%s, %d blocks)", hipGetErrorString(e), v);
             return -1;
         }
         o = v;
     }
-    const long long tiles = (long long)cdiv(a.M, BM) * (a.Cout / BN);
+    const long long tiles = tile_grid<T>(a);
     long long grid = (long long)o * (conv_dma2_simds() / 4);
     if (grid < 8) grid = 8;              // every XCD's range needs a block
     if (grid > tiles) grid = tiles;
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(NW * 64), lds, st, a);
-    return launch_status("conv_dma2/split3/persistent");
+    return launch_with_lds(kern, (int)grid, T::NW * 64, lds, st, a, "conv_dma2/split3/persistent");
 }
 
-int launch_conv_dma2_split3_persist(int tile, const ConvArgs& a, hipStream_t st) {
-    if (a.stats || a.rowmask || (a.flags & PEMP_CONV_BF16_IO)) {
-        set_error("conv split3: tile %d / epilogue outside the family", tile);
-        return -1;
-    }
-    if (tile == 9) return launch_dma2_s3p<256, 128, 8, 8>(a, st);
-    return launch_dma2_s3p<64, 64, 2, 4>(a, st);
+int launch_conv_dma2_split3_persist(int shape, const ConvArgs& a, hipStream_t st) {
+    if (split3_check(true, shape, a)) return -1;
+    return with_tile<FamPersist>(shape, [&](auto t) { return launch_dma2_s3p<decltype(t)>(a, st); });
 }
 
-int launch_conv_dma2_group_split3(int tile, ConvGroupArgs& g, hipStream_t st) {
-    if (tile == 5) {
+int launch_conv_dma2_group_split3(int shape, ConvGroupArgs& g, hipStream_t st) {
+    if (shape == 5) {
         set_error("conv split3: no 128 x 64 8-wave form");
         return -1;
     }
-    const bool padv = g.a[0].padv != nullptr;
-    if (tile == 6) return launch_dma2_group<256, 128, 8, 8, false, true>(g, padv, st);
-    if (tile == 4) return launch_dma2_group<128, 128, 4, 8, false, true>(g, padv, st);
-    if (tile == 1) return launch_dma2_group<128, 128, 4, 4, false, true>(g, padv, st);
-    if (tile == 2) return launch_dma2_group<128, 64, 4, 4, false, true>(g, padv, st);
-    return launch_dma2_group<64, 64, 2, 4, false, true>(g, padv, st);
+    return with_tile<FamSplit3>(shape, [&](auto t) { return launch_dma2_group<decltype(t), false, true>(g, st); });
 }
 
 // [Cout][Kpad] fp32 -> [Cout][Kpad / 32][3][32] bf16: per row and 32-channel K step the h, m and l planes of split3_bf16
@@ -1262,29 +1105,23 @@ bool conv_dma2_supported(const ConvArgs& a) {
     return xbytes < (1ll << 31) && wbytes < (1ll << 31);
 }
 
-// tile 8: the 16-row variant (32 x 64 block, 16 x 32 wave tiles on v_mfma_f32_16x16x4_f32); plain epilogue only
+// shape 8: the 16-row variant (32 x 64 block, 16 x 32 wave tiles on v_mfma_f32_16x16x4_f32); plain epilogue only
 static int launch_dma2_r16(const ConvArgs& a, hipStream_t st) {
     if (a.stats) {
         set_error("conv_dma2: the 16-row tile has no statistics epilogue");
         return -1;
     }
-    auto kern = a.padv ? conv_dma2_kernel<32, 64, 2, 4, true, 0, false, false, false, true>
-                       : conv_dma2_kernel<32, 64, 2, 4, false, 0, false, false, false, true>;
-    const size_t lds = (size_t)2 * 8 * (32 + 64) * sizeof(v4f);
-    const int grid = cdiv(a.M, 32) * (a.Cout / 64);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, a);
-    return launch_status("conv_dma2/r16");
+    using T = Tile<8>;
+    auto kern = a.padv ? dma2_kernel<T, true, 0, false, false, false, true> : dma2_kernel<T, false, 0, false, false, false, true>;
+    return launch_with_lds(kern, tile_grid<T>(a), T::NW * 64, tile_lds<T>(), st, a, "conv_dma2/r16");
 }
 
-int launch_conv_dma2(int tile, const ConvArgs& a, hipStream_t st) {
-    if (tile == 8) return launch_dma2_r16(a, st);
-    if (tile == 7) return launch_dma2<256, 256, 4, 8>(a, st);
-    if (tile == 6) return launch_dma2<256, 128, 4, 8>(a, st);
-    if (tile == 4) return launch_dma2<128, 128, 4, 8>(a, st);
-    if (tile == 5) return launch_dma2<128, 64, 4, 8>(a, st);
-    if (tile == 1) return launch_dma2<128, 128, 2, 4>(a, st);
-    if (tile == 2) return launch_dma2<128, 64, 2, 4>(a, st);
-    return launch_dma2<64, 64, 2, 4>(a, st);
+int launch_conv_dma2(int shape, const ConvArgs& a, hipStream_t st) {
+    if (shape == 8) return launch_dma2_r16(a, st);
+    return with_tile<FamFp32>(shape, [&](auto t) {
+        using T = decltype(t);
+        return launch_with_lds(dma2_fp32_kernel<T, false>(a), tile_grid<T>(a), T::NW * 64, tile_lds<T>(), st, a, "conv_dma2");
+    });
 }
 
 }  // namespace pemp

@@ -23,7 +23,7 @@
 //
 //   Staging: global -> registers (issued before the MFMAs of the current step) -> LDS buffer
 //   b^1 after them; one __syncthreads per K step.
-#include "conv_common.h"
+#include "conv_tiles.h"
 
 namespace pemp {
 
@@ -233,20 +233,13 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(ConvArgs a) {
     conv_epilogue_lds<TM, TN>(a, acc, (float*)smem + wave * 1024, m0 + wm0, n0 + wn0, lane);
 }
 
-template <int BM, int BN, int WGM, bool STEM>
-static int launch_conv(const ConvArgs& a, hipStream_t st) {
-    const size_t lds = (size_t)2 * 8 * (BM + BN) * sizeof(v4f);
-    auto kern = conv_igemm_kernel<BM, BN, WGM, STEM>;
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) {
-            set_error("hipFuncSetAttribute(lds=%zu): %s", lds, hipGetErrorString(e));
-            return (int)e;
-        }
-    }
-    const int grid = cdiv(a.M, BM) * (a.Cout / BN);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, a);
-    return launch_status("conv_igemm");
+// the register-staged kernels (ids 1..3: the 4-wave shapes of the table)
+static int launch_conv(int shape, const ConvArgs& a, hipStream_t st) {
+    return with_tile<FamIgemm>(shape, [&](auto t) {
+        using T = decltype(t);
+        auto kern = (a.flags & PEMP_CONV_STEM4) ? conv_igemm_kernel<T::BM, T::BN, T::WGM, true> : conv_igemm_kernel<T::BM, T::BN, T::WGM, false>;
+        return launch_with_lds(kern, tile_grid<T>(a), 256, tile_lds<T>(), st, a, "conv_igemm");
+    });
 }
 
 }  // namespace pemp
@@ -265,7 +258,7 @@ static int conv2d_impl(const pemp_conv_desc* d, const float* x, const float* w, 
 extern "C" int pemp_conv2d_padv_nhwc_f32(const pemp_conv_desc* d, const float* x, const float* w, float* y,
                                          const float* scale, const float* shift, const float* residual,
                                          const float* pad_value, void* stream) {
-    PEMP_REQUIRE(!d || ((d->tile < 31 || d->tile > 37) && (d->tile < 51 || d->tile > 56)),
+    PEMP_REQUIRE(!d || !decode_tile(d->tile).splitk,
                  "conv2d: the split-K tile ids 31..37 / 51..56 need pemp_conv2d_splitk_nhwc_f32 (workspace)");
     return conv2d_impl(d, x, w, y, scale, shift, residual, pad_value, nullptr, 0, stream);
 }
@@ -338,72 +331,59 @@ static int conv2d_impl(const pemp_conv_desc* d, const float* x, const float* w, 
     if (rc) return rc;
     const bool stem = d->flags & PEMP_CONV_STEM4;
     int tile = d->tile;
-    if (d->flags & PEMP_CONV_POOL3S2) {     // the fused stem (conv_stem_pool.hip): y is the pooled tensor
-        PEMP_REQUIRE(stem && tile >= 41 && tile <= 49 && !residual && !pad_value,
-                     "conv2d: PEMP_CONV_POOL3S2 needs PEMP_CONV_STEM4 with split3 weights (a tile id 41..49), no residual, no padding value");
-        return launch_conv_stem_pool(a, (hipStream_t)stream);
-    }
     if (tile == 0) {
         // Measured on MI355X (scratch/conv_tune.py): at these problem sizes (M <= ~80k rows) the 64x64
         // tile wins or ties everywhere -- waves per SIMD matter more than operand reuse for the
         // 64-cycle fp32 MFMA.  Callers that know better (engine autotune) pass an explicit tile.
         tile = 3;
     }
+    TileId t = decode_tile(tile);
+    if (d->flags & PEMP_CONV_POOL3S2) {     // the fused stem (conv_stem_pool.hip): y is the pooled tensor
+        PEMP_REQUIRE(stem && t.family == TILE_SPLIT3 && !t.splitk && !residual && !pad_value,
+                     "conv2d: PEMP_CONV_POOL3S2 needs PEMP_CONV_STEM4 with split3 weights (a tile id 41..49), no residual, no padding value");
+        return launch_conv_stem_pool(a, (hipStream_t)stream);
+    }
+    PEMP_REQUIRE(tile != 33 && tile != 53, "conv2d: no split-K variant of the 64 x 64 tile");
+    PEMP_REQUIRE(tile != 45 && tile != 55, "conv2d: no split3 form of the 128 x 64 8-wave tile");
+    PEMP_REQUIRE(tile != 48, "conv2d: no persistent split3 form of the 128 x 128 4-wave tile");
+    PEMP_REQUIRE(t.exists, "conv2d: unknown tile id %d", tile);
     hipStream_t st = (hipStream_t)stream;
-    if ((tile >= 41 && tile <= 49) || (tile >= 51 && tile <= 56)) {     // split3 family (conv_dma2.hip, S3): w from pemp_pack_split3_bf16
-        PEMP_REQUIRE(tile != 53, "conv2d: no split-K variant of the 64 x 64 tile");
-        PEMP_REQUIRE(tile != 45 && tile != 55, "conv2d: no split3 form of the 128 x 64 8-wave tile");
-        PEMP_REQUIRE(tile != 48, "conv2d: no persistent split3 form of the 128 x 128 4-wave tile");
+    if (t.family == TILE_SPLIT3) {       // conv_dma2.hip, S3: w from pemp_pack_split3_bf16
         PEMP_REQUIRE(!stem && conv_dma2_supported(a) && (long long)a.Cout * a.Kpad * 6 < (1ll << 31),
                      "conv2d: split3 tile %d needs a geometry of the buffer-addressed kernels (no stem, <= 32 taps, operands < 2 GiB)", tile);
-        if (tile == 47 || tile == 49) {    // persistent forms of 43 and 46 (same results)
-            PEMP_REQUIRE(tile == 47 || a.Cout % 128 == 0, "conv2d: tile N=128 needs Cout %% 128 == 0");
-            return launch_conv_dma2_split3_persist(tile - 40, a, st);
-        }
-        const int t = tile > 50 ? tile - 50 : tile - 40;
-        PEMP_REQUIRE((t != 1 && t != 4 && t != 6) || a.Cout % 128 == 0, "conv2d: tile N=128 needs Cout %% 128 == 0");
-        return launch_conv_dma2_split3(t, a, ws, ws_bytes, tile > 50, st);
+        PEMP_REQUIRE_COUT("conv2d", t.shape, a.Cout);
+        if (t.persistent) return launch_conv_dma2_split3_persist(t.shape, a, st);      // same results as the id it walks
+        return launch_conv_dma2_split3(t.shape, a, ws, ws_bytes, t.splitk, st);
     }
-    if (tile >= 31 && tile <= 37) {      // conv_dma2.hip with the last round of tiles split along K (pemp_hip.h)
-        PEMP_REQUIRE(tile != 33, "conv2d: no split-K variant of the 64 x 64 tile");
+    // the fp32 chain: every id falls back towards the pointer-addressed kernels where its own do not apply (same results)
+    if (t.family == TILE_DMA2 && t.splitk) {      // the last round of tiles split along K
         if (conv_dma2_supported(a)) {
-            const int t = tile - 30;
-            PEMP_REQUIRE((t != 1 && t != 4 && t != 6) || a.Cout % 128 == 0, "conv2d: tile N=128 needs Cout %% 128 == 0");
-            PEMP_REQUIRE(t != 7 || a.Cout % 256 == 0, "conv2d: tile 256x256 needs Cout %% 256 == 0");
-            return launch_conv_dma2_splitk(t, a, ws, ws_bytes, st);
+            PEMP_REQUIRE_COUT("conv2d", t.shape, a.Cout);
+            return launch_conv_dma2_splitk(t.shape, a, ws, ws_bytes, st);
         }
-        tile -= 20;
+        t.splitk = false;                // 3x -> 2x
     }
-    if (tile == 29) {                    // hybrid (conv_dma2.hip): whole rounds of 32 x 32 wave tiles + the remaining rows on 16-row tiles, one grid
+    if (t.family == TILE_DMA2 && t.shape == 9) {  // hybrid: whole rounds of 32 x 32 wave tiles + the remaining rows on 16-row tiles, one grid
         if (conv_dma2_supported(a)) {
             const int rc2 = launch_conv_dma2_hybrid(a, st);
             if (rc2 != -2) return rc2;
         }
-        tile = 23;                       // no hybrid split for this geometry: the 64 x 64 tile (same results)
+        t.shape = 3;                     // no hybrid split for this geometry: 29 -> 23
     }
-    if (tile >= 21 && tile <= 28) {      // conv_dma2.hip: buffer-addressed LDS-DMA + barrier inside the MFMA stream (same tile shapes as 11..17;
-                                         // 28: the 16-row variant, 32 x 64 blocks on v_mfma_f32_16x16x4_f32)
+    if (t.family == TILE_DMA2) {         // buffer-addressed LDS-DMA + barrier inside the MFMA stream
         if (conv_dma2_supported(a)) {
-            const int t = tile - 20;
-            PEMP_REQUIRE((t != 1 && t != 4 && t != 6) || a.Cout % 128 == 0, "conv2d: tile N=128 needs Cout %% 128 == 0");
-            PEMP_REQUIRE(t != 7 || a.Cout % 256 == 0, "conv2d: tile 256x256 needs Cout %% 256 == 0");
-            return launch_conv_dma2(t, a, st);
+            PEMP_REQUIRE_COUT("conv2d", t.shape, a.Cout);
+            return launch_conv_dma2(t.shape, a, st);
         }
-        tile = tile == 28 ? 13 : tile - 10;      // stem / padding value / > 32 taps / >= 2 GiB operands: the pointer-addressed variant
+        t.family = TILE_DMA;             // stem / padding value / > 32 taps / >= 2 GiB operands: 2x -> 1x, and 28 -> 13
+        if (t.shape == 8) t.shape = 3;
     }
-    if (tile >= 11 && tile <= 17) {      // LDS-DMA staging variants (conv_dma.hip); 14..17: 8-wave blocks, 16: 256x128, 17: 256x256
-        PEMP_REQUIRE((tile != 11 && tile != 14 && tile != 16) || a.Cout % 128 == 0, "conv2d: tile N=128 needs Cout %% 128 == 0");
-        PEMP_REQUIRE(tile != 17 || a.Cout % 256 == 0, "conv2d: tile 256x256 needs Cout %% 256 == 0");
-        return launch_conv_dma(tile - 10, a, st);
+    if (t.family == TILE_DMA) {          // LDS-DMA staging, pointer-addressed (conv_dma.hip)
+        PEMP_REQUIRE_COUT("conv2d", t.shape, a.Cout);
+        return launch_conv_dma(t.shape, a, st);
     }
-    if (tile == 1) {
-        PEMP_REQUIRE(a.Cout % 128 == 0, "conv2d: tile 128x128 needs Cout %% 128 == 0");
-        return stem ? launch_conv<128, 128, 2, true>(a, st) : launch_conv<128, 128, 2, false>(a, st);
-    }
-    if (tile == 2) return stem ? launch_conv<128, 64, 2, true>(a, st) : launch_conv<128, 64, 2, false>(a, st);
-    if (tile == 3) return stem ? launch_conv<64, 64, 2, true>(a, st) : launch_conv<64, 64, 2, false>(a, st);
-    set_error("conv2d: unknown tile id %d", tile);
-    return -1;
+    PEMP_REQUIRE(t.shape != 1 || a.Cout % 128 == 0, "conv2d: tile 128x128 needs Cout %% 128 == 0");
+    return launch_conv(t.shape, a, st);      // register staging (this file)
 }
 
 
@@ -414,9 +394,9 @@ extern "C" int pemp_conv2d_group_nhwc_f32(int n, const pemp_conv_desc* d, const 
     ConvGroupArgs g;
     g.n = n;
     const int tile = d[0].tile;
-    const bool s3 = tile >= 41 && tile <= 46 && tile != 45;
-    PEMP_REQUIRE((tile >= 21 && tile <= 28) || s3, "conv2d_group: tile must be one of the buffer-addressed variants 21..28 or 41..44, 46, got %d", tile);
-    const int t = s3 ? tile - 40 : tile - 20;
+    const TileId t = decode_tile(tile);
+    const bool s3 = t.family == TILE_SPLIT3 && t.exists && !t.splitk && !t.persistent;
+    PEMP_REQUIRE((t.family == TILE_DMA2 && !t.splitk && t.shape <= 8) || s3, "conv2d_group: tile must be one of the buffer-addressed variants 21..28 or 41..44, 46, got %d", tile);
     for (int i = 0; i < n; ++i) {
         PEMP_REQUIRE(d[i].tile == tile, "conv2d_group: every member must name the same tile variant");
         PEMP_REQUIRE(!pad_value || (pad_value[i] != nullptr) == (pad_value[0] != nullptr), "conv2d_group: pad_value for every member or for none");
@@ -424,8 +404,7 @@ extern "C" int pemp_conv2d_group_nhwc_f32(int n, const pemp_conv_desc* d, const 
                                  residual ? residual[i] : nullptr, pad_value ? pad_value[i] : nullptr, g.a[i], true);
         if (rc) return rc;
         PEMP_REQUIRE(conv_dma2_supported(g.a[i]), "conv2d_group: member %d lies outside the buffer-addressed kernels (stem / > 32 taps / 2 GiB operands / padding vector not behind the activations)", i);
-        PEMP_REQUIRE((t != 1 && t != 4 && t != 6) || g.a[i].Cout % 128 == 0, "conv2d_group: tile N=128 needs Cout %% 128 == 0");
-        PEMP_REQUIRE(t != 7 || g.a[i].Cout % 256 == 0, "conv2d_group: tile 256x256 needs Cout %% 256 == 0");
+        PEMP_REQUIRE_COUT("conv2d_group", t.shape, g.a[i].Cout);
         PEMP_REQUIRE(!s3 || (long long)g.a[i].Cout * g.a[i].Kpad * 6 < (1ll << 31), "conv2d_group: split3 weights of 2 GiB or more");
     }
     // members run beside each other in one grid: no member may write what another one writes or reads.  Two tensors that interleave
@@ -454,7 +433,7 @@ extern "C" int pemp_conv2d_group_nhwc_f32(int n, const pemp_conv_desc* d, const 
         }
     }
     for (int i = n; i < CONV_GROUP_MAX; ++i) g.a[i] = g.a[0];
-    return s3 ? launch_conv_dma2_group_split3(t, g, (hipStream_t)stream) : launch_conv_dma2_group(t, g, (hipStream_t)stream);
+    return s3 ? launch_conv_dma2_group_split3(t.shape, g, (hipStream_t)stream) : launch_conv_dma2_group(t.shape, g, (hipStream_t)stream);
 }
 
 extern "C" int pemp_pack_split3_bf16(const float* w, void* out, int cout, int kpad, void* stream) {
@@ -473,16 +452,14 @@ extern "C" int pemp_conv2d_dropblock_nhwc_f32(const pemp_conv_desc* d, const flo
     ConvArgs a;
     const int rc = conv_fill(d, x, w, y, scale, shift, residual, nullptr, a);
     if (rc) return rc;
-    PEMP_REQUIRE(d->tile >= 21 && d->tile <= 37 && d->tile != 33 && !(d->tile >= 28 && d->tile <= 30),
+    const TileId t = decode_tile(d->tile);
+    PEMP_REQUIRE(t.family == TILE_DMA2 && t.exists && t.shape <= 7,
                  "conv2d_dropblock: tile must be 21..27 or 31..37 (no 33), got %d", d->tile);
     PEMP_REQUIRE(conv_dma2_supported(a), "conv2d_dropblock: geometry / operand size outside the buffer-addressed kernels");
     a.rowmask = rowmask;
     a.rowcnt = kept_count;
-    const int t = d->tile > 30 ? d->tile - 30 : d->tile - 20;
-    PEMP_REQUIRE((t != 1 && t != 4 && t != 6) || a.Cout % 128 == 0, "conv2d_dropblock: tile N=128 needs Cout %% 128 == 0");
-    PEMP_REQUIRE(t != 7 || a.Cout % 256 == 0, "conv2d_dropblock: tile 256x256 needs Cout %% 256 == 0");
-    PEMP_REQUIRE(d->tile != 33, "conv2d_dropblock: no split-K variant of the 64 x 64 tile");
-    return launch_conv_dma2_db(t, a, ws, ws_bytes, d->tile > 30, (hipStream_t)stream);
+    PEMP_REQUIRE_COUT("conv2d_dropblock", t.shape, a.Cout);
+    return launch_conv_dma2_db(t.shape, a, ws, ws_bytes, t.splitk, (hipStream_t)stream);
 }
 
 
@@ -495,7 +472,8 @@ extern "C" int pemp_conv2d_bf16_nhwc(const pemp_conv_desc* d, const void* x, con
     PEMP_REQUIRE(d->Cin % 64 == 0 && d->ldx % 8 == 0 && d->ldx >= d->Cin && d->Kpad == d->KH * d->KW * d->Cin,
                  "conv2d_bf16: Cin must be a multiple of 64, ldx of 8 (bf16 elements), Kpad = KH*KW*Cin");
     PEMP_REQUIRE(!residual || !out_f32, "conv2d_bf16: a residual comes with a bf16 output");
-    PEMP_REQUIRE(d->tile == 0 || (d->tile >= 21 && d->tile <= 27), "conv2d_bf16: tile must be 0 or 21..27");
+    const TileId t = decode_tile(d->tile == 0 ? 24 : d->tile);
+    PEMP_REQUIRE(t.family == TILE_DMA2 && !t.splitk && t.shape <= 7, "conv2d_bf16: tile must be 0 or 21..27");
     pemp_conv_desc h = *d;
     h.Cin = d->Cin / 2;
     h.ldx = d->ldx / 2;
@@ -507,12 +485,13 @@ extern "C" int pemp_conv2d_bf16_nhwc(const pemp_conv_desc* d, const void* x, con
     if (rc) return rc;
     if (!out_f32) a.flags |= PEMP_CONV_BF16_IO;
     PEMP_REQUIRE(conv_dma2_supported(a), "conv2d_bf16: geometry / operand size outside the buffer-addressed kernels");
-    const int t = d->tile == 0 ? 4 : d->tile - 20;
-    PEMP_REQUIRE((t != 1 && t != 4 && t != 6) || a.Cout % 128 == 0, "conv2d_bf16: tile N=128 needs Cout %% 128 == 0");
-    PEMP_REQUIRE(t != 7 || a.Cout % 256 == 0, "conv2d_bf16: tile 256x256 needs Cout %% 256 == 0");
-    return launch_conv_dma2_bf16(t, a, (hipStream_t)stream);
+    PEMP_REQUIRE_COUT("conv2d_bf16", t.shape, a.Cout);
+    return launch_conv_dma2_bf16(t.shape, a, (hipStream_t)stream);
 }
 
+
+// the id of a statistics / BatchNorm-backward launch: 0 runs as 23
+static TileId stats_tile(const pemp_conv_desc* d) { return decode_tile(d->tile == 0 ? 23 : d->tile); }
 
 static int conv_stats_fill(const char* what, const pemp_conv_desc* d, ConvArgs& a) {
     PEMP_REQUIRE(!(d->flags & (PEMP_CONV_STEM4 | PEMP_CONV_RELU | PEMP_CONV_SHIFT_PER_IMAGE | PEMP_CONV_POOL3S2)), "%s: plain conv only (no stem / ReLU / per-image shift)", what);
@@ -539,18 +518,17 @@ static int conv_stats_fill(const char* what, const pemp_conv_desc* d, ConvArgs& 
         set_error("%s: geometry / operand size outside the buffer-addressed kernels", what);
         return -2;
     }
-    const int t = d->tile == 0 ? 3 : (d->tile > 30 ? d->tile - 30 : d->tile - 20);
-    PEMP_REQUIRE(t >= 1 && t <= 7 && d->tile != 33, "%s: tile must be 0, 21..27 or 31..37 (no 33)", what);
-    PEMP_REQUIRE((t != 1 && t != 4 && t != 6) || a.Cout % 128 == 0, "%s: tile N=128 needs Cout %% 128 == 0", what);
-    PEMP_REQUIRE(t != 7 || a.Cout % 256 == 0, "%s: tile 256x256 needs Cout %% 256 == 0", what);
+    const TileId t = stats_tile(d);
+    PEMP_REQUIRE(t.family == TILE_DMA2 && t.exists && t.shape <= 7, "%s: tile must be 0, 21..27 or 31..37 (no 33)", what);
+    PEMP_REQUIRE_COUT(what, t.shape, a.Cout);
     return 0;
 }
 
 static int conv_stats_common(const char* what, const pemp_conv_desc* d, ConvArgs& a, void* ws, size_t ws_bytes, hipStream_t st) {
     const int rc = conv_stats_fill(what, d, a);
     if (rc) return rc;
-    if (d->tile > 30) return launch_conv_dma2_splitk(d->tile - 30, a, ws, ws_bytes, st);
-    return launch_conv_dma2(d->tile == 0 ? 3 : d->tile - 20, a, st);
+    const TileId t = stats_tile(d);
+    return t.splitk ? launch_conv_dma2_splitk(t.shape, a, ws, ws_bytes, st) : launch_conv_dma2(t.shape, a, st);
 }
 
 extern "C" int pemp_conv2d_hybrid_rows(const pemp_conv_desc* d) {
@@ -558,23 +536,29 @@ extern "C" int pemp_conv2d_hybrid_rows(const pemp_conv_desc* d) {
     return conv_dma2_hybrid_rows(d->N * d->Ho * d->Wo, d->Cout);
 }
 
+extern "C" int pemp_conv2d_tile_shape(int id, int* bm, int* bn) {
+    const TileId t = decode_tile(id);
+    if (!t.exists) return 0;
+    if (bm) *bm = kTileShapes[t.shape].bm;
+    if (bn) *bn = kTileShapes[t.shape].bn;
+    return 1;
+}
+
 extern "C" int pemp_conv2d_stats_rows(const pemp_conv_desc* d) {
     if (!d || d->N <= 0 || d->Ho <= 0 || d->Wo <= 0) return 0;
-    const int t = d->tile == 0 ? 3 : (d->tile > 30 ? d->tile - 30 : d->tile - 20);
-    if (t < 1 || t > 7) return 0;            // 28 / 29 (16-row and hybrid launches) have no statistics epilogue
-    const int bm = conv_dma2_tile_rows(t);
-    return bm ? cdiv(d->N * d->Ho * d->Wo, bm) : 0;
+    const TileId t = stats_tile(d);          // by shape alone: a refused id of the two decades (33) answers like its shape
+    if (t.family != TILE_DMA2 || t.shape > 7) return 0;      // 28 / 29 (16-row and hybrid launches) have no statistics epilogue
+    return cdiv(d->N * d->Ho * d->Wo, kTileShapes[t.shape].bm);
 }
 
 extern "C" size_t pemp_conv2d_splitk_workspace_bytes(const pemp_conv_desc* d) {
-    const int t = d ? (d->tile > 50 ? d->tile - 50 : d->tile - 30) : 0;     // 31..37: fp32 chain; 51..56: split3 (same plan)
-    if (!d || t < 1 || t > 7 || t == 3 || (d->tile > 50 && (t == 5 || t > 6)) || (d->tile > 37 && d->tile < 51) || d->N <= 0 || d->Ho <= 0 ||
-        d->Wo <= 0 || d->Cout <= 0 || d->Kpad < 32) return 0;
+    const TileId t = decode_tile(d ? d->tile : 0);      // 3x: fp32 chain; 5x: split3 (same plan)
+    if (!t.splitk || !t.exists || d->N <= 0 || d->Ho <= 0 || d->Wo <= 0 || d->Cout <= 0 || d->Kpad < 32) return 0;
     ConvArgs a;
     a.M = d->N * d->Ho * d->Wo;
     a.Cout = d->Cout;
     a.nk = d->Kpad / 32;
-    return conv_dma2_splitk_plan(t, a).ws_bytes;
+    return conv_dma2_splitk_plan(t.shape, a).ws_bytes;
 }
 
 extern "C" int pemp_conv2d_stats_nhwc_f32(const pemp_conv_desc* d, const float* x, const float* w, float* y, float* stats,

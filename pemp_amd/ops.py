@@ -6,6 +6,7 @@ tensors ``[N,H,W,C]`` whose last-dim stride is 1; a channel slice of a wider buf
 as a view (its pixel stride ``ld`` is taken from ``stride(2)``).
 """
 import ctypes as C
+import collections
 import json
 import os
 
@@ -64,24 +65,39 @@ class ConvParams:
         self.stride, self.pad, self.dil, self.kpad, self.stem, self.relu = stride, pad, dil, kpad, stem, relu
 
 
-#: kernel variants the autotuner may pick: id -> (BM, BN); ids >= 11 stage through LDS-DMA.  All variants
-#: accumulate in the same K order, so they are bit-identical and the choice only affects speed.
-TILE_VARIANTS = {13: (64, 64), 14: (128, 128), 12: (128, 64), 11: (128, 128), 15: (128, 64), 3: (64, 64),
-                 17: (256, 256), 16: (256, 128),    # 16/17: 8-wave blocks, 98/131 KB LDS, half the L2->LDS bytes per flop
-                 # 2x: the same shapes on conv_dma2.hip (buffer-addressed LDS-DMA, barrier inside the MFMA stream)
-                 23: (64, 64), 24: (128, 128), 22: (128, 64), 21: (128, 128), 25: (128, 64), 27: (256, 256), 26: (256, 128),
-                 # 28: 32 x 64 blocks of four 16 x 32 wave tiles on v_mfma_f32_16x16x4_f32 -- same K order, bit-identical (the fp32
-                 # MFMAs are sequential fma chains: scratch/mfma_eq); finer granularity for launches of a few rounds (one episode)
-                 28: (32, 64),
-                 # 29: hybrid launch for convs of a few rounds -- the rows that fill whole rounds of the chip on the 64 x 64 tile, the
-                 # remaining rows on 16-row wave tiles, one grid (csrc/conv_dma2.hip); other geometries run as 23
-                 29: (64, 64)}
+#: ---- tile ids (the scheme: include/pemp_hip.h, at pemp_conv2d_tile_shape).  The last digit of an id is its SHAPE, the decade its
+#: kernel family; csrc/conv_tiles.h holds the same table and tests/test_conv_tiles_cpu.py holds the two together.
+_SHAPES = {1: (128, 128), 2: (128, 64), 3: (64, 64), 4: (128, 128), 5: (128, 64), 6: (256, 128), 7: (256, 256),     # 4..7: 8 waves
+           8: (32, 64),        # four 16 x 32 wave tiles on v_mfma_f32_16x16x4_f32: finer granularity for launches of a few rounds
+           9: (64, 64)}        # hybrid launch: the rows that fill whole rounds on 64 x 64, the rest on 16-row wave tiles, one grid
+Tile = collections.namedtuple("Tile", "shape family splitk persistent_of")      # shape: (BM, BN)
+SPLIT3_PERSISTENT = {47: 43, 49: 46}
+TILES = {base + s: Tile(_SHAPES[s], family, base in (30, 50), None)
+         for family, base, shapes in (("igemm", 0, (1, 2, 3)),               # register staging
+                                      ("dma", 10, range(1, 8)),              # LDS-DMA staging, pointer-addressed
+                                      ("dma2", 20, range(1, 10)),            # buffer-addressed LDS-DMA, barrier inside the MFMA stream
+                                      ("dma2", 30, (1, 2, 4, 5, 6, 7)),      # ... with the last round of tiles split along K
+                                      ("split3", 40, (1, 2, 3, 4, 6)),       # fp32 operands as three bf16 pieces
+                                      ("split3", 50, (1, 2, 4, 6)))          # ... split-K
+         for s in shapes}
+TILES.update({t: TILES[of]._replace(persistent_of=of) for t, of in SPLIT3_PERSISTENT.items()})
+_NO_TILE = Tile(None, None, False, None)        # an id outside the registry: the library refuses it
+
+
+def tile_shape(t):
+    """(BM, BN) of tile id ``t``; None for an id no entry point takes (pemp_conv2d_tile_shape)."""
+    return TILES.get(t, _NO_TILE).shape
+
+
+#: kernel variants the autotuner may pick on the fp32 chain: id -> (BM, BN), in the order they are timed.  All of them accumulate
+#: in the same K order, so they are bit-identical and the choice only affects speed.  (29 runs as 23 where the geometry has no
+#: hybrid split.)
+TILE_VARIANTS = {t: TILES[t].shape for t in (13, 14, 12, 11, 15, 3, 17, 16, 23, 24, 22, 21, 25, 27, 26, 28, 29)}
 #: the split3 family (pemp_hip.h: fp32 operands split into three bf16 pieces on v_mfma_f32_32x32x16_bf16, fp32 accuracy; the
 #: shapes of 21..24 / 26): the variants of a layer that carries split weights (ConvParams.w3) -- bit-identical among themselves,
 #: not to the fp32-chain ids above.  51..56: their split-K forms (EVAL_SPLITK).  47 / 49: persistent forms of 43 / 46 (a resident
 #: grid that walks the tiles and overlaps one tile's epilogue with the next one's operand DMA; single convs only, no grouped form).
 SPLIT3_TILES = (43, 42, 41, 44, 46, 47, 49)
-SPLIT3_PERSISTENT = {47: 43, 49: 46}
 SPLIT3_SPLITK_TILES = (51, 52, 54, 56)
 SPLIT3_DEFAULT_TILE = 43
 AUTOTUNE = True
@@ -180,14 +196,24 @@ def _tunes(rows, least=1024):
     return (PICK_HOOK is not None or (AUTOTUNE and rows >= least)) and not torch.cuda.is_current_stream_capturing()
 
 
-def _pick_tile(launch, p, key, cout, only=None):
+def _fits(ids, *couts):
+    """The ids of ``ids``, in order, whose tile width divides every one of ``couts``."""
+    return [t for t in ids if all(c % _tile_bn(t) == 0 for c in couts)]
+
+
+def _choose_tile(key, rows, launch, cands, default):
+    """The variant of a call that names none: the remembered pick for ``key``; else, where a pick happens now (``_tunes(rows)``),
+    one of ``cands()`` by ``_pick_tile``; else ``default`` (not remembered: a later call may still tune)."""
+    tile = _TILE_CACHE.get(key)
+    if tile is None:
+        tile = _pick_tile(launch, key, cands()) if _tunes(rows) else default
+    return tile
+
+
+def _pick_tile(launch, key, cands):
     """Time the candidate variants for this (layer, input shape) and remember the fastest: two rounds over all
     candidates (the minimum of a variant's two timings counts: a round can be disturbed by whatever else the GPU is
     finishing), then a run-off between the best three with more repetitions."""
-    if only is None:
-        cands = [t for t, (bm, bn) in TILE_VARIANTS.items() if cout % bn == 0]
-    else:
-        cands = [t for t in only if cout % _tile_bn(t) == 0]
     if PICK_HOOK is not None:
         best = PICK_HOOK("conv", list(cands), key)
         if best not in cands:
@@ -217,9 +243,8 @@ def _pick_tile(launch, p, key, cout, only=None):
 
 
 def _tile_bn(t):
-    """BN of tile id ``t``: the split-K ids (31..37, 51..56) and the split3 ids (41..46) have the shapes of 21..27."""
-    t = SPLIT3_PERSISTENT.get(t, t)
-    return TILE_VARIANTS[t - 30 if t > 50 else t - 20 if t > 40 else t - 10 if t > 30 else t][1]
+    """BN of tile id ``t``."""
+    return TILES[t].shape[1]
 
 
 def pack_split3(w):
@@ -256,6 +281,28 @@ def pack_conv_weight(w_oihw, stem4=False):
     return w.reshape(co, kh * kw * ci), kh * kw * ci
 
 
+def _conv_geom(who, x, p, out, residual, dtype=torch.float32, out_dtype=None):
+    """What every conv wrapper checks of its tensors: x an NHWC view of the layer's channel count, ``out`` (allocated when None)
+    and ``residual`` NHWC views of the output's shape.  -> (n, h, w, cin, ldx, ho, wo, out, ldy, ldr)"""
+    ldx = _nhwc(x, "x", dtype)
+    n, h, w, cin = x.shape
+    if cin != p.cin:
+        raise ValueError(f"{who}: input has {cin} channels, layer expects {p.cin}")
+    ho = conv_out_size(h, p.kh, p.stride, p.pad, p.dil)
+    wo = conv_out_size(w, p.kw, p.stride, p.pad, p.dil)
+    if out is None:
+        out = torch.empty((n, ho, wo, p.cout), dtype=out_dtype or dtype, device=x.device)
+    ldy = _nhwc(out, "out", out_dtype or dtype)
+    if tuple(out.shape) != (n, ho, wo, p.cout):
+        raise ValueError(f"{who}: out shape {tuple(out.shape)} != {(n, ho, wo, p.cout)}")
+    ldr = 0
+    if residual is not None:
+        ldr = _nhwc(residual, "residual", dtype)
+        if tuple(residual.shape) != tuple(out.shape):
+            raise ValueError(f"{who}: residual shape mismatch")
+    return n, h, w, cin, ldx, ho, wo, out, ldy, ldr
+
+
 def conv2d(x, p, out=None, residual=None, shift_override=None, per_image_shift=False, relu=None, tile=0,
            pad_value=None, splitk=False, dropblock=None):
     """y = act(scale * conv(x, w) + shift (+ residual)).  x: NHWC view, returns NHWC tensor/view ``out``.
@@ -268,22 +315,7 @@ def conv2d(x, p, out=None, residual=None, shift_override=None, per_image_shift=F
         return _conv2d_bf16(x, p, out, residual, shift_override, per_image_shift, relu, tile, pad_value)
     lib = _lib.load()
     _chk_dev(x, p.w, out, residual)
-    ldx = _nhwc(x, "x")
-    n, h, w, cin = x.shape
-    if cin != p.cin:
-        raise ValueError(f"conv2d: input has {cin} channels, layer expects {p.cin}")
-    ho = conv_out_size(h, p.kh, p.stride, p.pad, p.dil)
-    wo = conv_out_size(w, p.kw, p.stride, p.pad, p.dil)
-    if out is None:
-        out = torch.empty((n, ho, wo, p.cout), dtype=torch.float32, device=x.device)
-    ldy = _nhwc(out, "out")
-    if tuple(out.shape) != (n, ho, wo, p.cout):
-        raise ValueError(f"conv2d: out shape {tuple(out.shape)} != {(n, ho, wo, p.cout)}")
-    ldr = 0
-    if residual is not None:
-        ldr = _nhwc(residual, "residual")
-        if tuple(residual.shape) != tuple(out.shape):
-            raise ValueError("conv2d: residual shape mismatch")
+    n, h, w, cin, ldx, ho, wo, out, ldy, ldr = _conv_geom("conv2d", x, p, out, residual)
     shift = p.shift if shift_override is None else shift_override
     if pad_value is not None:
         _chk_dev(pad_value)
@@ -315,19 +347,20 @@ def conv2d(x, p, out=None, residual=None, shift_override=None, per_image_shift=F
 
     def launch(t):
         d = ConvDesc(n, h, w, cin, ldx, ho, wo, p.cout, ldy, p.kh, p.kw, p.stride, p.pad, p.dil, ldr, p.kpad, flags, t)
-        pw = p.w3 if t > 40 else p.w
+        tl = TILES.get(t, _NO_TILE)
+        pw, sk = p.w3 if tl.family == "split3" else p.w, tl.splitk
         if dropblock is not None:
-            ws, ws_bytes = _splitk_ws(lib, d, x.device) if t > 30 else (None, 0)
+            ws, ws_bytes = _splitk_ws(lib, d, x.device) if sk else (None, 0)
             _check_sk(lib, lib.pemp_conv2d_dropblock_nhwc_f32(C.byref(d), _p(x), _p(pw), _p(out), _p(p.scale), _p(shift), _p(residual),
                                                               _p(dropblock[0]), _p(dropblock[1]), C.c_void_p(ws), ws_bytes, _stream()),
                       ws, "pemp_conv2d_dropblock_nhwc_f32")
             return
-        if t > 30 and pad_value is not None:
+        if sk and pad_value is not None:
             ws, ws_bytes = _splitk_ws(lib, d, x.device)
             _check_sk(lib, lib.pemp_conv2d_padv_splitk_nhwc_f32(C.byref(d), _p(x), _p(pw), _p(out), _p(p.scale), _p(shift), _p(residual),
                                                                 _p(pad_value), C.c_void_p(ws), ws_bytes, _stream()), ws,
                       "pemp_conv2d_padv_splitk_nhwc_f32")
-        elif t > 30:
+        elif sk:
             ws, ws_bytes = _splitk_ws(lib, d, x.device)
             _check_sk(lib, lib.pemp_conv2d_splitk_nhwc_f32(C.byref(d), _p(x), _p(pw), _p(out), _p(p.scale), _p(shift), _p(residual),
                                                            C.c_void_p(ws), ws_bytes, _stream()), ws, "pemp_conv2d_splitk_nhwc_f32")
@@ -341,23 +374,16 @@ def conv2d(x, p, out=None, residual=None, shift_override=None, per_image_shift=F
     if tile == 0:
         key = (p.cin, p.cout, p.kh, p.kw, p.stride, p.pad, p.dil, (6 if dropblock is not None else 4) if splitk else int(p.stem) + (7 if dropblock is not None else 0),
                n, h, w, int(residual is not None), int(pad_value is not None)) + ((3,) if s3 else ())    # 3: split3 picks
-        tile = _TILE_CACHE.get(key)
-        if tile is None and s3:
-            only = list(SPLIT3_TILES) + (list(SPLIT3_SPLITK_TILES) if splitk else [])
-            tile = _pick_tile(launch, p, key, p.cout, only=only) if _tunes(n * ho * wo) else SPLIT3_DEFAULT_TILE
-        if tile is None:
-            if dropblock is not None:
-                only = list(GROUP_TILES) + (list(SPLITK_TILES) if splitk else [])
-            else:
-                only = list(TILE_VARIANTS) + list(SPLITK_TILES) if splitk else None
-            if _tunes(n * ho * wo):
-                if only is None:
-                    only = list(TILE_VARIANTS)
-                if 29 in only and not (hybrid_rows(n, ho, wo, p.cout) and dma2_supported(x, p)):
-                    only = [t for t in only if t != 29]       # no hybrid launch for this geometry / layer: id 29 would run as 23 (or 13)
-                tile = _pick_tile(launch, p, key, p.cout, only=only)
-            else:
-                tile = DEFAULT_TILE + (10 if dropblock is not None else 0)
+        if s3:
+            cands = lambda: _fits(list(SPLIT3_TILES) + (list(SPLIT3_SPLITK_TILES) if splitk else []), p.cout)
+        else:
+            def cands():
+                ids = list(GROUP_TILES if dropblock is not None else TILE_VARIANTS) + (list(SPLITK_TILES) if splitk else [])
+                if 29 in ids and not (hybrid_rows(n, ho, wo, p.cout) and dma2_supported(x, p)):
+                    ids.remove(29)         # no hybrid launch for this geometry / layer: id 29 would run as 23 (or 13)
+                return _fits(ids, p.cout)
+        tile = _choose_tile(key, n * ho * wo, launch, cands,
+                            SPLIT3_DEFAULT_TILE if s3 else DEFAULT_TILE + (10 if dropblock is not None else 0))
     launch(tile)
     return out
 
@@ -402,23 +428,9 @@ def _conv2d_bf16(x, p, out, residual, shift_override, per_image_shift, relu, til
     _chk_dev(x, p.w, out, residual, pad_value)
     if p.w.dtype != torch.bfloat16 or p.stem:
         raise ValueError("conv2d (bf16 input): the layer's weights must be packed as bf16 (engine precision 'bf16'); no stem")
-    ldx = _nhwc(x, "x", torch.bfloat16)
-    n, h, w, cin = x.shape
-    if cin != p.cin:
-        raise ValueError(f"conv2d: input has {cin} channels, layer expects {p.cin}")
-    ho = conv_out_size(h, p.kh, p.stride, p.pad, p.dil)
-    wo = conv_out_size(w, p.kw, p.stride, p.pad, p.dil)
-    if out is None:
-        out = torch.empty((n, ho, wo, p.cout), dtype=torch.bfloat16, device=x.device)
+    n, h, w, cin, ldx, ho, wo, out, ldy, ldr = _conv_geom("conv2d", x, p, out, residual, torch.bfloat16,
+                                                          None if out is None else out.dtype)
     out_f32 = out.dtype == torch.float32
-    ldy = _nhwc(out, "out", out.dtype)
-    if tuple(out.shape) != (n, ho, wo, p.cout):
-        raise ValueError(f"conv2d: out shape {tuple(out.shape)} != {(n, ho, wo, p.cout)}")
-    ldr = 0
-    if residual is not None:
-        ldr = _nhwc(residual, "residual", torch.bfloat16)
-        if tuple(residual.shape) != tuple(out.shape):
-            raise ValueError("conv2d: residual shape mismatch")
     if pad_value is not None and (pad_value.numel() != cin or pad_value.dtype != torch.bfloat16 or not pad_value.is_contiguous()):
         raise ValueError(f"conv2d: pad_value must be a contiguous bf16 [{cin}] vector")
     shift = p.shift if shift_override is None else shift_override
@@ -431,12 +443,7 @@ def _conv2d_bf16(x, p, out, residual, shift_override, per_image_shift, relu, til
 
     if tile == 0:
         key = (p.cin, p.cout, p.kh, p.kw, p.stride, p.pad, p.dil, 5, n, h, w, int(residual is not None), int(pad_value is not None))   # 5: bf16
-        tile = _TILE_CACHE.get(key)
-        if tile is None:
-            if _tunes(n * ho * wo):
-                tile = _pick_tile(launch, p, key, p.cout, only=GROUP_TILES)
-            else:
-                tile = 24 if p.cout % 128 == 0 else 23
+        tile = _choose_tile(key, n * ho * wo, launch, lambda: _fits(GROUP_TILES, p.cout), 24 if p.cout % 128 == 0 else 23)
     launch(tile)
     return out
 
@@ -493,18 +500,9 @@ def conv2d_group(xs, ps, outs, pad_values=None, residuals=None, tile=0):
         _chk_dev(x, p.w, out, pv, res)
         if p.stem:
             raise ValueError("conv2d_group: no stem convs")
-        ldx, ldy = _nhwc(x, "x"), _nhwc(out, "out")
-        nb, h, w, cin = x.shape
-        if cin != p.cin:
-            raise ValueError(f"conv2d_group: input has {cin} channels, layer expects {p.cin}")
-        ho, wo = conv_out_size(h, p.kh, p.stride, p.pad, p.dil), conv_out_size(w, p.kw, p.stride, p.pad, p.dil)
-        if tuple(out.shape) != (nb, ho, wo, p.cout):
-            raise ValueError(f"conv2d_group: out shape {tuple(out.shape)} != {(nb, ho, wo, p.cout)}")
-        ldr = 0
-        if res is not None:
-            ldr = _nhwc(res, "residual")
-            if tuple(res.shape) != tuple(out.shape):
-                raise ValueError("conv2d_group: residual shape mismatch")
+        if out is None:
+            raise ValueError("conv2d_group: every member needs its output")
+        nb, h, w, cin, ldx, ho, wo, out, ldy, ldr = _conv_geom("conv2d_group", x, p, out, res)
         descs.append((nb, h, w, cin, ldx, ho, wo, p.cout, ldy, p.kh, p.kw, p.stride, p.pad, p.dil, ldr, p.kpad, CONV_RELU if p.relu else 0))
         keys += [p.cin, p.cout, p.kh, p.stride, p.pad, p.dil, nb, h, w, int(res is not None), int(pv is not None)]
     s3 = all(p.w3 is not None for p in ps)
@@ -527,18 +525,12 @@ def conv2d_group(xs, ps, outs, pad_values=None, residuals=None, tile=0):
 
     if tile == 0:
         key = (-8 if s3 else -7,) + tuple(keys)     # -7: a grouped launch, -8: of the split3 family (the cache file stores keys as integer lists)
-        tile = _TILE_CACHE.get(key)
-        if tile is None and s3:
-            tile = SPLIT3_DEFAULT_TILE
-            if _tunes(max(d[0] * d[5] * d[6] for d in descs)):
-                tile = _pick_tile(launch, None, key, min(p.cout for p in ps),
-                                  only=[t for t in SPLIT3_TILES if t not in SPLIT3_PERSISTENT and all(p.cout % _tile_bn(t) == 0 for p in ps)])
-        if tile is None:
-            if _tunes(max(d[0] * d[5] * d[6] for d in descs)):
-                tile = _pick_tile(launch, None, key, min(p.cout for p in ps),
-                                  only=[t for t in GROUP_TILES + (28,) if all(p.cout % TILE_VARIANTS[t][1] == 0 for p in ps)])
-            else:
-                tile = DEFAULT_TILE + 10
+        couts = [p.cout for p in ps]
+        if s3:
+            cands = lambda: _fits([t for t in SPLIT3_TILES if t not in SPLIT3_PERSISTENT], *couts)
+        else:
+            cands = lambda: _fits(GROUP_TILES + (28,), *couts)
+        tile = _choose_tile(key, max(d[0] * d[5] * d[6] for d in descs), launch, cands, SPLIT3_DEFAULT_TILE if s3 else DEFAULT_TILE + 10)
     launch(tile)
     return outs
 
@@ -612,12 +604,22 @@ def _check_sk(lib, rc, ws, what):
 
 def _stats_rows(m, tile):
     """Partial rows the stats / bnbwd epilogues of variant ``tile`` write: one per row tile (pemp_conv2d_stats_rows)."""
-    bm = TILE_VARIANTS[tile - 10 if tile > 30 else tile][0]
+    bm = TILES[tile].shape[0]
     return (m + bm - 1) // bm
 
 
 def _train_tiles(cout):
-    return [t for t in list(range(21, 28)) + list(SPLITK_TILES) if cout % TILE_VARIANTS[t - 10 if t > 30 else t][1] == 0]
+    """What the statistics / BatchNorm-backward convs may pick for ``cout`` channels, split-K forms included."""
+    return _fits(list(range(21, 28)) + list(SPLITK_TILES), cout)
+
+
+def _stats_launch(lib, fn, what, desc, x, *operands):
+    """launch(t) of a statistics-epilogue entry ``fn(desc(t), operands..., ws, ws_bytes, stream)``."""
+    def launch(t):
+        d = ConvDesc(*desc, t)
+        ws, ws_bytes = _splitk_ws(lib, d, x.device) if TILES.get(t, _NO_TILE).splitk else (None, 0)
+        _check_sk(lib, fn(C.byref(d), *operands, C.c_void_p(ws), ws_bytes, _stream()), ws, what)
+    return launch
 
 
 def conv2d_stats(x, p, out=None, tile=0):
@@ -626,34 +628,17 @@ def conv2d_stats(x, p, out=None, tile=0):
     (callers then use conv2d + bn_stats); ``stats_supported`` says so beforehand."""
     lib = _lib.load()
     _chk_dev(x, p.w, out)
-    ldx = _nhwc(x, "x")
-    n, h, w, cin = x.shape
-    if cin != p.cin:
-        raise ValueError(f"conv2d_stats: input has {cin} channels, layer expects {p.cin}")
+    n, h, w, cin, ldx, ho, wo, out, ldy, _ = _conv_geom("conv2d_stats", x, p, out, None)
     if p.stem or p.scale is not None:
         raise ValueError("conv2d_stats: plain (non-stem, unscaled) convs only")
-    ho = conv_out_size(h, p.kh, p.stride, p.pad, p.dil)
-    wo = conv_out_size(w, p.kw, p.stride, p.pad, p.dil)
-    if out is None:
-        out = torch.empty((n, ho, wo, p.cout), dtype=torch.float32, device=x.device)
-    ldy = _nhwc(out, "out")
     m = n * ho * wo
     part = torch.empty(((m + 63) // 64, 2, p.cout), dtype=torch.float32, device=x.device)     # the smallest row tile has 64 rows
-
-    def launch(t):
-        d = ConvDesc(n, h, w, cin, ldx, ho, wo, p.cout, ldy, p.kh, p.kw, p.stride, p.pad, p.dil, 0, p.kpad, 0, t)
-        ws, ws_bytes = _splitk_ws(lib, d, x.device) if t > 30 else (None, 0)
-        _check_sk(lib, lib.pemp_conv2d_stats_nhwc_f32(C.byref(d), _p(x), _p(p.w), _p(out), _p(part), C.c_void_p(ws), ws_bytes,
-                                                      _stream()), ws, "pemp_conv2d_stats_nhwc_f32")
-
+    launch = _stats_launch(lib, lib.pemp_conv2d_stats_nhwc_f32, "pemp_conv2d_stats_nhwc_f32",
+                           (n, h, w, cin, ldx, ho, wo, p.cout, ldy, p.kh, p.kw, p.stride, p.pad, p.dil, 0, p.kpad, 0),
+                           x, _p(x), _p(p.w), _p(out), _p(part))
     if tile == 0:
         key = (p.cin, p.cout, p.kh, p.kw, p.stride, p.pad, p.dil, 2, n, h, w, 0, 0)     # 2: the stats epilogue
-        tile = _TILE_CACHE.get(key)
-        if tile is None:
-            if _tunes(m):
-                tile = _pick_tile(launch, p, key, p.cout, only=_train_tiles(p.cout) if SPLITK else range(21, 28))
-            else:
-                tile = DEFAULT_TILE + 10
+        tile = _choose_tile(key, m, launch, lambda: _train_tiles(p.cout) if SPLITK else _fits(range(21, 28), p.cout), DEFAULT_TILE + 10)
     launch(tile)
     return out, part[:_stats_rows(m, tile)]
 
@@ -667,45 +652,22 @@ def conv2d_bnbwd(x, p, bn, residual=None, out=None, tile=0):
     lib = _lib.load()
     z, mask = bn["z"], bn.get("mask")
     _chk_dev(x, p.w, out, residual, z, mask, bn["mean"], bn["invstd"])
-    ldx = _nhwc(x, "x")
-    n, h, w, cin = x.shape
-    if cin != p.cin:
-        raise ValueError(f"conv2d_bnbwd: input has {cin} channels, layer expects {p.cin}")
+    n, h, w, cin, ldx, ho, wo, out, ldy, ldr = _conv_geom("conv2d_bnbwd", x, p, out, residual)
     if p.stem or p.scale is not None or p.shift is not None:
         raise ValueError("conv2d_bnbwd: plain (non-stem, no affine) convs only")
-    ho = conv_out_size(h, p.kh, p.stride, p.pad, p.dil)
-    wo = conv_out_size(w, p.kw, p.stride, p.pad, p.dil)
-    if out is None:
-        out = torch.empty((n, ho, wo, p.cout), dtype=torch.float32, device=x.device)
-    ldy = _nhwc(out, "out")
     if tuple(z.shape) != tuple(out.shape):
         raise ValueError(f"conv2d_bnbwd: the BatchNorm input is {tuple(z.shape)}, the gradient {tuple(out.shape)}")
     ldz = _nhwc(z, "z")
     m = n * ho * wo
     if mask is not None and (mask.dtype != torch.int32 or not mask.is_contiguous() or mask.numel() != m * (p.cout // 32)):
         raise ValueError("conv2d_bnbwd: mask must be a contiguous int32 [M, Cout/32] tensor")
-    ldr = 0
-    if residual is not None:
-        ldr = _nhwc(residual, "residual")
-        if tuple(residual.shape) != tuple(out.shape):
-            raise ValueError("conv2d_bnbwd: residual shape mismatch")
     part = torch.empty(((m + 63) // 64, 2, p.cout), dtype=torch.float32, device=x.device)
-
-    def launch(t):
-        d = ConvDesc(n, h, w, cin, ldx, ho, wo, p.cout, ldy, p.kh, p.kw, p.stride, p.pad, p.dil, ldr, p.kpad, 0, t)
-        ws, ws_bytes = _splitk_ws(lib, d, x.device) if t > 30 else (None, 0)
-        _check_sk(lib, lib.pemp_conv2d_bnbwd_nhwc_f32(C.byref(d), _p(x), _p(p.w), _p(out), _p(residual), _p(mask), _p(z), ldz,
-                                                      _p(bn["mean"]), _p(bn["invstd"]), _p(part), C.c_void_p(ws), ws_bytes,
-                                                      _stream()), ws, "pemp_conv2d_bnbwd_nhwc_f32")
-
+    launch = _stats_launch(lib, lib.pemp_conv2d_bnbwd_nhwc_f32, "pemp_conv2d_bnbwd_nhwc_f32",
+                           (n, h, w, cin, ldx, ho, wo, p.cout, ldy, p.kh, p.kw, p.stride, p.pad, p.dil, ldr, p.kpad, 0),
+                           x, _p(x), _p(p.w), _p(out), _p(residual), _p(mask), _p(z), ldz, _p(bn["mean"]), _p(bn["invstd"]), _p(part))
     if tile == 0:
         key = (p.cin, p.cout, p.kh, p.kw, p.stride, p.pad, p.dil, 3, n, h, w, int(residual is not None), 0)   # 3: this epilogue
-        tile = _TILE_CACHE.get(key)
-        if tile is None:
-            if _tunes(m):
-                tile = _pick_tile(launch, p, key, p.cout, only=_train_tiles(p.cout) if SPLITK else range(21, 28))
-            else:
-                tile = DEFAULT_TILE + 10
+        tile = _choose_tile(key, m, launch, lambda: _train_tiles(p.cout) if SPLITK else _fits(range(21, 28), p.cout), DEFAULT_TILE + 10)
     launch(tile)
     return out, part[:_stats_rows(m, tile)]
 

@@ -33,7 +33,7 @@ for (N, name) in ((2, "eval 1 episode"), (8, "train 4 episodes")):
         prm = ops.ConvParams(packed, None, torch.zeros(cout, device=dev), cin, cout, k, k, 1, d if k == 3 else 0, d, kpad, False, True)
         row = []
         for tile in ops.SPLITK_TILES:
-            if cout % ops.TILE_VARIANTS[tile - 10][1]:
+            if cout % ops.tile_shape(tile)[1]:
                 continue
             try:
                 us = t(lambda: ops.conv2d(x, prm, tile=tile))

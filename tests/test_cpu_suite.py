@@ -1051,7 +1051,7 @@ def test_bench_counts_the_work_of_every_gemm_entry_point():
     import ctypes as C
     import bench
     from pemp_amd import _lib, ops
-    launching = [n for n in _lib.SYMBOLS if n.startswith("pemp_conv2d") and not n.endswith("_bytes") and not n.endswith("_rows")]        # (_bytes / _rows: queries, they launch nothing)
+    launching = [n for n in _lib.SYMBOLS if n.startswith("pemp_conv2d") and not n.endswith(("_bytes", "_rows", "_tile_shape"))]        # (queries: they launch nothing)
     assert len(launching) >= 10
     for n in launching:
         assert bench.CLASS_OF.get(n) in ("conv", "wgrad"), n

@@ -150,7 +150,7 @@ def test_conv_with_batch_statistics_in_the_epilogue(hip_lib, dev, case):
         return torch.cat([t, torch.zeros(pad, Cout, dtype=torch.float64)]).view(-1, bm, Cout).sum(1)
 
     def check_partials(z, part, tile):
-        bm = ops.TILE_VARIANTS[tile - 10 if tile > 30 else tile][0]
+        bm = ops.tile_shape(tile)[0]
         assert part.shape == ((M + bm - 1) // bm, 2, Cout) and part.is_contiguous(), tile     # one row per row tile
         zd = z.reshape(M, Cout).double().cpu()
         pc = part.double().cpu()
@@ -168,7 +168,7 @@ def test_conv_with_batch_statistics_in_the_epilogue(hip_lib, dev, case):
             first = part.clone()
     # split-K variants: the remainder tiles add K slices in a different grouping -> fp32 rounding of the regrouped sum
     # (|d| <= 1e-5 max|z| at K <= 2304); reproducible from launch to launch; the partial sums are those of the stored values
-    for tile in [t for t in ops.SPLITK_TILES if Cout % ops.TILE_VARIANTS[t - 10][1] == 0]:
+    for tile in [t for t in ops.SPLITK_TILES if Cout % ops.tile_shape(t)[1] == 0]:
         z, part = ops.conv2d_stats(x, prm, tile=tile)
         assert (z - z_ref).abs().max() <= 1e-5 * z_ref.abs().max(), tile
         z2, part2 = ops.conv2d_stats(x, prm, tile=tile)
@@ -247,7 +247,7 @@ def test_input_gradient_conv_with_batchnorm_backward_in_the_epilogue(hip_lib, de
         return torch.cat([t, torch.zeros(pad, Cout, dtype=torch.float64)]).view(-1, bm, Cout).sum(1)
 
     def check_partials(gv, part, tile):
-        bm = ops.TILE_VARIANTS[tile - 10 if tile > 30 else tile][0]
+        bm = ops.tile_shape(tile)[0]
         assert part.shape == ((M + bm - 1) // bm, 2, Cout), tile
         gs = gv.view(M, Cout).double().cpu()
         pc = part.double().cpu()
@@ -261,7 +261,7 @@ def test_input_gradient_conv_with_batchnorm_backward_in_the_epilogue(hip_lib, de
         check_partials(g, part, tile)
         if first is None:
             first = part.clone()
-    for tile in [t for t in ops.SPLITK_TILES if Cout % ops.TILE_VARIANTS[t - 10][1] == 0]:      # split-K variants (see above)
+    for tile in [t for t in ops.SPLITK_TILES if Cout % ops.tile_shape(t)[1] == 0]:      # split-K variants (see above)
         g, part = ops.conv2d_bnbwd(x, prm, bn, residual=add, tile=tile)
         assert (g - g_ref).abs().max() <= 1e-5 * dy.abs().max(), tile
         check_partials(g, part, tile)
@@ -470,7 +470,7 @@ def test_split_k_conv_variants_match_the_unsplit_conv(hip_lib, dev, case):
     ref = ops.conv2d(x, prm, residual=res, tile=13)
     lib = hip_lib
     M = N * H * W
-    for tile in [t for t in ops.SPLITK_TILES if Cout % ops.TILE_VARIANTS[t - 10][1] == 0]:
+    for tile in [t for t in ops.SPLITK_TILES if Cout % ops.tile_shape(t)[1] == 0]:
         y1 = ops.conv2d(x, prm, residual=res, tile=tile)
         y2 = ops.conv2d(x, prm, residual=res, tile=tile)
         assert torch.equal(y1, y2), tile
@@ -492,7 +492,7 @@ def test_split_k_hand_off_is_complete_and_stable_under_uneven_load(hip_lib, dev,
     sum -- while a second stream keeps the memory system busy with a large copy and idle gaps (uneven load: the
     condition under which a missing release / acquire shows, MI355X_MICROARCH.md "Test every hand-off")."""
     from pemp_amd import ops
-    bm, bn = ops.TILE_VARIANTS[tile - 10]
+    bm, bn = ops.tile_shape(tile)
     Cin, Cout = 256, bn                                     # one column of tiles: the tile count is ceil(M / bm)
     w = _rand(Cout, Cin, 1, 1, seed=2, lo=-0.1, hi=0.1)
     packed, kpad = ops.pack_conv_weight(w.to(dev))
@@ -588,7 +588,7 @@ def test_split_k_with_a_padding_value_matches_the_unsplit_conv(hip_lib, dev):
         ref = ops.conv2d(x, prm, pad_value=pv, tile=27)
         plain = ops.conv2d(x, prm, tile=27)
         assert (ref - plain).abs().max() > 1e-2                                 # the padding value really enters
-        for tile in [t for t in ops.SPLITK_TILES if Cout % ops.TILE_VARIANTS[t - 10][1] == 0]:
+        for tile in [t for t in ops.SPLITK_TILES if Cout % ops.tile_shape(t)[1] == 0]:
             y1 = ops.conv2d(x, prm, pad_value=pv, tile=tile).clone()
             y2 = ops.conv2d(x, prm, pad_value=pv, tile=tile)
             assert torch.equal(y1, y2), (d, tile)
