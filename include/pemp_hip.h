@@ -67,6 +67,11 @@ int pemp_abi_version(void);
  *     4x  41..44, 46    split3: fp32 operands as three bf16 pieces on v_mfma_f32_32x32x16_bf16 (pemp_pack_split3_bf16);
  *         47, 49        persistent forms of 43 and 46: a resident grid walks the tiles
  *     5x  51, 52, 54, 56  split3 with the last round split along K
+ *     7x  71, 72          split3, activation-stationary (1x1 convs without padding, Kpad <= 256, pemp_conv2d_nhwc_f32 only): a
+ *                       block of 4 waves keeps 128 output rows x K of split activations in registers and walks ALL of Cout, 128
+ *                       (71) or 64 (72) columns at a time, with only the packed weights streaming through LDS; no padding value,
+ *                       per-image shift, workspace or grouped form, operands below 2 GiB -- anything else is an error.
+ *                       Bit-identical to 4x (same MFMA order per accumulator, same epilogue arithmetic)
  *   0x, 1x and 2x are bit-identical to each other, and so are 4x among themselves.  Where an id's own kernels do not take a
  *   geometry, pemp_conv2d_nhwc_f32 and its _padv_ / _splitk_ forms fall back in this order, with the same results: 3x -> 2x,
  *   29 -> 23 (no hybrid split), 2x -> 1x (28 -> 13); 4x / 5x never fall back (an error instead).  Which ids an entry takes is

@@ -321,6 +321,9 @@ int launch_conv_dma2_split3(int shape, ConvArgs a, void* ws, size_t ws_bytes, bo
 int launch_conv_dma2_group_split3(int shape, ConvGroupArgs& g, hipStream_t st);
 // its persistent forms (shapes 3 and 6): a resident grid walks the tiles
 int launch_conv_dma2_split3_persist(int shape, const ConvArgs& a, hipStream_t st);
+// conv_panel.hip: the activation-stationary split3 form of short-K 1x1 convs (shapes 1 and 2 = 128 / 64 columns at a time)
+bool conv_panel_supported(const ConvArgs& a);
+int launch_conv_panel(int shape, const ConvArgs& a, hipStream_t st);
 int conv_dma2_simds();                                                     // SIMDs of the current device (4 per CU)
 int pack_split3(const float* w, void* out, int cout, int kpad, hipStream_t st);
 // conv_stem_pool.hip: the 7x7 / 2 / 3 NHWC4 stem (split3 weights) + its 3 / 2 / 1 ceil-mode max-pool in one launch (PEMP_CONV_POOL3S2)

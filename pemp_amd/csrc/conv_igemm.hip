@@ -339,7 +339,7 @@ static int conv2d_impl(const pemp_conv_desc* d, const float* x, const float* w, 
     }
     TileId t = decode_tile(tile);
     if (d->flags & PEMP_CONV_POOL3S2) {     // the fused stem (conv_stem_pool.hip): y is the pooled tensor
-        PEMP_REQUIRE(stem && t.family == TILE_SPLIT3 && !t.splitk && !residual && !pad_value,
+        PEMP_REQUIRE(stem && t.family == TILE_SPLIT3 && !t.splitk && !t.panel && !residual && !pad_value,
                      "conv2d: PEMP_CONV_POOL3S2 needs PEMP_CONV_STEM4 with split3 weights (a tile id 41..49), no residual, no padding value");
         return launch_conv_stem_pool(a, (hipStream_t)stream);
     }
@@ -352,6 +352,11 @@ static int conv2d_impl(const pemp_conv_desc* d, const float* x, const float* w, 
         PEMP_REQUIRE(!stem && conv_dma2_supported(a) && (long long)a.Cout * a.Kpad * 6 < (1ll << 31),
                      "conv2d: split3 tile %d needs a geometry of the buffer-addressed kernels (no stem, <= 32 taps, operands < 2 GiB)", tile);
         PEMP_REQUIRE_COUT("conv2d", t.shape, a.Cout);
+        if (t.panel) {                   // conv_panel.hip: same results as 41..49 where it applies, an error elsewhere
+            PEMP_REQUIRE(!ws && conv_panel_supported(a),
+                         "conv2d: tile %d needs a 1x1 conv without padding, Kpad <= 256, no padding value / per-image shift / workspace, operands < 2 GiB", tile);
+            return launch_conv_panel(t.shape, a, st);
+        }
         if (t.persistent) return launch_conv_dma2_split3_persist(t.shape, a, st);      // same results as the id it walks
         return launch_conv_dma2_split3(t.shape, a, ws, ws_bytes, t.splitk, st);
     }
@@ -395,7 +400,7 @@ extern "C" int pemp_conv2d_group_nhwc_f32(int n, const pemp_conv_desc* d, const 
     g.n = n;
     const int tile = d[0].tile;
     const TileId t = decode_tile(tile);
-    const bool s3 = t.family == TILE_SPLIT3 && t.exists && !t.splitk && !t.persistent;
+    const bool s3 = t.family == TILE_SPLIT3 && t.exists && !t.splitk && !t.persistent && !t.panel;
     PEMP_REQUIRE((t.family == TILE_DMA2 && !t.splitk && t.shape <= 8) || s3, "conv2d_group: tile must be one of the buffer-addressed variants 21..28 or 41..44, 46, got %d", tile);
     for (int i = 0; i < n; ++i) {
         PEMP_REQUIRE(d[i].tile == tile, "conv2d_group: every member must name the same tile variant");

@@ -44,6 +44,7 @@ struct FamGroup { static constexpr unsigned shapes = shape_bits({1, 2, 3, 4, 5, 
 struct FamSplitK { static constexpr unsigned shapes = shape_bits({1, 2, 4, 5, 6, 7}); static constexpr bool s3 = false; };
 struct FamSplit3 { static constexpr unsigned shapes = shape_bits({1, 2, 3, 4, 6}); static constexpr bool s3 = true; };
 struct FamPersist { static constexpr unsigned shapes = shape_bits({3, 6}); static constexpr bool s3 = true; };
+struct FamPanel { static constexpr unsigned shapes = shape_bits({1, 2}); static constexpr bool s3 = true; };     // conv_panel.hip: 128 rows x all of Cout, BN columns at a time
 
 template <class Fam> inline bool in_family(int shape) { return shape >= 1 && shape <= 9 && ((Fam::shapes >> shape) & 1u); }
 
@@ -69,11 +70,16 @@ struct TileId {
     bool splitk;       // 3x / 5x: the last round of tiles split along K
     bool persistent;   // 47, 49
     bool exists;       // some entry point takes the id
+    bool panel;        // 71, 72: the activation-stationary 1x1 form (conv_panel.hip)
 };
 
 inline TileId decode_tile(int id) {
-    TileId t = {TILE_NONE, 0, false, false, false};
+    TileId t = {TILE_NONE, 0, false, false, false, false};
     const int decade = id / 10, s = id % 10;
+    if (decade == 7 && in_family<FamPanel>(s)) {
+        t.family = TILE_SPLIT3, t.shape = s, t.exists = t.panel = true;
+        return t;
+    }
     if (id < 1 || id > 56 || s == 0) return t;
     t.shape = s;
     if (decade == 0) t.family = TILE_IGEMM, t.exists = in_family<FamIgemm>(s);

@@ -81,6 +81,9 @@ TILES = {base + s: Tile(_SHAPES[s], family, base in (30, 50), None)
                                       ("split3", 50, (1, 2, 4, 6)))          # ... split-K
          for s in shapes}
 TILES.update({t: TILES[of]._replace(persistent_of=of) for t, of in SPLIT3_PERSISTENT.items()})
+#: the activation-stationary split3 form of short-K 1x1 convs (csrc/conv_panel.hip): a block keeps 128 rows x K of split activations in
+#: registers and walks all of Cout, 128 (71) or 64 (72) columns at a time
+TILES.update({70 + s: Tile(_SHAPES[s], "split3", False, None) for s in (1, 2)})
 _NO_TILE = Tile(None, None, False, None)        # an id outside the registry: the library refuses it
 
 
@@ -100,6 +103,10 @@ TILE_VARIANTS = {t: TILES[t].shape for t in (13, 14, 12, 11, 15, 3, 17, 16, 23, 
 SPLIT3_TILES = (43, 42, 41, 44, 46, 47, 49)
 SPLIT3_SPLITK_TILES = (51, 52, 54, 56)
 SPLIT3_DEFAULT_TILE = 43
+#: ... and their activation-stationary forms for 1x1 convs with Kpad <= 256 (bit-identical to the ids above): a registry of
+#: their own, offered to timing-based picks only, where ``_panel_ok`` holds (PEMP_SPLIT3_PANEL=0: never, the A/B switch)
+SPLIT3_PANEL_TILES = (71, 72)
+SPLIT3_PANEL = os.environ.get("PEMP_SPLIT3_PANEL", "1") != "0"
 AUTOTUNE = True
 #: test hook: ``PICK_HOOK(kind, cands, key) -> one of cands`` decides every kernel-variant pick INSTEAD of timing (kind "conv":
 #: tile ids, "wgrad": block counts / (tile kind, block count) pairs), at any problem size.  Timing-based picks differ from box
@@ -247,6 +254,14 @@ def _tile_bn(t):
     return TILES[t].shape[1]
 
 
+def _panel_ok(p, n, ho, wo, ldx, ldy, ldr, h, w, pad_value, splitk, per_image_shift):
+    """Whether the ids of SPLIT3_PANEL_TILES take this call (conv_panel.hip: conv_panel_supported)."""
+    lim = 1 << 31
+    return (SPLIT3_PANEL and PICK_HOOK is None and p.kh == 1 and p.kw == 1 and p.pad == 0 and p.kpad <= 256 and p.cin % 32 == 0
+            and pad_value is None and not splitk and not per_image_shift and n * h * w * ldx * 4 < lim
+            and n * ho * wo * max(ldy, ldr) * 4 < lim)
+
+
 def pack_split3(w):
     """KRSC [Cout, Kpad] fp32 (Kpad % 32 == 0) -> its split3 form (pemp_pack_split3_bf16): bf16 [Cout, Kpad / 32, 3, 32], per row
     and 32-channel K step the planes h, m, l with w == h + m + l exactly."""
@@ -375,7 +390,13 @@ def conv2d(x, p, out=None, residual=None, shift_override=None, per_image_shift=F
         key = (p.cin, p.cout, p.kh, p.kw, p.stride, p.pad, p.dil, (6 if dropblock is not None else 4) if splitk else int(p.stem) + (7 if dropblock is not None else 0),
                n, h, w, int(residual is not None), int(pad_value is not None)) + ((3,) if s3 else ())    # 3: split3 picks
         if s3:
-            cands = lambda: _fits(list(SPLIT3_TILES) + (list(SPLIT3_SPLITK_TILES) if splitk else []), p.cout)
+            # a pick among candidates that include the panel ids is remembered under a key of its own (71): a call of the same
+            # geometry that they do not take (a per-image shift, operands of 2 GiB) must never replay it
+            panel = _panel_ok(p, n, ho, wo, ldx, ldy, ldr, h, w, pad_value, splitk, per_image_shift)
+            if panel:
+                key += (71,)
+            cands = lambda: _fits(list(SPLIT3_TILES) + (list(SPLIT3_SPLITK_TILES) if splitk else []) +
+                                  (list(SPLIT3_PANEL_TILES) if panel else []), p.cout)
         else:
             def cands():
                 ids = list(GROUP_TILES if dropblock is not None else TILE_VARIANTS) + (list(SPLITK_TILES) if splitk else [])

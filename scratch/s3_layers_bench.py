@@ -17,11 +17,14 @@ from pemp_amd import ops  # noqa: E402
 
 UNSPLIT = (43, 42, 41, 44, 46, 47, 49)     # 47 / 49: persistent forms of 43 / 46
 SPLIT = (52, 51, 54, 56)
-# (cin, cout, k, dil, residual, padding value): the six geometries that carry ~81 % of the step's conv time, and the 3 x 3 layer
+PANEL = ops.SPLIT3_PANEL_TILES             # 71 / 72: activation-stationary forms (1x1, Kpad <= 256; conv_panel.hip)
+# (cin, cout, k, dil, residual, padding value[, stride, maps of HW x HW]): the six geometries that carry ~81 % of the step's conv time, and the 3 x 3 layer
 # once more with a padding value (the PADV instantiation)
 LAYERS = ((256, 1024, 1, 1, True, False), (512, 1024, 1, 1, False, False), (1024, 256, 1, 1, False, False),
           (256, 256, 3, 2, False, False), (128, 512, 1, 1, True, False), (1024, 512, 1, 1, False, False),
-          (256, 256, 3, 2, False, True))
+          (256, 256, 3, 2, False, True),
+          # the short-K expand convs of layer1 / layer2 at the headline's M (510 050 rows: 50 maps of 101 x 101), the stride-2 downsample
+          (64, 256, 1, 1, True, False, 1, 101), (64, 256, 1, 1, False, False, 1, 101), (256, 512, 1, 1, False, False, 2, 101))
 
 
 def timed(fn, reps, n=5):
@@ -49,10 +52,13 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     args = ap.parse_args()
     dev = torch.device("cuda:0")
-    N, HW = 50, 51
-    M = N * HW * HW
-    for (cin, cout, k, dil, has_res, padv) in LAYERS:
-        name = f"{cin}-{cout}-k{k}" + ("-padv" if padv else "")
+    N = 50
+    for layer in LAYERS:
+        cin, cout, k, dil, has_res, padv = layer[:6]
+        stride, HW = layer[6:] if len(layer) > 6 else (1, 51)
+        M = N * HW * HW
+        HO = (HW - 1) // stride + 1 if k == 1 else HW
+        name = f"{cin}-{cout}-k{k}" + ("-padv" if padv else "") + (f"-s{stride}" if stride > 1 else "") + (f"-hw{HW}-res{int(has_res)}" if HW != 51 else "")
         if args.only and args.only != name:
             continue
         g = torch.Generator().manual_seed(cin * 7 + cout * 3 + k)
@@ -63,15 +69,16 @@ def main():
         w = (torch.randn(cout, cin, k, k, generator=g) * (1.0 / (cin * k * k) ** 0.5)).to(dev)
         packed, kpad = ops.pack_conv_weight(w)
         packed = packed.contiguous()
-        prm = ops.ConvParams(packed, None, torch.randn(cout, generator=g).to(dev), cin, cout, k, k, 1, dil if k == 3 else 0, dil, kpad,
+        prm = ops.ConvParams(packed, None, torch.randn(cout, generator=g).to(dev), cin, cout, k, k, stride, dil if k == 3 else 0, dil, kpad,
                              False, True, ops.pack_split3(packed))
-        res = torch.randn(N, HW, HW, cout, generator=g).to(dev) if has_res else None
+        res = torch.randn(N, HO, HO, cout, generator=g).to(dev) if has_res else None
         pad_value = pv if padv else None
-        out = torch.empty(N, HW, HW, cout, device=dev)
-        fl = 2.0 * M * cout * k * k * cin
+        out = torch.empty(N, HO, HO, cout, device=dev)
+        fl = 2.0 * N * HO * HO * cout * k * k * cin
         ref = ops.conv2d(x, prm, residual=res, pad_value=pad_value, tile=43).clone()
         cells, hashes = [], [f"43={digest(ref)}"]
-        for tile in UNSPLIT + SPLIT:
+        panel = PANEL if k == 1 and kpad <= 256 and not padv else ()
+        for tile in UNSPLIT + panel + SPLIT:
             if cout % ops._tile_bn(tile):
                 continue
             run = lambda: ops.conv2d(x, prm, residual=res, pad_value=pad_value, out=out, tile=tile)
@@ -80,9 +87,9 @@ def main():
             if tile in SPLIT:
                 hashes.append(f"{tile}=" + ("43" if same else digest(out)))
             us = timed(run, args.reps)
-            mark = "" if same else (" !" if tile in UNSPLIT else " ~")
+            mark = "" if same else (" ~" if tile in SPLIT else " !")
             cells.append(f"{tile}: {us:7.1f}us {fl / us / 1e6:5.1f}TF{mark}")
-            if tile in UNSPLIT and not same:
+            if tile not in SPLIT and not same:
                 hashes.append(f"{tile}=MISMATCH:{digest(out)}")
         print(f"{name:>16} k{k} d{dil} res{int(has_res)} | " + " | ".join(cells), flush=True)
         print(f"{'':>16} hash " + " ".join(hashes), flush=True)
