@@ -353,6 +353,107 @@ def test_sgd_clip_step_matches_torch(hip_lib, dev):
     assert torch.allclose(pa.cpu(), pb.cpu(), rtol=1e-6, atol=1e-7)
 
 
+# ---------------------------------------------------------------------------------------------
+# prototype-head backward (csrc/head_bwd.hip): the sequence every head test performs -- the forward the trainers run, the
+# kernel's own winning prototypes, and torch autograd through tests/util.py::head_loss with those winners replayed
+# ---------------------------------------------------------------------------------------------
+def _head_inputs(B, S, p, c, h, w, H, W, Ho, Wo):
+    """-> features [B*S + B, h, w, c] (supports first), support masks [B, S, 2, H, W], ctr [c, 2p] | None, target [B, Ho, Wo]."""
+    feat = _rand(B * S + B, h, w, c, seed=1) * 2
+    m = (_rand(B, S, 1, H, W, seed=3) > 0.1).float()
+    mask = torch.cat((m, 1 - m), dim=2)
+    ctr = _rand(c, 2 * p, seed=4, lo=0, hi=1) if p > 0 else None
+    tgt = (_rand(B, Ho, Wo, seed=5) > 0.2).long()
+    tgt[0, :3] = 255
+    return feat, mask, ctr, tgt
+
+
+def _head_forward(dev, fd, mask, ctr, tgt, B, S, p, full_res=False, weight=None):
+    """The forward ahead of the head backward, on the device: prototypes (``mpm_protos`` or ``masked_avg_pool``), cosine map
+    and, with a target, the loss statistics.  ``fd`` is the device feature tensor or a channel slice of a wider one."""
+    from types import SimpleNamespace
+    from pemp_amd import ops
+    h, w, c = fd.shape[1:]
+    ws = {}
+    sup, qry = fd[:B * S], fd[B * S:]
+    md = mask.reshape(B * S, 2, *mask.shape[-2:]).to(dev)
+    cd = ctr.detach().to(dev) if p > 0 else None
+    if p > 0:
+        pro = ops.mpm_protos(sup, md, cd, B, S, p, ws_cache=ws)
+        key = ("mpm", B, S, h, w, c, p)
+    else:
+        pro = ops.masked_avg_pool(sup, md, B, S, full_res=full_res, ws_cache=ws)
+        key = ("map", B, S, h, w, c)
+    pred = ops.cosine_proto_max(qry, pro, 20.0)
+    td = stats = None
+    if tgt is not None:
+        td = tgt.to(dev)
+        _, stats, _ = ops.eval_tail(pred, td, ws_cache=ws, weight=weight)
+    return SimpleNamespace(sup=sup, qry=qry, md=md, cd=cd, td=td, pro=pro, pred=pred, stats=stats, ws=ws, fwd_ws=ws[key],
+                           weight=weight, full_res=full_res)
+
+
+def _head_backward(fw, B, S, p, dlogits=None, dfeat=None):
+    """``head_bwd`` (mean / weighted CE of the forward's target) or, with ``dlogits``, ``head_bwd_dlogits`` -> (dfeat, dctr)."""
+    from pemp_amd import train_ops as T
+    if dfeat is None:
+        dfeat = torch.empty((B * S + B, *fw.sup.shape[1:]), device=fw.sup.device)
+    if dlogits is None:
+        dctr = T.head_bwd(fw.sup, fw.qry, fw.md, fw.cd, fw.fwd_ws, fw.pro, fw.pred, fw.td, fw.stats, dfeat, B, S, p, 20.0,
+                          ws_cache=fw.ws, weight=fw.weight, map_full_res=fw.full_res)
+    else:
+        dctr = T.head_bwd_dlogits(fw.sup, fw.qry, fw.md, fw.cd, fw.fwd_ws, fw.pro, dlogits, dfeat, B, S, p, 20.0,
+                                  ws_cache=fw.ws, map_full_res=fw.full_res)
+    return dfeat, dctr
+
+
+def _head_winners(fw, B, S, p):
+    """The prototype each (query pixel, class) gradient was routed to by the last backward through ``fw.ws`` (the tail of
+    its workspace), as ``head_loss(win=)`` takes it; None for plain MAP."""
+    if p == 0:
+        return None
+    from pemp_amd import _lib
+    h, w, c = fw.sup.shape[1:]
+    n = h * w
+    nbytes = _lib.load().pemp_head_bwd_workspace_bytes(B, S, n, c, p)
+    wk = fw.ws[("head_bwd", B, S, h, w, c, p)][nbytes - B * 2 * n * 4:nbytes].view(torch.int32).view(B, 2, h, w).cpu().long()
+    return torch.stack((wk[:, 1] - p, wk[:, 0]), dim=1)
+
+
+def _head_autograd(feat, mask, ctr, tgt, B, S, p, out_hw, dtype, win=None, weight=None, full_res=False, cot=None):
+    """torch autograd through ``head_loss`` on the CPU in ``dtype`` -> (loss, gradients of the loss, gradients of
+    ``(logits * cot).sum()`` or None); each gradient list is [dfeat] (+ [dctr] when p > 0)."""
+    from tests.util import head_loss
+    f = feat.detach().to(dtype).requires_grad_()
+    cc = ctr.detach().to(dtype).requires_grad_() if p > 0 else None
+    leaves = [f] + ([cc] if p > 0 else [])
+    loss, logits = head_loss(f, mask.to(dtype), tgt if tgt is not None else torch.zeros(B, *out_hw, dtype=torch.int64), cc, B, S, 1,
+                             p, 20.0, tuple(out_hw), weight=None if weight is None else weight.to(dtype), win=win, full_res=full_res)
+    g_cot = torch.autograd.grad((logits * cot.to(dtype)).sum(), leaves, retain_graph=tgt is not None) if cot is not None else None
+    g_loss = torch.autograd.grad(loss, leaves) if tgt is not None else None
+    return loss.detach(), g_loss, g_cot
+
+
+def _rel(a, b):
+    """Relative L2 error of ``a`` against the float64 ``b``; where ``b`` is exactly zero (the centres' gradient of a group of
+    one, whose softmax is the constant 1) ``a`` has to be exactly zero as well."""
+    d, nb = (a.double() - b).norm().item(), b.norm().item()
+    return d / nb if nb > 0 else (0.0 if d == 0 else float("inf"))
+
+
+HEAD_F64_BOUND = 1e-5     # relative L2 of the head backward against float64 autograd with the kernel's winners replayed
+
+
+def _head_check(what, got, g32, g64, bound=HEAD_F64_BOUND):
+    """Relative L2 error per output tensor (dfeat, and dctr when there is one) of the kernels and of torch float32, both against
+    float64; prints both, asserts the kernels'."""
+    e = [(_rel(g.cpu(), r), _rel(t, r)) for g, t, r in zip(got, g32, g64)]
+    print(f"{what}: relative L2 error vs float64  " +
+          "   ".join(f"{n} hip {a:.2e} torch-fp32 {b:.2e}" for n, (a, b) in zip(("dfeat", "dctr"), e)))
+    assert all(a < bound for a, _ in e), (what, e)
+    return e
+
+
 @pytest.mark.parametrize("B,S,p,c,h,w,H,W,Ho,Wo", [(2, 2, 3, 512, 9, 11, 70, 85, 50, 61), (1, 1, 2, 256, 7, 7, 50, 50, 33, 40),
                                                    (2, 1, 0, 512, 6, 5, 41, 37, 41, 37), (1, 5, 3, 128, 5, 6, 40, 47, 40, 47),
                                                    (2, 1, 5, 512, 7, 6, 41, 37, 41, 37), (1, 2, 8, 256, 5, 6, 40, 47, 33, 40)])   # protos 5..8: MAXJ = 16
@@ -360,57 +461,242 @@ def test_head_backward_matches_autograd(hip_lib, dev, B, S, p, c, h, w, H, W, Ho
     """pemp_head_bwd_f32 vs torch autograd through the torch restatement of the head (CPU): against its float32 evaluation at the
     tolerance two float32 evaluations of this head can be held to (2e-4 / 5e-4 of the maximum), and against its float64
     evaluation with the kernel's own winning prototypes replayed at 1e-5 in L2."""
-    from pemp_amd import ops, train_ops as T
-    from tests.util import head_loss
-    feat = (_rand(B * S + B, h, w, c, seed=1) * 2).requires_grad_()
-    m = (_rand(B, S, 1, H, W, seed=3) > 0.1).float()
-    mask = torch.cat((m, 1 - m), dim=2)
-    ctr = _rand(c, 2 * p, seed=4, lo=0, hi=1).requires_grad_() if p > 0 else None
-    tgt = (_rand(B, Ho, Wo, seed=5) > 0.2).long()
-    tgt[0, :3] = 255
-    loss, _ = head_loss(feat, mask, tgt, ctr, B, S, 1, p, 20.0, (Ho, Wo))
-    grads = torch.autograd.grad(loss, [feat] + ([ctr] if p > 0 else []))
-    fd, md, td = feat.detach().to(dev), mask.reshape(B * S, 2, H, W).to(dev), tgt.to(dev)
-    ws = {}
-    sup, qry = fd[:B * S], fd[B * S:]
-    if p > 0:
-        pro = ops.mpm_protos(sup, md, ctr.detach().to(dev), B, S, p, ws_cache=ws)
-        key = ("mpm", B, S, h, w, c, p)
-    else:
-        pro = ops.masked_avg_pool(sup, md, B, S, full_res=False, ws_cache=ws)
-        key = ("map", B, S, h, w, c)
-    pred = ops.cosine_proto_max(qry, pro, 20.0)
-    _, stats, _ = ops.eval_tail(pred, td, ws_cache=ws)
-    got_loss = (stats[:, 0].sum() / stats[:, 1].sum()).item()
+    feat, mask, ctr, tgt = _head_inputs(B, S, p, c, h, w, H, W, Ho, Wo)
+    loss, grads, _ = _head_autograd(feat, mask, ctr, tgt, B, S, p, (Ho, Wo), torch.float32)
+    fw = _head_forward(dev, feat.to(dev), mask, ctr, tgt, B, S, p)
+    got_loss = (fw.stats[:, 0].sum() / fw.stats[:, 1].sum()).item()
     assert abs(got_loss - loss.item()) < 1e-5
-    dfeat = torch.empty_like(fd)
-    dctr = T.head_bwd(sup, qry, md, ctr.detach().to(dev) if p > 0 else None, ws[key], pro, pred, td, stats, dfeat, B, S, p,
-                      20.0, ws_cache=ws)
+    dfeat, dctr = _head_backward(fw, B, S, p)
     scale = grads[0].abs().max().item()
     assert (dfeat.cpu() - grads[0]).abs().max().item() < 2e-4 * scale + 1e-9, (dfeat.cpu() - grads[0]).abs().max().item() / scale
     if p > 0:
         cs = grads[1].abs().max().item()
         assert (dctr.cpu() - grads[1]).abs().max().item() < 5e-4 * cs + 1e-9, (dctr.cpu() - grads[1]).abs().max().item() / cs
     # the same head in float64 with the winners the kernel itself took (frozen decision): rounding only
-    win = None
-    if p > 0:
-        from pemp_amd import _lib
-        n = h * w
-        nbytes = _lib.load().pemp_head_bwd_workspace_bytes(B, S, n, c, p)
-        wk = ws[("head_bwd", B, S, h, w, c, p)][nbytes - B * 2 * n * 4:nbytes].view(torch.int32).view(B, 2, h, w).cpu().long()
-        win = torch.stack((wk[:, 1] - p, wk[:, 0]), dim=1)
-    f64 = feat.detach().double().requires_grad_()
-    c64 = ctr.detach().double().requires_grad_() if p > 0 else None
-    l64, _ = head_loss(f64, mask.double(), tgt, c64, B, S, 1, p, 20.0, (Ho, Wo), win=win)
-    g64 = torch.autograd.grad(l64, [f64] + ([c64] if p > 0 else []))
-    rel = lambda a, b: ((a.double() - b).norm() / b.norm()).item()
-    e = [rel(dfeat.cpu(), g64[0]), rel(grads[0], g64[0])] + ([rel(dctr.cpu(), g64[1]), rel(grads[1], g64[1])] if p > 0 else [])
+    l64, g64, _ = _head_autograd(feat, mask, ctr, tgt, B, S, p, (Ho, Wo), torch.float64, win=_head_winners(fw, B, S, p))
+    e = [_rel(dfeat.cpu(), g64[0]), _rel(grads[0], g64[0])] + ([_rel(dctr.cpu(), g64[1]), _rel(grads[1], g64[1])] if p > 0 else [])
     print(f"head backward B{B} S{S} p{p} c{c}: relative L2 error vs float64  dfeat hip {e[0]:.2e} torch-fp32 {e[1]:.2e}"
           + (f"   dctr hip {e[2]:.2e} torch-fp32 {e[3]:.2e}" if p > 0 else ""))
     assert abs(got_loss - l64.item()) < 2e-6
     # measured 3e-7 .. 2e-6 (torch float32 on the reference's formulation: 7e-6 .. 3.4e-5 -- the rounding of its squared
     # distances, which the kernels' shift-invariant logits do not have, csrc/head_common.h)
     assert max(e[0::2]) < 1e-5, e
+
+
+def _head_vs_float64(what, dev, feat, mask, ctr, tgt, B, S, p, out_hw, weight=False, full_res=False, cot=None):
+    """One head problem through the kernels and through float64 / float32 autograd with the kernels' winners: the CE entry
+    when ``tgt`` is given, the ``dlogits`` entry when ``cot`` is, both against ``HEAD_F64_BOUND``.  -> (forward, results)."""
+    from pemp_amd import ops
+    wmap = ops.cedt_weight(tgt.to(dev), 5.0) if weight else None
+    fw = _head_forward(dev, feat.to(dev), mask, ctr, tgt, B, S, p, full_res=full_res, weight=wmap)
+    wcpu = wmap.cpu() if weight else None
+    out = {}
+    if tgt is not None:
+        out["ce"] = _head_backward(fw, B, S, p)
+    win = _head_winners(fw, B, S, p) if tgt is not None else None
+    if cot is not None:
+        out["dlogits"] = _head_backward(fw, B, S, p, dlogits=cot.to(dev))
+        wcot = _head_winners(fw, B, S, p)
+        assert win is None or torch.equal(win, wcot)         # the winners do not depend on the logit gradient
+        win = wcot
+    args = (feat, mask, ctr, tgt, B, S, p, out_hw)
+    l64, g64, c64 = _head_autograd(*args, torch.float64, win=win, weight=wcpu, full_res=full_res, cot=cot)
+    l32, g32, c32 = _head_autograd(*args, torch.float32, win=win, weight=wcpu, full_res=full_res, cot=cot)
+    if tgt is not None:
+        got_loss = (fw.stats[:, 0].sum() / fw.stats[:, 1].sum()).item()
+        assert abs(got_loss - l64.item()) < 2e-6, (got_loss, l64.item())
+        _head_check(what + " CE", out["ce"], g32, g64)
+    if cot is not None:
+        _head_check(what + " dlogits", out["dlogits"], c32, c64)
+    return fw, out
+
+
+HEAD_DLOGITS_CASES = [  # B, S, p, c, h, w, H, W, Ho, Wo
+    (2, 2, 3, 512, 9, 11, 70, 85, 50, 61),      # MAXJ = 8
+    (1, 1, 5, 256, 7, 6, 41, 37, 33, 40),       # MAXJ = 16
+    (2, 1, 0, 128, 6, 5, 41, 37, 41, 37),       # plain MAP: the bilinear adjoint alone routes G
+    (1, 2, 0, 128, 13, 13, 50, 50, 7, 5),       # output smaller than the map (sh = 2, sw = 3)
+    (1, 1, 2, 128, 13, 13, 50, 50, 7, 5),
+    (1, 1, 0, 128, 11, 13, 50, 50, 8, 6),       # ... at non-integer scales (10/7, 12/5)
+    (2, 1, 0, 128, 7, 9, 50, 47, 7, 9),         # output equal to the map
+    (1, 1, 2, 128, 7, 9, 50, 47, 7, 9),
+    (1, 1, 0, 128, 5, 6, 41, 47, 1, 9),         # one output row / one output column (scale 0)
+    (1, 1, 0, 128, 5, 6, 41, 47, 9, 1),
+    (1, 1, 2, 128, 5, 6, 41, 47, 1, 1),
+    (2, 2, 0, 128, 1, 1, 20, 20, 9, 11),        # one-pixel map (at p = 2 float32 torch's dctr is 2.1e-2 off float64, the kernel's 7.3e-3)
+    (1, 2, 0, 128, 1, 7, 20, 20, 9, 11),        # one-row map
+    (1, 2, 2, 260, 6, 7, 31, 47, 20, 25),       # c = 260: one lane of the second float4 group works
+    (1, 1, 3, 320, 6, 7, 31, 47, 20, 25),       # c = 320: sixteen lanes
+    (1, 2, 0, 260, 6, 7, 31, 47, 20, 25),
+    (2, 1, 1, 64, 5, 7, 41, 33, 20, 25),        # c = 64: a quarter of the first group
+    (3, 5, 3, 128, 5, 6, 41, 47, 20, 25),       # B = 3, S = 5
+]
+
+
+@pytest.mark.parametrize("B,S,p,c,h,w,H,W,Ho,Wo", HEAD_DLOGITS_CASES)
+def test_head_backward_for_a_given_logit_gradient_matches_float64(hip_lib, dev, B, S, p, c, h, w, H, W, Ho, Wo):
+    """pemp_head_bwd_dlogits_f32 (what the autograd bridge calls; the only user of ``upsample_bwd_kernel<false>``) for a random
+    cotangent G [B,2,Ho,Wo]: the gradient of ``(logits * G).sum()`` by float64 autograd with the kernel's winners replayed, 1e-5
+    relative L2 per output tensor.  The backward is linear in G and G enters through the bilinear adjoint alone, so the p = 0
+    rows test that kernel's window arithmetic: output larger, smaller (integer and fractional scale), equal, one row / column,
+    and a one-pixel / one-row map.
+    measured: p = 0 rows 1.0e-7 .. 4.2e-7 (torch float32 1.1e-7 .. 4.7e-7); p > 1 rows dfeat 6.6e-7 .. 1.6e-6, dctr 3.5e-7 .. 1.1e-6
+    (torch float32 4.8e-6 .. 4.1e-5); p = 1, c = 64: dfeat 1.4e-7 (torch float32 1.9e-7), dctr exactly zero in all three."""
+    feat, mask, ctr, _ = _head_inputs(B, S, p, c, h, w, H, W, Ho, Wo)
+    G = _rand(B, 2, Ho, Wo, seed=7)
+    _head_vs_float64(f"head dlogits B{B} S{S} p{p} c{c} {h}x{w}->{Ho}x{Wo}", dev, feat, mask, ctr, None, B, S, p, (Ho, Wo), cot=G)
+
+
+def _blob_target(B, Ho, Wo):
+    """A disc of foreground per episode (so that the CEDT weight map has a boundary to measure from) with a few ignored rows."""
+    yy, xx = torch.meshgrid(torch.arange(Ho), torch.arange(Wo), indexing="ij")
+    tgt = torch.stack([((yy - Ho * (0.4 + 0.1 * b)) ** 2 + (xx - Wo * 0.5) ** 2 < (min(Ho, Wo) * (0.25 + 0.05 * b)) ** 2).long()
+                       for b in range(B)])
+    tgt[0, :3] = 255
+    return tgt
+
+
+@pytest.mark.parametrize("B,S,c,h,w,H,W,weight", [(2, 2, 256, 7, 9, 50, 65, False),
+                                                  (1, 5, 512, 13, 13, 97, 97, False),     # more shots and channels
+                                                  (2, 1, 128, 7, 9, 7, 9, False),         # masks at feature resolution: no up-sampling
+                                                  (2, 2, 256, 7, 9, 50, 65, True)])       # CEDT weight map
+def test_full_resolution_map_head_backward_matches_float64(hip_lib, dev, B, S, c, h, w, H, W, weight):
+    """The Baseline's head (``map_full_res``: pooling over bilinearly up-sampled support features under the full-resolution
+    masks, ``den_override`` / ``L.A`` / ``L.msum``), through ``head_bwd`` and ``head_bwd_dlogits``, against float64 autograd
+    of ``head_loss(full_res=True)`` at 1e-5 relative L2.
+    measured: CE entry 2.1e-7 (no up-sampling) and 1.3e-6 .. 1.5e-6 (torch float32 1.5e-7, 1.0e-6 .. 1.2e-6); dlogits entry
+    1.2e-7 .. 1.9e-7 (torch float32 1.2e-7 .. 4.2e-7)."""
+    feat, mask, _, tgt = _head_inputs(B, S, 0, c, h, w, H, W, H, W)
+    if weight:
+        tgt = _blob_target(B, H, W)
+    G = _rand(B, 2, H, W, seed=7)
+    _head_vs_float64(f"full-res MAP B{B} S{S} c{c} {h}x{w}->{H}x{W}" + (" cedt" if weight else ""), dev, feat, mask, None, tgt, B, S,
+                     0, (H, W), weight=weight, full_res=True, cot=G)
+
+
+@pytest.mark.parametrize("B,S,p,c,h,w,H,W,Ho,Wo", [(2, 1, 5, 256, 7, 6, 41, 37, 41, 37),      # MAXJ = 16
+                                                   (2, 2, 0, 128, 6, 5, 41, 37, 33, 40)])     # plain MAP
+def test_weighted_head_backward_matches_float64(hip_lib, dev, B, S, p, c, h, w, H, W, Ho, Wo):
+    """``head_bwd(weight=)`` (CELossDT: sum(CE * w) / sum(w)) on the low-resolution path, beside the one shape of
+    test_cedt_gpu.py, against float64 autograd at 1e-5 relative L2.
+    measured: p = 5 dfeat 1.2e-6, dctr 9.0e-7 (torch float32 2.0e-5, 2.6e-5); p = 0 dfeat 1.7e-7 (torch float32 2.2e-7)."""
+    feat, mask, ctr, _ = _head_inputs(B, S, p, c, h, w, H, W, Ho, Wo)
+    _head_vs_float64(f"weighted head B{B} S{S} p{p} c{c}", dev, feat, mask, ctr, _blob_target(B, Ho, Wo), B, S, p, (Ho, Wo), weight=True)
+
+
+@pytest.mark.parametrize("p", [3, 0])
+def test_head_backward_on_channel_slices_of_wider_buffers(hip_lib, dev, p):
+    """Features that are 128 channels starting at channel 32 of a 192-channel buffer (ldf = 192), gradients written into 128
+    channels starting at channel 64 of a 256-channel buffer (ldd = 256): bit-identical to the same calls on contiguous copies,
+    through ``head_bwd`` and ``head_bwd_dlogits``, and nothing outside the slice is written."""
+    B, S, c, h, w, H, W, Ho, Wo = 2, 2, 128, 6, 7, 41, 47, 33, 40
+    feat, mask, ctr, tgt = _head_inputs(B, S, p, c, h, w, H, W, Ho, Wo)
+    G = _rand(B, 2, Ho, Wo, seed=7).to(dev)
+    wide = _rand(B * S + B, h, w, 192, seed=8).to(dev)
+    wide[..., 32:160] = feat.to(dev)
+    sentinel = -7.5
+    fw_c = _head_forward(dev, feat.to(dev), mask, ctr, tgt, B, S, p)
+    fw_s = _head_forward(dev, wide[..., 32:160], mask, ctr, tgt, B, S, p)
+    assert not fw_s.sup.is_contiguous() and torch.equal(fw_s.pro, fw_c.pro) and torch.equal(fw_s.pred, fw_c.pred)
+    assert torch.equal(fw_s.stats, fw_c.stats)                                      # the loss
+    for dl in (None, G):
+        ref, ref_ctr = _head_backward(fw_c, B, S, p, dlogits=dl)
+        gbuf = torch.full((B * S + B, h, w, 256), sentinel, device=dev)
+        _, got_ctr = _head_backward(fw_s, B, S, p, dlogits=dl, dfeat=gbuf[..., 64:192])
+        assert ref.abs().max().item() > 0
+        assert torch.equal(gbuf[..., 64:192], ref)
+        assert (gbuf[..., :64] == sentinel).all() and (gbuf[..., 192:] == sentinel).all()
+        if p > 0:
+            assert torch.equal(got_ctr, ref_ctr)
+
+
+@pytest.mark.parametrize("p", [3, 0])
+def test_head_backward_with_every_target_ignored(hip_lib, dev, p):
+    """Targets that are all 255.  In the whole batch: no valid pixel, gradients exactly zero (``nv == 0 -> inv = 0``, never
+    0 * inf).  In one episode of two: that episode's rows are exactly zero and the rest matches float64 autograd, whose
+    ``F.cross_entropy(ignore_index=255)`` normalises by the batch's valid count as well.
+    measured: p = 3 dfeat 1.5e-6, dctr 9.6e-7 (torch float32 5.5e-6, 6.7e-6); p = 0 dfeat 2.1e-7 (torch float32 2.9e-7)."""
+    B, S, c, h, w, H, W, Ho, Wo = 2, 1, 128, 7, 7, 50, 50, 33, 40
+    feat, mask, ctr, tgt = _head_inputs(B, S, p, c, h, w, H, W, Ho, Wo)
+    fw = _head_forward(dev, feat.to(dev), mask, ctr, torch.full_like(tgt, 255), B, S, p)
+    assert fw.stats[:, 1].sum().item() == 0                                         # n_valid
+    dfeat, dctr = _head_backward(fw, B, S, p, dfeat=torch.full((B * S + B, h, w, c), 3.0, device=dev))
+    assert (dfeat == 0).all() and (p == 0 or (dctr == 0).all())
+    tgt[1] = 255
+    _, out = _head_vs_float64(f"head, episode 1 of 2 ignored, p{p}", dev, feat, mask, ctr, tgt, B, S, p, (Ho, Wo))
+    dfeat = out["ce"][0]
+    assert (dfeat[B * S + 1] == 0).all() and (dfeat[1 * S:2 * S] == 0).all()        # its query rows, and its supports'
+    assert dfeat[B * S].abs().max().item() > 0
+
+
+@pytest.mark.parametrize("p", [3, 0])
+@pytest.mark.parametrize("S", [2, 1])
+def test_head_backward_with_an_empty_support_foreground(hip_lib, dev, S, p):
+    """A support shot whose foreground mask is empty.  With S = 2 the episode's prototype is half the other shot's; with S = 1 it
+    is zero: its norm is clamped to 1e-8, 1 / nrm = 1e8 flows into the prototype gradient, the pooling denominator is eps
+    alone (gradients of order 1e13 per unit of assignment weight) -- and every one of them meets an assignment weight that is
+    exactly zero.  Finite, and equal to float64 autograd (F.cosine_similarity clamps at the same 1e-8) at the 1e-5 of every
+    other case.  Exactly zero is asserted at ``dead``: the 2 * w pixels of rows 0..1 of the emptied shot, whose nearest-sampled
+    mask is zero in both classes, so that the gradient of either prototype reaches them with weight zero; the shot's other
+    pixels carry background weight and a nonzero gradient, and their zero foreground weight is held by the 1e-5 bound alone.
+    measured: p = 3 dfeat 1.0e-6, dctr 5.6e-7 .. 6.9e-7 (torch float32 5.1e-6 .. 9.4e-6); p = 0 dfeat 2.4e-7 .. 2.8e-7 (torch
+    float32 2.7e-7 .. 3.1e-7): float32 torch is as usable here as anywhere, so the bound is not widened."""
+    B, c, h, w, H, W, Ho, Wo = 2, 128, 7, 7, 50, 50, 33, 40
+    feat, mask, ctr, tgt = _head_inputs(B, S, p, c, h, w, H, W, Ho, Wo)
+    mask[0, S - 1, 0] = 0                       # episode 0, last shot: no foreground, all background
+    mask[0, S - 1, 1] = 1
+    mask[0, S - 1, 1, :14] = 0                  # ... but for rows 0..1 of its 7 x 7 map, which are in neither class
+    _, out = _head_vs_float64(f"head, empty foreground S{S} p{p}", dev, feat, mask, ctr, tgt, B, S, p, (Ho, Wo))
+    dfeat, dctr = out["ce"]
+    assert torch.isfinite(dfeat).all() and (p == 0 or torch.isfinite(dctr).all())
+    low = F.interpolate(mask.reshape(B * S, 2, H, W), (h, w), mode="nearest")
+    dead = low.sum(dim=1) == 0                                                      # [B*S, h, w]
+    assert dead[S - 1, :2].all() and int(dead.sum()) == 2 * w
+    assert (dfeat[:B * S].cpu()[dead] == 0).all()
+    assert dfeat[S - 1, 2:].abs().max().item() > 0                                  # the background still pools there
+
+
+def test_head_backward_refuses_what_it_cannot_run(hip_lib, dev):
+    """Shapes outside the kernels' contract are refused by the entry points before anything is launched (the gradient buffer
+    keeps its fill), a malformed ``dlogits`` by the wrapper."""
+    from pemp_amd import _lib, train_ops as T
+    B, S, h, w, H, W, Ho, Wo = 1, 1, 5, 6, 40, 47, 20, 25
+    lib = _lib.load()
+
+    def refused(p, c, match, map_full_res=False):
+        # operands of the sizes the call would need, so that a refusal that failed to happen stays inside its buffers
+        fd = torch.zeros(B * S + B, h, w, c, device=dev)
+        md = torch.ones(B * S, 2, H, W, device=dev)
+        cd = torch.zeros(c, 2 * p, device=dev) if p > 0 else None
+        J = 2 * p if p > 0 else 2
+        fwd_ws = torch.zeros(lib.pemp_mpm_workspace_bytes(B, S, h * w, c, max(p, 1)), dtype=torch.uint8, device=dev)
+        pro, pred = torch.zeros(B, J, c, device=dev), torch.zeros(B, 2, h, w, device=dev)
+        td = torch.zeros(B, Ho, Wo, dtype=torch.int64, device=dev)
+        stats = torch.ones(B, 8, dtype=torch.float64, device=dev)
+        G = torch.zeros(B, 2, Ho, Wo, device=dev)
+        for dl in (None, G):
+            dfeat = torch.full_like(fd, 3.0)
+            with pytest.raises(_lib.PempHipError, match=match):
+                if dl is None:
+                    T.head_bwd(fd[:B * S], fd[B * S:], md, cd, fwd_ws, pro, pred, td, stats, dfeat, B, S, p, 20.0, map_full_res=map_full_res)
+                else:
+                    T.head_bwd_dlogits(fd[:B * S], fd[B * S:], md, cd, fwd_ws, pro, dl, dfeat, B, S, p, 20.0, map_full_res=map_full_res)
+            assert (dfeat == 3.0).all()
+
+    refused(3, 128, "map_full_res is the Baseline's plain-MAP head", map_full_res=True)
+    refused(3, 514, "c=514 must be a multiple of 4 and <= 512")
+    refused(3, 516, "c=516 must be a multiple of 4 and <= 512")
+    refused(0, 516, "c=516 must be a multiple of 4 and <= 512")
+    refused(9, 128, "bad dims")                                                    # 2p = 18 > 16
+    fd = torch.zeros(B * S + B, h, w, 128, device=dev)
+    args = (fd[:B * S], fd[B * S:], torch.ones(B * S, 2, H, W, device=dev), None, torch.zeros(1 << 16, dtype=torch.uint8, device=dev),
+            torch.zeros(B, 2, 128, device=dev))
+    dfeat = torch.full_like(fd, 3.0)
+    for bad in (torch.zeros(B, 2, Ho, 2 * Wo, device=dev)[..., ::2], torch.zeros(B, 1, Ho, Wo, device=dev),
+                torch.zeros(B, 2, Ho, Wo, device=dev, dtype=torch.float64)):
+        with pytest.raises(ValueError, match="dlogits must be contiguous fp32"):
+            T.head_bwd_dlogits(*args, bad, dfeat, B, S, 0, 20.0)
+    assert (dfeat == 3.0).all()
 
 
 def test_cm_linear_bias_and_backward_match_autograd(hip_lib, dev):

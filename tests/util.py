@@ -67,9 +67,14 @@ def counts(pred, ref):
 # prototype head on torch ops (GPU), differentiated by autograd -- reference networks/pemp_stage1.py:142-163,195-261
 # (cross-check of the HIP head kernels; test infrastructure)
 # ---------------------------------------------------------------------------------------------
-def head_loss(feat_nhwc, sup_mask, qry_mask, ctr, B, S, Q, protos, dist_scalar, out_shape, weight=None, win=None):
+def head_loss(feat_nhwc, sup_mask, qry_mask, ctr, B, S, Q, protos, dist_scalar, out_shape, weight=None, win=None,
+              full_res=False):
     """``win`` (int64 [B*Q,2,h,w], channel 0 = background): take these prototypes instead of the group maxima (a frozen
-    decision, see test_grad_frozen_gpu.py)."""
+    decision, see test_grad_frozen_gpu.py).  ``full_res`` (plain MAP, ``protos == 0``, only): the Baseline's prototypes --
+    the support features are up-sampled bilinearly to the masks' resolution and pooled under the full-resolution masks
+    (reference networks/baseline.py:100-110)."""
+    if full_res and protos > 0:
+        raise ValueError("head_loss: full_res is the Baseline's plain-MAP head (protos == 0)")
     n, h, w, c = feat_nhwc.shape
     f = feat_nhwc.permute(0, 3, 1, 2)
     sup = f[:B * S].reshape(B, S, c, h * w).reshape(B * S, c, h * w)
@@ -90,8 +95,14 @@ def head_loss(feat_nhwc, sup_mask, qry_mask, ctr, B, S, Q, protos, dist_scalar, 
         st = torch.stack((bgd, fgd), dim=1)
         pred = st.max(dim=2).values if win is None else st.gather(2, win.unsqueeze(2)).squeeze(2)
     else:
-        fgv = (sup * fg).sum(-1) / (fg.sum(-1) + 1e-5)
-        bgv = (sup * bg).sum(-1) / (bg.sum(-1) + 1e-5)
+        if full_res:
+            up = F.interpolate(f[:B * S], (H, W), mode="bilinear", align_corners=True)
+            mk = sup_mask.reshape(B * S, 2, 1, H, W)
+            fgv = (up * mk[:, 0]).sum(dim=(2, 3)) / (mk[:, 0].sum(dim=(2, 3)) + 1e-5)
+            bgv = (up * mk[:, 1]).sum(dim=(2, 3)) / (mk[:, 1].sum(dim=(2, 3)) + 1e-5)
+        else:
+            fgv = (sup * fg).sum(-1) / (fg.sum(-1) + 1e-5)
+            bgv = (sup * bg).sum(-1) / (bg.sum(-1) + 1e-5)
         fgp, bgp = fgv.view(B, S, c).mean(1), bgv.view(B, S, c).mean(1)
         q = qry.view(-1, c, h, w)
         pred = torch.stack((F.cosine_similarity(q, bgp[..., None, None], dim=1) * dist_scalar,
