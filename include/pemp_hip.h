@@ -596,6 +596,30 @@ int pemp_canet_block_input_f32(const float* x, int ldx, const float* hist, const
 int pemp_canet_history_update_f32(const float* logits, float* table, const int* slot, int nslots, float* out, int B,
                                   int HW, void* stream);
 
+/* ---- RPMMs inference (networks/rpmms.py) -----------------------------------------------------------------------------
+ * The EM of the prototype mixture models (PMMs.EM :65-86) for the mixtures K = 1 | 3 | 6 side by side (10 columns), foreground
+ * (side 0, pixel weight m) and background (side 1, weight 1 - m): feat NHWC [B][h][w][C] (ldf), mask [B][h][w], mu0 [10][C]
+ * (row 0: K = 1, rows 1..3: K = 3, rows 4..9: K = 6; unit rows) -> mu_out [B][2][10][C].  Per iteration, with x_p = wgt_p f_p:
+ * s_pj = softmax_j(20 <x_p, mu_j>) inside each mixture, mu'_j = sum_p x_p s_pj / (1e-6 + sum_p s_pj), mu_j = mu'_j / (1e-6 +
+ * |mu'_j|).  One launch per iteration over G = min(16, ceil(h w / 64)) pixel slices per (image, side) plus one final reduction,
+ * all enqueued here; the slices' partial sums ping-pong through `work`, 2 * B * 2 * G * (10 * C + 16) floats of the caller.
+ * C == 256.  Fixed summation orders; an image's result does not depend on B.                                              */
+int pemp_rpmms_em_f32(const float* feat, int ldf, const float* mask, const float* mu0, float* work, float* mu_out, int B,
+                      int h, int w, int C, int iters, void* stream);
+/* The probability maps (rpmms.py:119-139): per query pixel and mixture the softmax over the 2K dots <q, [mu_f | mu_b]>, P_f =
+ * sum of the first K, P_b = sum of the last K.  qry NHWC [B][HW][C] (ldq), mu [B][2][10][C] -> mixture g (0..2):
+ * out[g * gstride + (b * HW + p) * ldo + C] = P_b, [... + C + 1] = P_f.  C == 256.                                        */
+int pemp_rpmms_prob_map_f32(const float* qry, int ldq, const float* mu, float* out, int ldo, long long gstride, int B, int HW,
+                            int C, void* stream);
+/* The sum over a mixture's prototypes of layer55(cat(query, prototype)) (rpmms.py:237-244; a 3x3, dilation dil, zero padding
+ * dil conv + bias + ReLU) from ONE conv of the query: T[b][i][tap][co] = sum_ci wz[tap][co][ci] mu[b][0][i][ci] (T: [B][10][9][C]
+ * scratch of the caller; wz [9][C][C]), then, for mixture g,
+ * out[g * gstride + (b * h * w + p) * ldo + c] = sum_{i in g, ascending} relu(base[b][p][c] + bias[c] + sum of T[b][i][tap][c]
+ * over the taps whose source pixel lies inside the image, in tap order).  base NHWC (ldb): the conv of the query with the
+ * query half of the weights, no bias, no ReLU.  C == 256.                                                                */
+int pemp_rpmms_proto_sum_f32(const float* wz, const float* mu, const float* base, int ldb, const float* bias, float* T,
+                             float* out, int ldo, long long gstride, int B, int h, int w, int C, int dil, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

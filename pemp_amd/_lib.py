@@ -149,6 +149,10 @@ SYMBOLS = {
     "pemp_canet_zterm_f32": (c_int, [c_fp, c_fp, c_fp, c_fp] + [c_int] * 7 + [c_fp]),
     "pemp_canet_block_input_f32": (c_int, [c_fp, c_int, c_fp, c_fp, c_int, c_fp] + [c_int] * 5 + [c_fp]),
     "pemp_canet_history_update_f32": (c_int, [c_fp, c_fp, c_fp, c_int, c_fp, c_int, c_int, c_fp]),
+    # RPMMs inference
+    "pemp_rpmms_em_f32": (c_int, [c_fp, c_int, c_fp, c_fp, c_fp, c_fp] + [c_int] * 5 + [c_fp]),
+    "pemp_rpmms_prob_map_f32": (c_int, [c_fp, c_int, c_fp, c_fp, c_int, C.c_longlong, c_int, c_int, c_int, c_fp]),
+    "pemp_rpmms_proto_sum_f32": (c_int, [c_fp, c_fp, c_fp, c_int, c_fp, c_fp, c_fp, c_int, C.c_longlong] + [c_int] * 5 + [c_fp]),
 }
 
 ABI_VERSION = 2          # include/pemp_hip.h: PEMP_ABI_VERSION

@@ -1191,3 +1191,88 @@ def canet_history_update(logits, table=None, slot=None, out=None):
     _lib.check(lib.pemp_canet_history_update_f32(_p(logits), _p(table), _p(slot), nslots, _p(out), b, h * w, _stream()),
                "canet_history_update")
     return out if out is not None else table
+
+
+# -- RPMMs inference (csrc/rpmms.hip) -----------------------------------------------------------------------------------------
+RPMMS_COLS = 10                 # the three mixtures K = 1 | 3 | 6 side by side
+RPMMS_GROUPS = ((0, 1), (1, 3), (4, 6))          # (first column, K) of every mixture
+
+
+def rpmms_em_work_floats(B, h, w, C=256):
+    """Size of ``rpmms_em``'s ping-pong workspace (include/pemp_hip.h: 2 halves x B x 2 sides x G slices x (10 C + 16))."""
+    g = min(16, -(-(h * w) // 64))
+    return 2 * B * 2 * g * (RPMMS_COLS * C + 16)
+
+
+def rpmms_em(feat, mask, mu0, out=None, work=None, iters=10):
+    """The PMMs EM (networks/rpmms.py:65-86,101-117) of all three mixtures, foreground and background, in one pass per iteration
+    over the support features: feat NHWC [B,h,w,256], mask contiguous fp32 [B,h,w] (the foreground plane at feature size), mu0
+    contiguous fp32 [10,256] -> mu [B,2,10,256] (side 0: foreground, 1: background)."""
+    lib = _lib.load()
+    _chk_dev(feat, mask, mu0, out, work)
+    ldf = _nhwc(feat, "feat")
+    b, h, w, c = feat.shape
+    if tuple(mask.shape) != (b, h, w) or not mask.is_contiguous() or mask.dtype != torch.float32:
+        raise ValueError(f"rpmms_em: mask must be contiguous fp32 [{b},{h},{w}], got {tuple(mask.shape)}")
+    if tuple(mu0.shape) != (RPMMS_COLS, c) or not mu0.is_contiguous() or mu0.dtype != torch.float32:
+        raise ValueError(f"rpmms_em: mu0 must be contiguous fp32 [{RPMMS_COLS},{c}]")
+    if out is None:
+        out = torch.empty((b, 2, RPMMS_COLS, c), dtype=torch.float32, device=feat.device)
+    if tuple(out.shape) != (b, 2, RPMMS_COLS, c) or not out.is_contiguous() or out.dtype != torch.float32:
+        raise ValueError(f"rpmms_em: out must be contiguous fp32 [{b},2,{RPMMS_COLS},{c}]")
+    need = rpmms_em_work_floats(b, h, w, c)
+    if work is None:
+        work = torch.empty(need, dtype=torch.float32, device=feat.device)
+    if work.numel() < need or not work.is_contiguous() or work.dtype != torch.float32:
+        raise ValueError(f"rpmms_em: work must be a contiguous fp32 buffer of at least {need} elements")
+    _lib.check(lib.pemp_rpmms_em_f32(_p(feat), ldf, _p(mask), _p(mu0), _p(work), _p(out), b, h, w, c, int(iters), _stream()), "rpmms_em")
+    return out
+
+
+def _rpmms_groups_out(who, out, b, h, w, c, need):
+    """``out`` [3,B,h,w,ld]: one NHWC buffer per mixture, ld >= need -> (pixel stride, mixture stride)."""
+    if out.dim() != 5 or tuple(out.shape[:4]) != (3, b, h, w) or out.shape[4] < need or out.dtype != torch.float32:
+        raise ValueError(f"{who}: out must be fp32 [3,{b},{h},{w},>={need}], got {tuple(out.shape)}")
+    st = out.stride()
+    if st[4] != 1 or st[2] != w * st[3] or st[1] != h * w * st[3]:
+        raise ValueError(f"{who}: out must be a channel slice of a dense [3,B,h,w,ld] buffer")
+    return st[3], st[0]
+
+
+def rpmms_prob_map(qry, mu, out):
+    """The probability maps of the three mixtures (rpmms.py:119-139): qry NHWC [B,h,w,256], mu [B,2,10,256] (``rpmms_em``) ->
+    out[g, b, y, x, 256] = P_b, out[g, b, y, x, 257] = P_f; ``out`` [3,B,h,w,ld >= 258], other channels untouched."""
+    lib = _lib.load()
+    _chk_dev(qry, mu, out)
+    ldq = _nhwc(qry, "qry")
+    b, h, w, c = qry.shape
+    if tuple(mu.shape) != (b, 2, RPMMS_COLS, c) or not mu.is_contiguous() or mu.dtype != torch.float32:
+        raise ValueError(f"rpmms_prob_map: mu must be contiguous fp32 [{b},2,{RPMMS_COLS},{c}]")
+    ldo, gstride = _rpmms_groups_out("rpmms_prob_map", out, b, h, w, c, c + 2)
+    _lib.check(lib.pemp_rpmms_prob_map_f32(_p(qry), ldq, _p(mu), _p(out), ldo, gstride, b, h * w, c, _stream()), "rpmms_prob_map")
+    return out
+
+
+def rpmms_proto_sum(wz, mu, base, bias, out, dil=2, taps=None):
+    """Per mixture the sum over its prototypes of layer55(cat(query, prototype)) (rpmms.py:237-244): wz [9,256,256]
+    (``pack_canet_zweights`` of the prototype half of the weights), mu [B,2,10,256], base NHWC [B,h,w,256] (the conv of the
+    query with the query half, no bias, no ReLU), bias [256] -> out[g, b, y, x, :256]; ``out`` [3,B,h,w,ld >= 256].  ``taps``: the
+    [B,10,9,256] intermediate (a scratch buffer)."""
+    lib = _lib.load()
+    _chk_dev(wz, mu, base, bias, out, taps)
+    ldb = _nhwc(base, "base")
+    b, h, w, c = base.shape
+    if tuple(wz.shape) != (9, c, c) or not wz.is_contiguous() or wz.dtype != torch.float32:
+        raise ValueError(f"rpmms_proto_sum: wz must be contiguous fp32 [9,{c},{c}]")
+    if tuple(mu.shape) != (b, 2, RPMMS_COLS, c) or not mu.is_contiguous() or mu.dtype != torch.float32:
+        raise ValueError(f"rpmms_proto_sum: mu must be contiguous fp32 [{b},2,{RPMMS_COLS},{c}]")
+    if tuple(bias.shape) != (c,) or not bias.is_contiguous() or bias.dtype != torch.float32:
+        raise ValueError(f"rpmms_proto_sum: bias must be contiguous fp32 [{c}]")
+    if taps is None:
+        taps = torch.empty((b, RPMMS_COLS, 9, c), dtype=torch.float32, device=base.device)
+    if tuple(taps.shape) != (b, RPMMS_COLS, 9, c) or not taps.is_contiguous() or taps.dtype != torch.float32:
+        raise ValueError(f"rpmms_proto_sum: taps must be contiguous fp32 [{b},{RPMMS_COLS},9,{c}]")
+    ldo, gstride = _rpmms_groups_out("rpmms_proto_sum", out, b, h, w, c, c)
+    _lib.check(lib.pemp_rpmms_proto_sum_f32(_p(wz), _p(mu), _p(base), ldb, _p(bias), _p(taps), _p(out), ldo, gstride, b, h, w, c,
+                                            int(dil), _stream()), "rpmms_proto_sum")
+    return out

@@ -1,0 +1,105 @@
+"""RPMMs inference engine (reference: networks/rpmms.py:213-287): CANet's trunk once and CANet's tail three times, behind the
+prototype mixture models, as one chain of libpemp_hip.so launches on one stream from a static ``Arena`` (hipGraph capture
+works as for the other models).  1-shot, one query (the reference's own limits, rpmms.py:129,266-267).
+
+Layout choices (RPMMs):
+- the trunk writes ``cat(layer2, layer3)`` into one [2B,h,w,1536] buffer (supports first), ``layer5`` runs once over it with its
+  BatchNorm folded;
+- the EM of the three mixtures K = 1 | 3 | 6, foreground and background, is ONE chain of launches over the support features
+  (``ops.rpmms_em``): the ten columns share every read of x; the initial mu is the model's ``pmm_mu0`` buffer;
+- ``layer55(cat(query, vec_i))`` summed over a mixture's prototypes needs ONE conv of the query with the query half of the
+  weights (``base``, shared by the three mixtures); the prototype half is ten 9-tap GEMVs and, per pixel, the taps that fall
+  inside the image (``ops.rpmms_proto_sum``; ``ops.canet_zterm``'s trick with the ReLU inside the sum);
+- the three ``layer56`` inputs are three [B,h,w,288] buffers (256 sums, P_b, P_f, 30 zero channels: the conv engine takes
+  Cin % 32 == 0) behind one another: ``layer56`` is one conv launch over 3B images;
+- the three ``Segmentation`` passes run in order on B images each, the softmax of a pass (``ops.canet_history_update``) being
+  the next one's history channels; the reference's ``interpolate`` of the history (:274) is the identity at feature size;
+- ``layer7`` is the 1280 -> 256 1x1 + ReLU behind the tail-less ASPP: exactly what ``ASPPEngine`` folds as its ``layer6``;
+- ``layer9`` (256 -> 2) is packed with 62 zero output channels, its two live channels copied into NCHW logits.
+"""
+import types
+
+import torch
+
+from . import ops
+from .canet_engine import HIST_CIN, MID, _pack_padded_in, feature_hw
+from .engine import ASPPEngine, ResNetEngine, conv_params, with_split3
+from .ops import ConvParams
+
+PASSES = 3
+
+
+class RPMMsEngine:
+    """The whole eval forward: ``lowres(sup_img, sup_mask, qry_img)`` -> [out0, out1, out2], logits [B,2,h,w] each."""
+
+    def __init__(self, model, arena):
+        self.arena = arena
+        self.model = model
+        self.trunk = ResNetEngine(model.model_res, arena)
+        self.l5 = conv_params(model.layer5[0], model.layer5[1], relu=True)
+        c55 = model.layer55[0]
+        self.l55_q = conv_params(c55, None, relu=False, in_slice=(0, MID))
+        self.l55_q.shift = None                                   # the bias joins the prototype terms inside the ReLU
+        self.b55 = c55.bias.detach().float().contiguous()
+        self.wz = ops.pack_canet_zweights(c55.weight[:, MID:])
+        self.dil55 = c55.dilation[0]
+        self.l56 = _pack_padded_in(model.layer56[0], HIST_CIN, True)
+        self.res = []
+        for k, seq in enumerate((model.residule1, model.residule2, model.residule3)):
+            first = _pack_padded_in(seq[1], HIST_CIN, True) if k == 0 else conv_params(seq[1], None, relu=True)
+            self.res.append((first, conv_params(seq[3], None, relu=False)))
+        prm = types.SimpleNamespace(layer6=model.layer7[0], **{f"aspp_{i}": getattr(model.layer6, f"aspp_{i}") for i in range(5)})
+        self.aspp = ASPPEngine(prm, arena, out_relu=True)
+        l9 = model.layer9
+        w = torch.zeros((64, MID), dtype=torch.float32, device=l9.weight.device)
+        w[:2] = l9.weight.detach().float()[:, :, 0, 0]
+        b = torch.zeros(64, dtype=torch.float32, device=l9.weight.device)
+        b[:2] = l9.bias.detach().float()
+        self.l9 = with_split3(ConvParams(w.contiguous(), None, b.contiguous(), MID, 64, 1, 1, 1, 0, 1, MID, False, False))
+
+    def lowres(self, sup_img, sup_mask, qry_img):
+        """sup_img [B,1,3,H,W], sup_mask [B,1,2,H,W] (plane 0: foreground), qry_img [B,1,3,H,W] on the device."""
+        a = self.arena
+        B, S, ch, H, W = sup_img.shape
+        n = 2 * B
+        x4 = a.get("x4", (n, H, W, 4))
+        ops.pack_input(sup_img.reshape(B, ch, H, W).contiguous(), out=x4[:B])
+        ops.pack_input(qry_img.reshape(B, ch, H, W).contiguous(), out=x4[B:])
+        h, w = feature_hw(H, W)
+        cat23 = a.get("rp_cat23", (n, h, w, 1536))
+        self.trunk.forward(x4, stage_outs={1: cat23[..., :512], 2: cat23[..., 512:]})
+        f5 = ops.conv2d(cat23, self.l5, out=a.get("rp_l5", (n, h, w, MID)))
+        self.last_layer5 = f5
+        fg = sup_mask.reshape(B, 2, H, W)[:, :1].permute(0, 2, 3, 1)                 # the foreground plane as [B,H,W,1]
+        m = ops.resize_bilinear_ac(fg, (h, w), out=a.get("rp_mask", (B, h, w, 1)))
+        mu = ops.rpmms_em(f5[:B], m.view(B, h, w), self.model.pmm_mu0, out=a.get("rp_mu", (B, 2, ops.RPMMS_COLS, MID)),
+                          work=a.get("rp_em_work", (ops.rpmms_em_work_floats(B, h, w, MID),)))
+        self.last_mu = mu
+        base = ops.conv2d(f5[B:], self.l55_q, out=a.get("rp_base", (B, h, w, MID)))
+        x56 = a.get("rp_l56_in", (PASSES, B, h, w, HIST_CIN), zero=True)            # channels 258.. stay zero
+        ops.rpmms_proto_sum(self.wz, mu, base, self.b55, x56[..., :MID], dil=self.dil55,
+                            taps=a.get("rp_T", (B, ops.RPMMS_COLS, 9, MID)))
+        ops.rpmms_prob_map(f5[B:], mu, x56)
+        self.last_layer56_in = x56
+        f56 = ops.conv2d(x56.view(PASSES * B, h, w, HIST_CIN), self.l56, out=a.get("rp_l56", (PASSES * B, h, w, MID)))
+        preds, hist = [], None
+        for p in range(PASSES):
+            out = f56[p * B:(p + 1) * B]
+            for k, (c1, c2) in enumerate(self.res):
+                if k == 0:
+                    inp = a.get("rp_in_hist", (B, h, w, HIST_CIN), zero=True)       # channels 258.. stay zero
+                    ops.canet_block_input(out, inp, history=hist, with_history=True)
+                else:
+                    inp = ops.canet_block_input(out, a.get("rp_in", (B, h, w, MID)))
+                t = ops.conv2d(inp, c1, out=a.get("rp_t", (B, h, w, MID)))
+                out = ops.conv2d(t, c2, out=a.get(("rp_res", k), (B, h, w, MID)), residual=out, relu=False)
+            if p == PASSES - 1:
+                self.last_aspp_in = out
+            feat = self.aspp.forward(out)
+            c = ops.conv2d(feat, self.l9, out=a.get("rp_l9", (B, h, w, 64)))
+            pred = a.get(("rp_pred", p), (B, 2, h, w))
+            ops.resize_bilinear_ac(c[..., :2], (h, w), out=pred.permute(0, 2, 3, 1))  # NHWC -> NCHW (identity resize: exact)
+            preds.append(pred)
+            if p + 1 < PASSES:
+                hist = ops.canet_history_update(pred, out=a.get("rp_hist", (B, 2, h, w)))
+        return preds
