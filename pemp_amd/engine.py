@@ -4,7 +4,8 @@ libpemp_hip.so launches on NHWC activations.
 
 Eval-mode arithmetic only in this round (BatchNorm folded with running statistics exactly like
 ATen's eval kernel: alpha = weight * rsqrt(var + eps), beta = bias - mean * alpha; DropBlock and
-Dropout2d are identities).
+Dropout2d are identities).  Also what the model engines (canet_engine, pfenet_engine, rpmms_engine) and networks/ share:
+the episode packer, the padded-Cin and 2-class packers, the bottleneck walker of both ResNet trunks.
 """
 import os
 
@@ -64,6 +65,45 @@ def conv_params(conv, bn=None, relu=False, stem4=False, in_slice=None, dtype=tor
                                   conv.kernel_size[1], conv.stride[0], conv.padding[0], conv.dilation[0], kpad, stem4, relu))
 
 
+def pack_padded_in(conv, cin_pad, relu):
+    """[Cout, C, k, k] -> KRSC over ``cin_pad`` input channels (zero weights on the padding channels: the conv engine takes
+    Cin % 32 == 0)."""
+    w = conv.weight.detach().float()
+    co, ci, kh, kw = w.shape
+    wp = torch.zeros((co, kh, kw, cin_pad), dtype=torch.float32, device=w.device)
+    wp[..., :ci] = w.permute(0, 2, 3, 1)
+    return with_split3(ConvParams(wp.reshape(co, kh * kw * cin_pad).contiguous(), None, conv.bias.detach().float().contiguous(),
+                                  cin_pad, co, kh, kw, 1, conv.padding[0], conv.dilation[0], kh * kw * cin_pad, False, relu))
+
+
+def classifier2(conv):
+    """A C -> 2 1x1 classifier conv packed with 62 zero output channels (the conv engine takes Cout % 64 == 0)."""
+    cin, dev = conv.weight.shape[1], conv.weight.device
+    w = torch.zeros((64, cin), dtype=torch.float32, device=dev)
+    w[:2] = conv.weight.detach().float()[:, :, 0, 0]
+    b = torch.zeros(64, dtype=torch.float32, device=dev)
+    b[:2] = conv.bias.detach().float()
+    return with_split3(ConvParams(w.contiguous(), None, b.contiguous(), cin, 64, 1, 1, 1, 0, 1, cin, False, False))
+
+
+def logits_nchw(c, pred):
+    """The two live channels of ``classifier2``'s [B,h,w,64] output -> NCHW logits ``pred`` [B,2,h,w] (identity resize: exact)."""
+    ops.resize_bilinear_ac(c[..., :2], tuple(c.shape[1:3]), out=pred.permute(0, 2, 3, 1))
+    return pred
+
+
+def pack_episode(arena, groups, priors=None):
+    """Image groups [n_i,3,H,W] (supports first, then queries), each with its prior planes [n_i,H,W] when ``priors`` is given
+    -> the arena's NHWC4 input buffer ``x4`` [sum n_i,H,W,4], one ``ops.pack_input`` per group."""
+    H, W = groups[0].shape[-2:]
+    x4 = arena.get("x4", (sum(g.shape[0] for g in groups), H, W, 4), torch.float32)
+    o = 0
+    for i, g in enumerate(groups):
+        ops.pack_input(g.contiguous(), None if priors is None else priors[i], out=x4[o:o + g.shape[0]])
+        o += g.shape[0]
+    return x4
+
+
 #: Steps of at most this many feature rows (one or two episodes: 5202 rows per 1-shot episode) issue their INDEPENDENT convs
 #: as ONE grouped launch (ops.conv2d_group): the dilated ASPP branches, a stage's downsample conv beside its conv1.  A
 #: 5202-row conv is 41-82 tiles on 256 CUs; grouped, the members fill the chip without splitting K and without a launch +
@@ -110,7 +150,45 @@ class _BlockPlan:
             self.ds_extra = (blk.downsample[0].weight.detach()[:, sl[1]:, 0, 0].float() * self.ds.scale[:, None]).contiguous()
 
 
-class ResNetEngine:
+class _BottleneckTrunk:
+    """The bottleneck walker of both ResNet trunks: stride on conv1 (torchvision v1, ResNetEngine) or on conv2 (pfe_resent v1.5,
+    pfenet_engine.DeepBaseResNetEngine)."""
+    #: a block's conv1 and downsample conv go out as one grouped launch on small steps.  The deep-base trunk launches them one
+    #: by one: switching the grouping on there changes PFENet's speed and is therefore a change of its own.
+    GROUP_DS = True
+
+    def _block(self, x, bp, tag, c1_shift=None, ds_shift=None, out=None):
+        """``out``: where the block's result goes (an NHWC view, e.g. a channel slice of a wider buffer); None: the arena's
+        ping-pong buffer of ``tag``."""
+        a = self.arena
+        n, h, w, _ = x.shape
+        h1, w1 = (ops.conv_out_size(v, k, bp.c1.stride, bp.c1.pad, bp.c1.dil) for v, k in ((h, bp.c1.kh), (w, bp.c1.kw)))
+        ho, wo = (ops.conv_out_size(v, k, bp.c2.stride, bp.c2.pad, bp.c2.dil) for v, k in ((h1, bp.c2.kh), (w1, bp.c2.kw)))
+        if out is None:
+            out = a.get(("blk", tag), (n, ho, wo, bp.c3.cout))
+        y1 = a.get("y1", (n, h1, w1, bp.c1.cout))
+        res = a.get("res", (n, ho, wo, bp.ds.cout)) if bp.ds is not None else x
+        # small step: conv1 and the downsample conv read the same x -- one grouped launch
+        grouped = self.GROUP_DS and bp.ds is not None and c1_shift is None and ds_shift is None \
+            and 0 < n * ho * wo <= GROUP_MAX_ROWS and x.dtype == torch.float32
+        if grouped:
+            ops.conv2d_group([x, x], [bp.c1, bp.ds], [y1, res])
+        else:
+            ops.conv2d(x, bp.c1, out=y1, shift_override=c1_shift, per_image_shift=c1_shift is not None)
+        y2 = ops.conv2d(y1, bp.c2, out=a.get("y2", (n, ho, wo, bp.c2.cout)))
+        if bp.ds is not None and not grouped:
+            ops.conv2d(x, bp.ds, out=res, shift_override=ds_shift, per_image_shift=ds_shift is not None)
+        return ops.conv2d(y2, bp.c3, out=out, residual=res)
+
+    def _stage(self, x, si, final_out=None):
+        """Stage ``si``; ``final_out``: an NHWC view its last block writes to (e.g. a channel slice of a wider buffer)."""
+        blocks = self.stages[si]
+        for bi, bp in enumerate(blocks):
+            x = self._block(x, bp, (si, bi & 1), out=final_out if bi == len(blocks) - 1 else None)
+        return x
+
+
+class ResNetEngine(_BottleneckTrunk):
     """ResNet trunk (reference: networks/backbones.py:124-136)."""
 
     def __init__(self, prm, arena):
@@ -119,31 +197,6 @@ class ResNetEngine:
         self.stages = []
         for name in ("layer1", "layer2", "layer3"):
             self.stages.append([_BlockPlan(b, dtype=arena.dtype) for b in getattr(prm, name)])
-
-    def _block(self, x, bp, tag, c1_shift=None, ds_shift=None, out=None):
-        """``out``: where the block's result goes (an NHWC view, e.g. a channel slice of a wider buffer); None: the arena's
-        ping-pong buffer of ``tag``."""
-        a = self.arena
-        n, h, w, _ = x.shape
-        ho = ops.conv_out_size(h, 1, bp.c1.stride, 0, 1)
-        wo = ops.conv_out_size(w, 1, bp.c1.stride, 0, 1)
-        if out is None:
-            out = a.get(("blk", tag), (n, ho, wo, bp.c3.cout))
-        if bp.ds is not None and c1_shift is None and ds_shift is None and 0 < n * ho * wo <= GROUP_MAX_ROWS and x.dtype == torch.float32:
-            # small step: conv1 and the downsample conv read the same x -- one grouped launch
-            y1, res = ops.conv2d_group([x, x], [bp.c1, bp.ds], [a.get("y1", (n, ho, wo, bp.c1.cout)),
-                                                                a.get("res", (n, ho, wo, bp.ds.cout))])
-            y2 = ops.conv2d(y1, bp.c2, out=a.get("y2", (n, ho, wo, bp.c2.cout)))
-            return ops.conv2d(y2, bp.c3, out=out, residual=res)
-        y1 = ops.conv2d(x, bp.c1, out=a.get("y1", (n, ho, wo, bp.c1.cout)),
-                        shift_override=c1_shift, per_image_shift=c1_shift is not None)
-        y2 = ops.conv2d(y1, bp.c2, out=a.get("y2", (n, ho, wo, bp.c2.cout)))
-        if bp.ds is not None:
-            res = ops.conv2d(x, bp.ds, out=a.get("res", (n, ho, wo, bp.ds.cout)),
-                             shift_override=ds_shift, per_image_shift=ds_shift is not None)
-        else:
-            res = x
-        return ops.conv2d(y2, bp.c3, out=out, residual=res)
 
     def stem_forward(self, x4):
         a = self.arena
@@ -164,10 +217,8 @@ class ResNetEngine:
         """``stage_outs`` {stage index: NHWC view}: the last block of that stage writes there (CANet: layer2 and layer3 into
         the channel slices of one buffer, so that their concatenation is never formed)."""
         x = self.stem_forward(x4)
-        for si, blocks in enumerate(self.stages):
-            for bi, bp in enumerate(blocks):
-                out = stage_outs.get(si) if stage_outs and bi == len(blocks) - 1 else None
-                x = self._block(x, bp, (si, bi & 1), out=out)
+        for si in range(len(self.stages)):
+            x = self._stage(x, si, stage_outs.get(si) if stage_outs else None)
         return x
 
 
@@ -237,7 +288,7 @@ class VGG16CMEngine:
                 conv = seq[2 * k]
                 relu = not (pool is None and k == nconv - 1 and not prm.last_relu)
                 if k == 0 and not first:
-                    convs.append(self._pack_extra(conv, relu))
+                    convs.append(pack_padded_in(conv, conv.weight.shape[1] - 2 + self.PADC, relu))
                 else:
                     convs.append(conv_params(conv, None, relu=relu, stem4=first and k == 0))
             self.stages.append((convs, cout, pool))
@@ -245,16 +296,6 @@ class VGG16CMEngine:
         self.lin = [(l.weight.detach().float().contiguous(), l.bias.detach().float().contiguous())
                     for l in (prm.linear1, prm.linear2, prm.linear3, prm.linear4)]
         self.group, self.n_groups = None, 0
-
-    def _pack_extra(self, conv, relu):
-        """[Cout, C+2, 3, 3] -> KRSC over C + PADC input channels (zero weights on the padding channels)."""
-        w = conv.weight.detach().float()
-        co, ci, kh, kw = w.shape
-        wp = torch.zeros((co, kh, kw, ci - 2 + self.PADC), dtype=torch.float32, device=w.device)
-        wp[..., :ci] = w.permute(0, 2, 3, 1)
-        cin = ci - 2 + self.PADC
-        return with_split3(ConvParams(wp.reshape(co, kh * kw * cin).contiguous(), None, conv.bias.detach().float().contiguous(),
-                                      cin, co, kh, kw, 1, conv.padding[0], conv.dilation[0], kh * kw * cin, False, relu))
 
     def forward(self, x4, prior):
         """x4: NHWC4 input (RGB + prior); prior: [N,H,W] fp32 mask plane -> NHWC features [N,h,w,512]."""

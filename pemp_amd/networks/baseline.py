@@ -63,17 +63,13 @@ class Baseline(_HeadMixin, backbones.BaseModel):
 
     def lowres(self, sup_img, sup_mask, qry_img, ret_ind=False, dist_scalar=None):
         dist_scalar = net_ingredient.cfg["dist_scalar"] if dist_scalar is None else dist_scalar
-        B, S, ch, H, W = sup_img.shape
+        B, S, _, H, W = sup_img.shape
         Q = qry_img.shape[1]
         if Q != 1:
             raise ValueError("query must be 1")
         eng = self._engine_for(sup_img.device)
         a = eng["arena"]
-        n = B * (S + Q)
-        x4 = a.get("x4", (n, H, W, 4))
-        ops.pack_input(sup_img.reshape(B * S, ch, H, W).contiguous(), out=x4[:B * S])
-        ops.pack_input(qry_img.reshape(B * Q, ch, H, W).contiguous(), out=x4[B * S:])
-        f = eng["trunk"].forward(x4)
+        f = eng["trunk"].forward(engine.pack_episode(a, (sup_img.flatten(0, 1), qry_img.flatten(0, 1))))
         if eng["proj"] is not None:
             f = ops.conv2d(f, eng["proj"], out=a.get("feat", tuple(f.shape[:3]) + (eng["proj"].cout,)))
         self.__dict__["_last_feats"] = f

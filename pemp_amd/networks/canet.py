@@ -133,34 +133,12 @@ class CaNet(_HeadMixin, backbones.BaseModel):
         are copied into static buffers before each replay, so a replay may name other slots than the captured call; the
         table is addressed in place.  The returned tensor is the graph's static output."""
         self._require_eval_gpu(self, sup_img, sup_mask, qry_img, table, read_slot, write_slot)
-        device = sup_img.device
-        eng = self._engine_for(device)
         inputs = (sup_img, sup_mask, qry_img, read_slot, write_slot)
         key = ("slots", table.data_ptr(), tuple(table.shape)) + tuple((tuple(t.shape), t.dtype) for t in inputs) + (ops.EVAL_SPLITK,)
-        graphs = eng.setdefault("graphs", {})
-        entry = graphs.get(key)
-        if entry is None:
-            static_in = [torch.empty(t.shape, dtype=t.dtype, device=device) for t in inputs]
-            for s, t in zip(static_in, inputs):
-                s.copy_(t)
-            none = torch.full_like(static_in[4], -1)                 # warm-up and capture write no table row
-            side = torch.cuda.Stream(device=device)
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side), torch.no_grad():
-                for _ in range(2):                                   # warm-up: populates arena + workspaces
-                    self.lowres_slots(*static_in[:3], table, static_in[3], none)
-            torch.cuda.current_stream().wait_stream(side)
-            torch.cuda.synchronize()
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph), torch.no_grad():
-                out = self.lowres_slots(*static_in[:3], table, static_in[3], static_in[4])
-            entry = (graph, static_in, out)
-            graphs[key] = entry
-        graph, static_in, out = entry
-        for s, t in zip(static_in, inputs):
-            s.copy_(t, non_blocking=True)
-        graph.replay()
-        return out
+        eng = self._engine_for(sup_img.device)
+        none = None if key in eng.get("graphs", ()) else torch.full_like(write_slot, -1)      # the warm-up writes no table row
+        return self._replay(eng, key, inputs, lambda s: self.lowres_slots(*s[:3], table, s[3], none),
+                            lambda s: self.lowres_slots(*s[:3], table, *s[3:]))
 
     def forward(self, sup_img, sup_mask, qry_img, out_shape=None, history_mask=None):
         """Same contract as the reference's eval forward (canet.py:127-161): ``out_shape`` False -> the feature-resolution

@@ -176,9 +176,18 @@ class _HeadMixin:
             device = inputs[0].device
         elif self.training:
             self._require_eval_gpu(self)
-        eng = self._engine_for(torch.device(device))
         key = tuple((tuple(t.shape), t.dtype) for t in inputs) + (ret_ind, ops.EVAL_SPLITK)    # the conv variants are baked in
         # (the bf16 variant has its own engine, hence its own graphs)
+        run = lambda static_in: self.lowres(*static_in, ret_ind=ret_ind)
+        return self._replay(self._engine_for(torch.device(device)), key, inputs, run, run)
+
+    @staticmethod
+    def _replay(eng, key, inputs, warm, capture):
+        """The capture protocol of every graphed entry point: on the first call with ``key`` the inputs go into static buffers
+        on the engine's device, ``warm(static_in)`` runs twice on a side stream (populates arena + workspaces) and
+        ``capture(static_in)`` is recorded into a hipGraph; every call then copies the inputs over and replays.  -> what
+        ``capture`` returned (the graph's static outputs)."""
+        device = eng["device"]
         graphs = eng.setdefault("graphs", {})
         entry = graphs.get(key)
         if entry is None:
@@ -188,15 +197,14 @@ class _HeadMixin:
             side = torch.cuda.Stream(device=device)
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side), torch.no_grad():
-                for _ in range(2):                       # warm-up: populates arena + workspaces
-                    self.lowres(*static_in, ret_ind=ret_ind)
+                for _ in range(2):
+                    warm(static_in)
             torch.cuda.current_stream().wait_stream(side)
             torch.cuda.synchronize()
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph), torch.no_grad():
-                out = self.lowres(*static_in, ret_ind=ret_ind)
-            entry = (graph, static_in, out)
-            graphs[key] = entry
+                out = capture(static_in)
+            entry = graphs[key] = (graph, static_in, out)
         graph, static_in, out = entry
         for s, t in zip(static_in, inputs):
             s.copy_(t, non_blocking=True)
@@ -254,15 +262,8 @@ class PEMPStage1(_HeadMixin, backbones.BaseModel):
 
     def encode(self, *image_groups):
         """One or more [n_i,3,H,W] fp32 device tensors -> NHWC features [sum n_i,h,w,c] (in order)."""
-        dev = image_groups[0].device
-        eng = self._engine_for(dev)
-        n = sum(g.shape[0] for g in image_groups)
-        H, W = image_groups[0].shape[-2:]
-        x4 = eng["arena"].get("x4", (n, H, W, 4), torch.float32)
-        o = 0
-        for g in image_groups:
-            ops.pack_input(g.contiguous(), out=x4[o:o + g.shape[0]])
-            o += g.shape[0]
+        eng = self._engine_for(image_groups[0].device)
+        x4 = engine.pack_episode(eng["arena"], image_groups)
         f = eng["trunk"].forward(x4)
         return eng["purifier"].forward(f) if eng["purifier"] is not None else f
 

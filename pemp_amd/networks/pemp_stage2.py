@@ -114,9 +114,7 @@ class PEMPStage2(_HeadMixin, backbones.BaseModel):
         prior = a.get("prior", (n, H, W))
         prior[:B * S].copy_(sup_mask[:, :, 0].reshape(B * S, H, W))
         prior[B * S:].copy_(qry_prior.reshape(B * Q, H, W))
-        x4 = a.get("x4", (n, H, W, 4))
-        ops.pack_input(sup_img.reshape(B * S, ch, H, W).contiguous(), prior[:B * S], out=x4[:B * S])
-        ops.pack_input(qry_img.reshape(B * Q, ch, H, W).contiguous(), prior[B * S:], out=x4[B * S:])
+        x4 = engine.pack_episode(a, (sup_img.flatten(0, 1), qry_img.flatten(0, 1)), (prior[:B * S], prior[B * S:]))
         trunk = eng["trunk"]
         key = ("group", B, S, Q)
         if key not in a.ws:

@@ -19,7 +19,7 @@ Layout choices:
 import torch
 
 from . import ops
-from .engine import conv_params, with_split3
+from .engine import _BlockPlan, _BottleneckTrunk, classifier2, conv_params, logits_nchw, pack_episode, with_split3
 from .ops import ConvParams
 
 PYRAMID_BINS = (60, 30, 15, 8)
@@ -27,46 +27,17 @@ REDUCE = 256
 MERGE_CIN = REDUCE + 32                 # query channels + the prior channel, zero-padded to a multiple of 32
 
 
-class _DeepBlockPlan:
-    """One pfe_resent Bottleneck (v1.5: the stride sits on the 3x3 conv; layer 3 / 4 dilated with stride 1)."""
-
-    def __init__(self, blk):
-        self.c1 = conv_params(blk.conv1, blk.bn1, relu=True)
-        self.c2 = conv_params(blk.conv2, blk.bn2, relu=True)
-        self.c3 = conv_params(blk.conv3, blk.bn3, relu=True)      # relu after the residual add
-        self.ds = conv_params(blk.downsample[0], blk.downsample[1], relu=False) if blk.downsample is not None else None
-
-
-class DeepBaseResNetEngine:
-    """pfe_resent.ResNet(Bottleneck, [3, 4, 6, 3], deep_base=True) with PFENet's dilations (pfenet.py:68-77)."""
+class DeepBaseResNetEngine(_BottleneckTrunk):
+    """pfe_resent.ResNet(Bottleneck, [3, 4, 6, 3], deep_base=True) with PFENet's dilations (pfenet.py:68-77): a three-conv stem, a
+    max-pool without ceil_mode and v1.5 bottlenecks (the stride sits on the 3x3 conv; layer 3 / 4 dilated with stride 1)."""
+    GROUP_DS = False                    # see _BottleneckTrunk: grouping conv1 with the downsample conv would change PFENet's speed
 
     def __init__(self, model, arena):
         self.arena = arena
         l0 = model.layer0
         self.stem = [conv_params(l0[0], l0[1], relu=True, stem4=True), conv_params(l0[3], l0[4], relu=True),
                      conv_params(l0[6], l0[7], relu=True)]
-        self.stages = [[_DeepBlockPlan(b) for b in getattr(model, f"layer{i}")] for i in (1, 2, 3, 4)]
-
-    def _block(self, x, bp, out):
-        a = self.arena
-        n, h, w, _ = x.shape
-        ho = ops.conv_out_size(h, bp.c2.kh, bp.c2.stride, bp.c2.pad, bp.c2.dil)
-        wo = ops.conv_out_size(w, bp.c2.kw, bp.c2.stride, bp.c2.pad, bp.c2.dil)
-        y1 = ops.conv2d(x, bp.c1, out=a.get("pf_y1", (n, h, w, bp.c1.cout)))
-        y2 = ops.conv2d(y1, bp.c2, out=a.get("pf_y2", (n, ho, wo, bp.c2.cout)))
-        res = ops.conv2d(x, bp.ds, out=a.get("pf_res", (n, ho, wo, bp.ds.cout))) if bp.ds is not None else x
-        return ops.conv2d(y2, bp.c3, out=out, residual=res)
-
-    def _stage(self, x, si, final_out=None):
-        blocks = self.stages[si]
-        for bi, bp in enumerate(blocks):
-            n, h, w, _ = x.shape
-            ho = ops.conv_out_size(h, bp.c2.kh, bp.c2.stride, bp.c2.pad, bp.c2.dil)
-            wo = ops.conv_out_size(w, bp.c2.kw, bp.c2.stride, bp.c2.pad, bp.c2.dil)
-            out = final_out if (bi == len(blocks) - 1 and final_out is not None) else \
-                self.arena.get(("pf_blk", si, bi & 1), (n, ho, wo, bp.c3.cout))
-            x = self._block(x, bp, out)
-        return x
+        self.stages = [[_BlockPlan(b) for b in getattr(model, f"layer{i}")] for i in (1, 2, 3, 4)]
 
     def forward_to_layer3(self, x4):
         """x4 NHWC4 [n,H,W,4] -> [n,h,w,1536]: layer 3 in channels 0..1023, layer 2 in 1024..1535."""
@@ -115,12 +86,7 @@ class PFENetEngine:
         self.res1 = conv_params(model.res1[0], None, relu=True)
         self.res2 = (conv_params(model.res2[0], None, relu=True), conv_params(model.res2[2], None, relu=True))
         self.cls0 = conv_params(model.cls[0], None, relu=True)
-        c3 = model.cls[3]
-        w = torch.zeros((64, REDUCE), dtype=torch.float32, device=c3.weight.device)
-        w[:2] = c3.weight.detach().float()[:, :, 0, 0]
-        b = torch.zeros(64, dtype=torch.float32, device=c3.weight.device)
-        b[:2] = c3.bias.detach().float()
-        self.cls3 = with_split3(ConvParams(w.contiguous(), None, b.contiguous(), REDUCE, 64, 1, 1, 1, 0, 1, REDUCE, False, False))
+        self.cls3 = classifier2(model.cls[3])
         self._ones = set()
 
     def lowres(self, sup_img, sup_mask, qry_img):
@@ -128,9 +94,7 @@ class PFENetEngine:
         a = self.arena
         B, S, ch, H, W = sup_img.shape
         ns, n = B * S, B * S + B
-        x4 = a.get("x4", (n, H, W, 4))
-        ops.pack_input(sup_img.reshape(ns, ch, H, W).contiguous(), out=x4[:ns])
-        ops.pack_input(qry_img.reshape(B, ch, H, W).contiguous(), out=x4[ns:])
+        x4 = pack_episode(a, (sup_img.flatten(0, 1), qry_img.flatten(0, 1)))
         cat23 = self.trunk.forward_to_layer3(x4)                                 # [n,h,w,1536]
         h, w = cat23.shape[1:3]
         # support masks at feature resolution (:182-185, == 1 then bilinear align_corners), the queries' rows = 1
@@ -179,6 +143,4 @@ class PFENetEngine:
         q2 = ops.scale_add(r, residual=q1, out=a.get("pf_q2", (B, h, w, REDUCE)))
         c = ops.conv2d(q2, self.cls0, out=a.get("pf_c0", (B, h, w, REDUCE)))
         c = ops.conv2d(c, self.cls3, out=a.get("pf_c3", (B, h, w, 64)))
-        pred = a.get("pf_pred", (B, 2, h, w))
-        ops.resize_bilinear_ac(c[..., :2], (h, w), out=pred.permute(0, 2, 3, 1))    # NHWC -> NCHW (identity resize: exact)
-        return pred
+        return logits_nchw(c, a.get("pf_pred", (B, 2, h, w)))

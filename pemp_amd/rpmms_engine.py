@@ -12,25 +12,22 @@ Layout choices (RPMMs):
   inside the image (``ops.rpmms_proto_sum``; ``ops.canet_zterm``'s trick with the ReLU inside the sum);
 - the three ``layer56`` inputs are three [B,h,w,288] buffers (256 sums, P_b, P_f, 30 zero channels: the conv engine takes
   Cin % 32 == 0) behind one another: ``layer56`` is one conv launch over 3B images;
-- the three ``Segmentation`` passes run in order on B images each, the softmax of a pass (``ops.canet_history_update``) being
-  the next one's history channels; the reference's ``interpolate`` of the history (:274) is the identity at feature size;
-- ``layer7`` is the 1280 -> 256 1x1 + ReLU behind the tail-less ASPP: exactly what ``ASPPEngine`` folds as its ``layer6``;
-- ``layer9`` (256 -> 2) is packed with 62 zero output channels, its two live channels copied into NCHW logits.
+- the three ``Segmentation`` passes are ``canet_engine.CANetTail`` run in order on B images each, the softmax of a pass
+  (``ops.canet_history_update``) being the next one's history channels; the reference's ``interpolate`` of the history
+  (:274) is the identity at feature size;
+- ``layer7`` is the 1280 -> 256 1x1 + ReLU behind the tail-less ASPP: exactly what ``ASPPEngine`` folds as its ``layer6``, and
+  ``layer9`` (256 -> 2) is the tail's classifier.
 """
-import types
-
-import torch
-
 from . import ops
-from .canet_engine import HIST_CIN, MID, _pack_padded_in, feature_hw
-from .engine import ASPPEngine, ResNetEngine, conv_params, with_split3
-from .ops import ConvParams
+from .canet_engine import HIST_CIN, MID, CANetTail, feature_hw
+from .engine import ResNetEngine, conv_params, pack_episode, pack_padded_in
 
 PASSES = 3
 
 
 class RPMMsEngine:
     """The whole eval forward: ``lowres(sup_img, sup_mask, qry_img)`` -> [out0, out1, out2], logits [B,2,h,w] each."""
+    last_aspp_in = property(lambda self: self.tail.last_aspp_in)          # of the last pass
 
     def __init__(self, model, arena):
         self.arena = arena
@@ -43,28 +40,15 @@ class RPMMsEngine:
         self.b55 = c55.bias.detach().float().contiguous()
         self.wz = ops.pack_canet_zweights(c55.weight[:, MID:])
         self.dil55 = c55.dilation[0]
-        self.l56 = _pack_padded_in(model.layer56[0], HIST_CIN, True)
-        self.res = []
-        for k, seq in enumerate((model.residule1, model.residule2, model.residule3)):
-            first = _pack_padded_in(seq[1], HIST_CIN, True) if k == 0 else conv_params(seq[1], None, relu=True)
-            self.res.append((first, conv_params(seq[3], None, relu=False)))
-        prm = types.SimpleNamespace(layer6=model.layer7[0], **{f"aspp_{i}": getattr(model.layer6, f"aspp_{i}") for i in range(5)})
-        self.aspp = ASPPEngine(prm, arena, out_relu=True)
-        l9 = model.layer9
-        w = torch.zeros((64, MID), dtype=torch.float32, device=l9.weight.device)
-        w[:2] = l9.weight.detach().float()[:, :, 0, 0]
-        b = torch.zeros(64, dtype=torch.float32, device=l9.weight.device)
-        b[:2] = l9.bias.detach().float()
-        self.l9 = with_split3(ConvParams(w.contiguous(), None, b.contiguous(), MID, 64, 1, 1, 1, 0, 1, MID, False, False))
+        self.l56 = pack_padded_in(model.layer56[0], HIST_CIN, True)
+        self.tail = CANetTail(arena, (model.residule1, model.residule2, model.residule3), model.layer6, model.layer7[0], model.layer9)
 
     def lowres(self, sup_img, sup_mask, qry_img):
         """sup_img [B,1,3,H,W], sup_mask [B,1,2,H,W] (plane 0: foreground), qry_img [B,1,3,H,W] on the device."""
         a = self.arena
-        B, S, ch, H, W = sup_img.shape
+        B, _, _, H, W = sup_img.shape
         n = 2 * B
-        x4 = a.get("x4", (n, H, W, 4))
-        ops.pack_input(sup_img.reshape(B, ch, H, W).contiguous(), out=x4[:B])
-        ops.pack_input(qry_img.reshape(B, ch, H, W).contiguous(), out=x4[B:])
+        x4 = pack_episode(a, (sup_img.flatten(0, 1), qry_img.flatten(0, 1)))
         h, w = feature_hw(H, W)
         cat23 = a.get("rp_cat23", (n, h, w, 1536))
         self.trunk.forward(x4, stage_outs={1: cat23[..., :512], 2: cat23[..., 512:]})
@@ -84,22 +68,7 @@ class RPMMsEngine:
         f56 = ops.conv2d(x56.view(PASSES * B, h, w, HIST_CIN), self.l56, out=a.get("rp_l56", (PASSES * B, h, w, MID)))
         preds, hist = [], None
         for p in range(PASSES):
-            out = f56[p * B:(p + 1) * B]
-            for k, (c1, c2) in enumerate(self.res):
-                if k == 0:
-                    inp = a.get("rp_in_hist", (B, h, w, HIST_CIN), zero=True)       # channels 258.. stay zero
-                    ops.canet_block_input(out, inp, history=hist, with_history=True)
-                else:
-                    inp = ops.canet_block_input(out, a.get("rp_in", (B, h, w, MID)))
-                t = ops.conv2d(inp, c1, out=a.get("rp_t", (B, h, w, MID)))
-                out = ops.conv2d(t, c2, out=a.get(("rp_res", k), (B, h, w, MID)), residual=out, relu=False)
-            if p == PASSES - 1:
-                self.last_aspp_in = out
-            feat = self.aspp.forward(out)
-            c = ops.conv2d(feat, self.l9, out=a.get("rp_l9", (B, h, w, 64)))
-            pred = a.get(("rp_pred", p), (B, 2, h, w))
-            ops.resize_bilinear_ac(c[..., :2], (h, w), out=pred.permute(0, 2, 3, 1))  # NHWC -> NCHW (identity resize: exact)
-            preds.append(pred)
+            preds.append(self.tail.forward(f56[p * B:(p + 1) * B], a.get(("rp_pred", p), (B, 2, h, w)), hist))
             if p + 1 < PASSES:
-                hist = ops.canet_history_update(pred, out=a.get("rp_hist", (B, 2, h, w)))
+                hist = ops.canet_history_update(preds[p], out=a.get("rp_hist", (B, 2, h, w)))
         return preds

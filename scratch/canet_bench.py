@@ -5,13 +5,10 @@ usage: python scratch/canet_bench.py [--shots 1,5] [--per-step 25,1] [--episodes
 Per (shot, episodes per step) one JSON line: episodes/s of ``entry.canet.Evaluator.eval_round`` (captured slot-form steps,
 fused tail, history table; Wgen weights) over a synthetic round with repeating keys whose episodes are generated once and
 kept on the host, after one warm-up round; the number of steps the group-closing rule made of the round; FLOPs per episode
-from the layer shapes below.  Then the z-term path against the variant that materialises layer55's 512-channel input
-(PEMP_CANET_ZCAT=1, same function): each arm in a child process of its own (the switch is read when the engine is built),
-alternating, the captured 25-episode lowres step timed alone."""
+from the layer shapes below.  Then, twice, the captured 25-episode lowres step timed alone."""
 import argparse
 import json
 import os
-import subprocess
 import sys
 import time
 
@@ -23,7 +20,7 @@ def conv_out(i, k, s, p, d=1):
     return (i + 2 * p - d * (k - 1) - 1) // s + 1
 
 
-def flops_per_episode(shot, H=401, zcat=False):
+def flops_per_episode(shot, H=401):
     """2 * MACs of every conv of one episode's eval forward (the reference's layer shapes, canet.py:50-121)."""
     imgs = shot + 1
     conv = lambda n, h, cin, cout, k: 2.0 * n * h * h * cin * cout * k * k
@@ -38,7 +35,7 @@ def flops_per_episode(shot, H=401, zcat=False):
             if b == 0:
                 f += conv(imgs, ho, cin, planes * 4, 1)
             h, cin = ho, planes * 4
-    head = {"layer5": conv(imgs, h, 1536, 256, 3), "layer55": conv(1, h, 512 if zcat else 256, 256, 3),
+    head = {"layer5": conv(imgs, h, 1536, 256, 3), "layer55": conv(1, h, 256, 256, 3),
             "residual": 6 * conv(1, h, 256, 256, 3), "aspp": conv(1, h, 256, 256, 1) + 3 * conv(1, h, 256, 256, 3) + conv(1, h, 1024, 256, 1)}
     return f + sum(head.values()), head, h
 
@@ -70,11 +67,9 @@ def _model(shot, dev):
     return net.to(dev).eval()
 
 
-def step_arm(shot, per, steps, warmup):
-    """One arm of the z-term A/B (child process): ms per captured lowres step of ``per`` episodes."""
-    from pemp_amd import canet_engine, synth
-    dev = torch.device("cuda:0")
-    net = _model(shot, dev)
+def step_alone(net, dev, shot, per, steps, warmup):
+    """ms per captured lowres step of ``per`` episodes."""
+    from pemp_amd import synth
     b = synth.make_batch(list(range(1000, 1000 + per)), shot=shot, height=401, width=401, out_hw=(401, 401))
     inputs = [torch.from_numpy(b[k]).to(dev) for k in ("sup_img", "sup_mask", "qry_img")]
     with torch.no_grad():
@@ -86,7 +81,7 @@ def step_arm(shot, per, steps, warmup):
             out = net.lowres_graphed(*inputs)[0]
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
-    print(json.dumps({"arm": "zcat" if canet_engine.ZCAT else "zterm", "shot": shot, "episodes_per_step": per,
+    print(json.dumps({"captured_step_alone": True, "shot": shot, "episodes_per_step": per,
                       "ms_per_step": round(1e3 * dt / steps, 3), "episodes_per_s": round(per * steps / dt, 2),
                       "logit_sum": float(out.double().sum())}), flush=True)
 
@@ -97,10 +92,7 @@ def main():
     ap.add_argument("--per-step", default="25,1")
     ap.add_argument("--episodes", type=int, default=200)
     ap.add_argument("--rounds", type=int, default=3)
-    ap.add_argument("--arm", default="", help="internal: run one arm of the z-term A/B (shot,per_step,steps,warmup)")
     args = ap.parse_args()
-    if args.arm:
-        return step_arm(*[int(v) for v in args.arm.split(",")])
     from pemp_amd.entry import canet as entry
     dev = torch.device("cuda:0")
     for shot in [int(s) for s in args.shots.split(",")]:
@@ -122,10 +114,9 @@ def main():
                               "distinct_keys": len(set(data.keys)), "steps_per_round": nsteps,
                               "gflop_per_episode": round(fl / 1e9, 2), "tflops": round(fl * eps / 1e12, 2), "feature_hw": h,
                               "head_gflop": {k: round(v / 1e9, 2) for k, v in head.items()}}), flush=True)
-    for rep in range(2):                                                     # the two arms alternating, twice
-        for zcat in ("0", "1"):
-            env = dict(os.environ, PEMP_CANET_ZCAT=zcat)
-            subprocess.run([sys.executable, os.path.abspath(__file__), "--arm", "1,25,20,5"], env=env, check=True, timeout=600)
+    net = _model(1, dev)
+    for rep in range(2):
+        step_alone(net, dev, 1, 25, 20, 5)
 
 
 if __name__ == "__main__":
