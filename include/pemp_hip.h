@@ -596,6 +596,31 @@ int pemp_canet_block_input_f32(const float* x, int ldx, const float* hist, const
 int pemp_canet_history_update_f32(const float* logits, float* table, const int* slot, int nslots, float* out, int B,
                                   int HW, void* stream);
 
+/* ---- CANet head training (csrc/canet_bwd.hip): adjoints of the kernels above + the classifier's backward.  Every reduction is
+ * a two-stage partial sum of fixed order (no atomics): bit-stable run to run.
+ * Adjoint of pemp_canet_zterm_f32.  g NHWC [B][h][w][Cout] (ldg): the gradient at layer55's pre-activation.  W: the z half of
+ * layer55's KRSC weight, W[(co * 9 + tap) * ldw + ci] (a column slice of [Cout][9][Cin_total]: ldw = Cin_total); z [B][Cin].
+ *   G[b][tap][co]  = sum of g[b][y][x][co] over the pixels whose tap lands inside the image (an empty window: exactly 0)
+ *   dz[b][ci]      = sum_tap sum_co W[co][tap][ci] G[b][tap][co]
+ *   dW[(co * 9 + tap) * ldw + ci] = sum_b G[b][tap][co] z[b][ci]        (written, not accumulated; laid out as W)           */
+size_t pemp_canet_zterm_bwd_workspace_bytes(int B, int h, int w, int Cout);
+int pemp_canet_zterm_bwd_f32(const float* g, int ldg, const float* W, int ldw, const float* z, float* G, float* dz, float* dW,
+                             void* ws, size_t ws_bytes, int B, int h, int w, int Cin, int Cout, int dil, void* stream);
+/* Adjoint of pemp_canet_support_vector_f32: df[b*S+s][p][c] (ldd) = dz[b][c] * m / (S * (sum_p m + 1e-5)), m = plane 0 of mask
+ * [B*S][2][H][W] sampled as the forward samples it.  An empty mask gives exact zeros.                                        */
+int pemp_canet_support_vector_bwd_f32(const float* dz, const float* mask, float* df, int ldd, int B, int S, int h, int w,
+                                      int H, int W, int C, void* stream);
+/* Backward of a 1x1 conv to 2 classes (layer7), one pass: dpred [B][2][HW] (NCHW), x NHWC [B][HW][C] (ldx), W [2][C] ->
+ * dx[b][p][:] (lddx) = dpred[b][0][p] W[0][:] + dpred[b][1][p] W[1][:], dW[k][c] = sum dpred[b][k][p] x[b][p][c], db[k].      */
+size_t pemp_canet_cls_bwd_workspace_bytes(int M, int C);
+int pemp_canet_cls_bwd_f32(const float* dpred, const float* x, int ldx, const float* W, float* dx, int lddx, float* dW, float* db,
+                           void* ws, size_t ws_bytes, int B, int HW, int C, void* stream);
+/* The first stage of pemp_head_bwd_f32 / pemp_head_bwd_dlogits_f32 on its own (the same kernel): dpred [B][2][h][w] = adjoint of
+ * F.interpolate(pred, (Ho,Wo), bilinear, align_corners) applied to the mean-CE gradient from (pred, target int64 [B][Ho][Wo],
+ * weight [B][Ho][Wo] | NULL, stats [B][8] of pemp_eval_tail_f32 or pemp_eval_tail_weighted_f32), or to `dlogits` [B][2][Ho][Wo] when given.        */
+int pemp_upsample_ce_bwd_f32(const float* pred, const int64_t* target, const float* weight, const double* stats,
+                             const float* dlogits, float* dpred, int B, int h, int w, int Ho, int Wo, void* stream);
+
 /* ---- RPMMs inference (networks/rpmms.py) -----------------------------------------------------------------------------
  * The EM of the prototype mixture models (PMMs.EM :65-86) for the mixtures K = 1 | 3 | 6 side by side (10 columns), foreground
  * (side 0, pixel weight m) and background (side 1, weight 1 - m): feat NHWC [B][h][w][C] (ldf), mask [B][h][w], mu0 [10][C]

@@ -149,6 +149,13 @@ SYMBOLS = {
     "pemp_canet_zterm_f32": (c_int, [c_fp, c_fp, c_fp, c_fp] + [c_int] * 7 + [c_fp]),
     "pemp_canet_block_input_f32": (c_int, [c_fp, c_int, c_fp, c_fp, c_int, c_fp] + [c_int] * 5 + [c_fp]),
     "pemp_canet_history_update_f32": (c_int, [c_fp, c_fp, c_fp, c_int, c_fp, c_int, c_int, c_fp]),
+    # CANet head training
+    "pemp_canet_zterm_bwd_workspace_bytes": (c_size, [c_int] * 4),
+    "pemp_canet_zterm_bwd_f32": (c_int, [c_fp, c_int, c_fp, c_int, c_fp, c_fp, c_fp, c_fp, c_fp, c_size] + [c_int] * 6 + [c_fp]),
+    "pemp_canet_support_vector_bwd_f32": (c_int, [c_fp, c_fp, c_fp] + [c_int] * 8 + [c_fp]),
+    "pemp_canet_cls_bwd_workspace_bytes": (c_size, [c_int] * 2),
+    "pemp_canet_cls_bwd_f32": (c_int, [c_fp, c_fp, c_int, c_fp, c_fp, c_int, c_fp, c_fp, c_fp, c_size] + [c_int] * 3 + [c_fp]),
+    "pemp_upsample_ce_bwd_f32": (c_int, [c_fp] * 6 + [c_int] * 5 + [c_fp]),
     # RPMMs inference
     "pemp_rpmms_em_f32": (c_int, [c_fp, c_int, c_fp, c_fp, c_fp, c_fp] + [c_int] * 5 + [c_fp]),
     "pemp_rpmms_prob_map_f32": (c_int, [c_fp, c_int, c_fp, c_fp, c_int, C.c_longlong, c_int, c_int, c_int, c_fp]),

@@ -50,3 +50,20 @@ extern "C" int pemp_head_bwd_dlogits_f32(const float* sup_feat, const float* qry
     return j16::pemp_head_bwd_dlogits_f32(sup_feat, qry_feat, ldf, mask, ctr, fwd_ws, protos, dlogits, dsup, dqry, ldd, dctr, ws,
                                           ws_bytes, B, S, h, w, H, W, Ho, Wo, c, p, map_full_res, dist_scalar, stream);
 }
+
+// The first stage of the head backward on its own: dpred [B][2][h][w] = adjoint of the bilinear (align_corners) upsample applied
+// to the CE gradient derived from (pred, target, weight | NULL, stats) -- normalised by the batch's valid-pixel total, label 255
+// ignored, as in pemp_head_bwd_f32 -- or to a given `dlogits` [B][2][Ho][Wo].  The same kernel the head backward launches.
+extern "C" int pemp_upsample_ce_bwd_f32(const float* pred, const int64_t* target, const float* weight, const double* stats,
+                                        const float* dlogits, float* dpred, int B, int h, int w, int Ho, int Wo, void* stream) {
+    PEMP_REQUIRE(dpred && (dlogits || (pred && target && stats)), "upsample_ce_bwd: null pointer");
+    PEMP_REQUIRE(B > 0 && B <= 65535 && h > 0 && w > 0 && Ho > 0 && Wo > 0 && (long long)h * w < (1LL << 30), "upsample_ce_bwd: bad sizes");
+    const int n = h * w;
+    if (dlogits)
+        hipLaunchKernelGGL(j8::upsample_bwd_kernel<false>, dim3(cdiv(n, 4), B), dim3(256), 0, (hipStream_t)stream, (const float*)nullptr,
+                           (const int64_t*)nullptr, (const float*)nullptr, (const double*)nullptr, B, dlogits, dpred, h, w, Ho, Wo);
+    else
+        hipLaunchKernelGGL(j8::upsample_bwd_kernel<true>, dim3(cdiv(n, 4), B), dim3(256), 0, (hipStream_t)stream, pred, target, weight,
+                           stats, B, (const float*)nullptr, dpred, h, w, Ho, Wo);
+    return launch_status("upsample_ce_bwd");
+}

@@ -12,7 +12,12 @@ data_kits/pascal_voc.py:324,420-429) and feeds it to the next episode of the rou
 * **rank assignment** (``assign_ranks``): episodes go to ranks by history key, all episodes of a key on one rank in round
   order, not as ``tasks[rank::world]``.
 
-The table is cleared (all keys forgotten) at every ``sample_tasks()``.  Training is not ported: ``train`` raises."""
+The table is cleared (all keys forgotten) at every ``sample_tasks()``.
+
+``train_head`` trains the head behind the frozen trunk (``pemp_amd.train_canet``; the reference's ``freeze_backbone = True``
+procedure, entry/canet.py:106-175) with the same kind of table: a training episode reads the row of its key -- dropped with
+probability 0.3, as the reference's loader drops a stored history (data_kits/pascal_voc.py:316,426) -- and the step writes its
+softmax back.  ``train`` (the reference's command name) still raises: a ``train()``-mode autograd forward is not ported."""
 import time
 
 import numpy as np
@@ -222,6 +227,125 @@ def test(_config, split, shot, query, exp_id, ckpt):
     loss, miou, biou = ev.start_eval_loop(data, num_classes(d["dataset"]), split, _config["te"]["epochs"], logger,
                                           batch=d["test_bs"], dataset_name=d["dataset"])
     return f"Loss: {loss:.4f}, mIoU: {np.mean(miou) * 100:.2f}, bIoU: {np.mean(biou) * 100:.2f}"
+
+
+class SyntheticHistoryTrainEpisodes(SyntheticHistoryEpisodes):
+    """``SyntheticHistoryEpisodes`` in the training role: the query label comes at the input size (the reference resizes a
+    training label with its image, data_kits/pascal_voc.py:401-406)."""
+
+    def task(self, i):
+        seed = self._seed(i)
+        cls, qi = self.history_key(i)
+        hw = (self.height, self.width)
+        ep = synth.make_episode(seed, self.shot, self.height, self.width, index=i, split=self.split, dataset=self.dataset)
+        qep = synth.make_episode(1_000_003 * cls + qi, 1, self.height, self.width, index=qi, out_hw=hw, split=self.split,
+                                 dataset=self.dataset)
+        t = lambda a: torch.from_numpy(a)[None]
+        return (t(ep["sup_img"]), t(ep["sup_mask"]), t(qep["qry_img"])), t(qep["qry_mask"]), torch.tensor([cls])
+
+
+class HistorySlots:
+    """Host side of the training history: ``key -> table row`` and the reference's history drop.  ``slots(keys)`` names, for
+    one batch, the row each episode reads (-1: zeros -- no stored history yet, or a stored one dropped: one draw of a
+    ``RandomState(9876)`` per episode that HAS a stored history, in batch order, ``<= 0.3`` drops it; data_kits/pascal_voc.py:
+    316,422-427) and the row its softmax goes to (a key twice in a batch: the last episode's stays, as the reference's
+    sequential write-back leaves it; the others write nowhere).  The sampler lives as long as the object (the reference seeds
+    it in ``reset_sampler``, once); ``clear()`` forgets the keys (``sample_tasks``, every epoch)."""
+    DROP = 0.3
+
+    def __init__(self):
+        self.sampler = np.random.RandomState(9876)
+        self.slot_of = {}
+
+    def clear(self):
+        self.slot_of = {}
+
+    def slots(self, keys):
+        read = []
+        for k in keys:
+            s = self.slot_of.get(k, -1)
+            if s >= 0 and self.sampler.random_sample() <= self.DROP:
+                s = -1
+            read.append(s)
+        rows = [self.slot_of.setdefault(k, len(self.slot_of)) for k in keys]
+        last = {k: j for j, k in enumerate(keys)}
+        return read, [r if last[k] == j else -1 for j, (k, r) in enumerate(zip(keys, rows))]
+
+
+class HeadTrainer:
+    """``train_step(sup_img, sup_mask, qry_img, keys, qry_msk=...)`` of the reference's CANet Trainer (entry/canet.py:107-116,
+    130-140) -> (loss, softmax): ``CANetTrainer`` with the history in a device table addressed by ``HistorySlots``."""
+
+    def __new__(cls, model, **kw):
+        from ..train_canet import CANetTrainer
+
+        class _Trainer(CANetTrainer):
+            def __init__(self, model, **kw):
+                super().__init__(model, **kw)
+                self.history, self.table = HistorySlots(), None
+
+            def start_epoch(self, capacity, H, W):
+                """Forget every key; the table is allocated once per capacity and feature size (rows need no clearing: a key's
+                first episode reads slot -1)."""
+                h, w = self.model.feature_hw(H, W)
+                if self.table is None or self.table.shape[0] < capacity or tuple(self.table.shape[-2:]) != (h, w):
+                    self.table = torch.zeros((max(int(capacity), 1), 2, h, w), dtype=torch.float32, device=self.device)
+                self.history.clear()
+
+            def train_step(self, sup_img, sup_mask, qry_img, keys, qry_msk=None):
+                qry_msk = qry_msk.view(-1, *qry_msk.shape[-2:])
+                if not self.model.use_history:
+                    return super().train_step(sup_img, sup_mask, qry_img, qry_msk=qry_msk)
+                if self.table is None:
+                    self.start_epoch(len(keys), *sup_img.shape[-2:])
+                read, write = self.history.slots(list(keys))
+                if max(write) >= self.table.shape[0]:
+                    raise ValueError("the history table is too small for this epoch: call start_epoch with its key count")
+                rs = torch.tensor(read, dtype=torch.int32).to(self.device, non_blocking=True)
+                ws = torch.tensor(write, dtype=torch.int32).to(self.device, non_blocking=True)
+                return super().train_step(sup_img, sup_mask, qry_img, qry_msk=qry_msk, table=self.table, read_slot=rs, write_slot=ws)
+
+        return _Trainer(model, **kw)
+
+
+def head_train_batches(trainer, dcfg, shot, split, rank, steps_per_epoch, device):
+    """-> ``batches(epoch)`` for ``TrainingLoop``: ``((sup_img, sup_mask, qry_img, history keys), qry_msk)`` per step, from
+    synthetic repeating-key episodes; every epoch samples anew and clears the trainer's history."""
+    bs = dcfg["bs"]
+    data = SyntheticHistoryTrainEpisodes(steps_per_epoch * bs, dcfg["seed"] + 7919 * rank, shot, split, dcfg["height"], dcfg["width"],
+                                         dcfg["dataset"])
+
+    def batches(epoch):
+        data.sample_tasks()
+        keys = [data.history_key(i) for i in range(len(data))]
+        trainer.start_epoch(len(set(keys)), data.height, data.width)
+        for s in range(steps_per_epoch):
+            eps = [data.task(i) for i in range(s * bs, (s + 1) * bs)]
+            inputs = tuple(torch.cat([e[0][k] for e in eps]) for k in range(3))
+            yield inputs + (keys[s * bs:(s + 1) * bs],), torch.cat([e[1] for e in eps])
+    return batches
+
+
+@ex.command
+def train_head(_config, split, shot, query, seed, loss, sigma, exp_id, ckpt):
+    """``python -m pemp_amd.entry.canet train_head with split=0 [shot=5]``: CANet's training procedure (entry/canet.py:106-175)
+    for the reference's frozen trunk -- the head trains on the HIP path, per-epoch evaluation with the history loop,
+    ``ckpt.pth`` / ``bestckpt.pth`` (reference-loadable state_dicts) under ``<g.model_dir>/<tag>/<id>``."""
+    from .pemp_stage1 import run_training
+    if query != 1:
+        raise ValueError("CANet takes exactly one query per episode here (query=1)")
+    if _config["data"].get("base_dir"):
+        raise ValueError("train_head reads synthetic episodes only: the PASCAL-5i loader (data_kits.pascal_voc.load) has no training "
+                         "mode that names the query's history key; leave data.base_dir empty")
+
+    def make_trainer(logger, dev):
+        from ..core.snapshots import load_for_eval
+        model = ModelClass(logger)
+        load_for_eval(model, _config, exp_id, ckpt, logger, wgen_seed=WGEN_SEED)     # the frozen trunk comes from a checkpoint
+        return HeadTrainer(model, lr=_config["tr"]["lr"], device=dev, loss=loss, sigma=sigma)
+
+    return run_training(_config, NAME, make_trainer, lambda tr, dev: Evaluator(tr.model, device=dev), split, shot, seed, exp_id,
+                        val_episodes=eval_episodes, batches=head_train_batches)
 
 
 @ex.command

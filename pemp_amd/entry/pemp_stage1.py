@@ -386,11 +386,13 @@ def test(_config, split, shot, seed, exp_id, ckpt):
     return f"Loss: {loss:.4f}, mIoU: {np.mean(miou) * 100:.2f}, bIoU: {np.mean(biou) * 100:.2f}"
 
 
-def run_training(_config, name, make_trainer, make_evaluator, split, shot, seed, exp_id):
+def run_training(_config, name, make_trainer, make_evaluator, split, shot, seed, exp_id, val_episodes=None, batches=None):
     """Shared body of the ``train`` commands: process-group setup, broadcast of every model involved (the trained one and,
     for stage 2, the frozen stage-1 prior network), TrainingLoop on synthetic episodes.  Checkpoints go to a FRESH run
     directory ``<g.model_dir>/<tag>/<next id>`` (Sacred numbers its runs the same way); ``exp_id`` only ever names a run to
-    LOAD from."""
+    LOAD from.  A model with episode sources of its own (CANet: episodes with history keys) passes ``val_episodes(data cfg,
+    shot, split)`` and ``batches(trainer, data cfg, shot, split, rank, steps per epoch, device)`` in place of ``eval_episodes``
+    / ``train_batches``."""
     import logging
     import os
     from ..core.base_trainer import TrainingLoop
@@ -415,8 +417,11 @@ def run_training(_config, name, make_trainer, make_evaluator, split, shot, seed,
     if world > 1:
         dist.broadcast(run_id, 0)                             # rank 0 names the run
     loop = TrainingLoop(_config, trainer, make_evaluator(trainer, dev), logger, run_id=int(run_id.item()))
-    val = eval_episodes(d, shot, split)
-    batches = train_batches(d, shot, split, rank, loop.steps_per_epoch, dev)
+    val = (val_episodes or eval_episodes)(d, shot, split)
+    if batches is None:
+        batches = train_batches(d, shot, split, rank, loop.steps_per_epoch, dev)
+    else:
+        batches = batches(trainer, d, shot, split, rank, loop.steps_per_epoch, dev)
     hist = loop.start_training_loop(batches, val, num_classes(d["dataset"]), split)
     return f"best val mIoU {loop.best_iou * 100:.2f} at epoch {loop.best_epoch}; checkpoints in {loop.model_dir}" if hist else "no epochs"
 

@@ -3,8 +3,9 @@
 
 The module tree holds the reference's parameters under the reference's ``state_dict`` keys (tests/golden/
 state_keys_canet.json); the forward runs on ``pemp_amd.canet_engine`` (HIP kernels only).  Unlike the reference the
-constructor reads no ImageNet checkpoint: a trained model comes from ``load_weights`` / ``ckpt``.  Inference only: a
-``train()``-mode forward raises.  Beside the reference's ``forward`` there is a slot form for the evaluator
+constructor reads no ImageNet checkpoint: a trained model comes from ``load_weights`` / ``ckpt``.  The module's forward is
+inference only: a ``train()``-mode forward raises; the head trains through the explicit ``pemp_amd.train_canet.CANetTrainer``
+(``entry.canet``'s ``train_head``).  Beside the reference's ``forward`` there is a slot form for the evaluator
 (``lowres_slots`` / ``lowres_graphed_slots``): the same forward with the history read from, and the softmax written to, rows
 of a device-resident table."""
 from pathlib import Path

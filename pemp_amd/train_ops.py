@@ -525,3 +525,106 @@ def head_bwd(sup_feat, qry_feat, sup_mask, ctr, fwd_ws, protos, pred, target, st
                                      _stream()),
                "head_bwd")
     return dctr
+
+
+# -- CANet head training (csrc/canet_bwd.hip) ---------------------------------------------------------------------------------
+def canet_zterm_bwd(g, w_z, z, dw_z, dil, ws_cache=None):
+    """Adjoint of ``ops.canet_zterm``: g NHWC [B,h,w,Cout] (the gradient at layer55's pre-activation), ``w_z`` / ``dw_z`` the z
+    half of layer55's KRSC weight / weight gradient as [Cout,9,Cin] views of unit channel stride (column slices of the
+    [Cout,9,Cin_total] matrix), z [B,Cin] -> (G [B,9,Cout] clipped tap sums of g, dz [B,Cin]); writes ``dw_z``."""
+    lib = _lib.load()
+    _chk_dev(g, w_z, z, dw_z)
+    from .ops import _nhwc
+    ldg = _nhwc(g, "g")
+    b, h, w, cout = g.shape
+
+    def rows(t, name):
+        if t.dim() != 3 or t.dtype != torch.float32 or tuple(t.shape[:2]) != (cout, 9) or t.stride(2) != 1 or t.stride(0) != 9 * t.stride(1):
+            raise ValueError(f"canet_zterm_bwd: {name} must be a fp32 [Cout,9,Cin] view with unit channel stride and dense rows")
+        return t.stride(1)
+    ldw = rows(w_z, "w_z")
+    cin = w_z.shape[2]
+    if rows(dw_z, "dw_z") != ldw or dw_z.shape[2] != cin:
+        raise ValueError("canet_zterm_bwd: dw_z must be laid out as w_z")
+    if tuple(z.shape) != (b, cin) or not z.is_contiguous() or z.dtype != torch.float32:
+        raise ValueError(f"canet_zterm_bwd: z must be contiguous fp32 [{b},{cin}]")
+    G = torch.empty((b, 9, cout), dtype=torch.float32, device=g.device)
+    dz = torch.empty((b, cin), dtype=torch.float32, device=g.device)
+    ws = _ws(lib.pemp_canet_zterm_bwd_workspace_bytes(b, h, w, cout), g.device, ws_cache, ("zterm_bwd", b, h, w, cout))
+    _lib.check(lib.pemp_canet_zterm_bwd_f32(_p(g), ldg, _p(w_z), ldw, _p(z), _p(G), _p(dz), _p(dw_z), _p(ws), ws.numel(), b, h, w,
+                                            cin, cout, int(dil), _stream()), "canet_zterm_bwd")
+    return G, dz
+
+
+def canet_support_vector_bwd(dz, sup_mask, S, df):
+    """Adjoint of ``ops.canet_support_vector``: dz [B,C], sup_mask contiguous fp32 [B*S,2,H,W] -> writes df NHWC [B*S,h,w,C] (the
+    support rows of the layer5-output gradient) = dz m / (S (sum m + 1e-5))."""
+    lib = _lib.load()
+    _chk_dev(dz, sup_mask, df)
+    from .ops import _nhwc
+    ldd = _nhwc(df, "df")
+    n, h, w, c = df.shape
+    if sup_mask.dim() != 4 or n % S or sup_mask.shape[0] != n or sup_mask.shape[1] != 2 or not sup_mask.is_contiguous() \
+            or sup_mask.dtype != torch.float32:
+        raise ValueError(f"canet_support_vector_bwd: sup_mask must be contiguous fp32 [B*S,2,H,W] for df {tuple(df.shape)}, S={S}")
+    if tuple(dz.shape) != (n // S, c) or not dz.is_contiguous() or dz.dtype != torch.float32:
+        raise ValueError("canet_support_vector_bwd: dz must be contiguous fp32 [B,C]")
+    H, W = sup_mask.shape[-2:]
+    _lib.check(lib.pemp_canet_support_vector_bwd_f32(_p(dz), _p(sup_mask), _p(df), ldd, n // S, S, h, w, H, W, c, _stream()),
+               "canet_support_vector_bwd")
+    return df
+
+
+def canet_cls_bwd(dpred, x, weight, dx, dw, db, ws_cache=None):
+    """Backward of a 1x1 conv to 2 classes: dpred contiguous [B,2,h,w], x NHWC [B,h,w,C], weight contiguous [2,C] -> writes dx
+    NHWC [B,h,w,C], dw [2,C], db [2] (contiguous; e.g. the gradient views of the flat buffer)."""
+    lib = _lib.load()
+    _chk_dev(dpred, x, weight, dx, dw, db)
+    from .ops import _nhwc
+    ldx, lddx = _nhwc(x, "x"), _nhwc(dx, "dx")
+    b, h, w, c = x.shape
+    if tuple(dpred.shape) != (b, 2, h, w) or not dpred.is_contiguous() or dpred.dtype != torch.float32:
+        raise ValueError(f"canet_cls_bwd: dpred must be contiguous fp32 [{b},2,{h},{w}]")
+    if tuple(dx.shape) != tuple(x.shape):
+        raise ValueError("canet_cls_bwd: dx must have x's shape")
+    for t, n in ((weight, 2 * c), (dw, 2 * c), (db, 2)):
+        if t.numel() != n or not t.is_contiguous() or t.dtype != torch.float32:
+            raise ValueError("canet_cls_bwd: weight / dw must be contiguous fp32 [2,C], db contiguous fp32 [2]")
+    ws = _ws(lib.pemp_canet_cls_bwd_workspace_bytes(b * h * w, c), x.device, ws_cache, ("cls_bwd", b * h * w, c))
+    _lib.check(lib.pemp_canet_cls_bwd_f32(_p(dpred), _p(x), ldx, _p(weight), _p(dx), lddx, _p(dw), _p(db), _p(ws), ws.numel(),
+                                          b, h * w, c, _stream()), "canet_cls_bwd")
+    return dx
+
+
+def upsample_ce_bwd(pred=None, target=None, stats=None, weight=None, dlogits=None, out=None, low_hw=None):
+    """The first stage of ``head_bwd`` on its own -> dpred [B,2,h,w]: the adjoint of the bilinear (align_corners) upsample of
+    ``pred`` [B,2,h,w] to the target's size, applied to the mean-CE gradient from (pred, target int64 [B,Ho,Wo], stats of
+    ``ops.eval_tail``, optional ``weight`` map) or to a given ``dlogits`` [B,2,Ho,Wo] (then ``low_hw`` = (h, w))."""
+    lib = _lib.load()
+    _chk_dev(pred, target, stats, weight, dlogits, out)
+    if dlogits is not None:
+        if dlogits.dim() != 4 or dlogits.shape[1] != 2 or not dlogits.is_contiguous() or dlogits.dtype != torch.float32 or low_hw is None:
+            raise ValueError("upsample_ce_bwd: dlogits must be contiguous fp32 [B,2,Ho,Wo] and comes with low_hw")
+        b, (ho, wo), (h, w), dev = dlogits.shape[0], dlogits.shape[-2:], low_hw, dlogits.device
+        pred = target = stats = weight = None
+    else:
+        if pred is None or target is None or stats is None:
+            raise ValueError("upsample_ce_bwd: (pred, target, stats) or dlogits is needed")
+        if pred.dim() != 4 or pred.shape[1] != 2 or not pred.is_contiguous() or pred.dtype != torch.float32:
+            raise ValueError("upsample_ce_bwd: pred must be contiguous fp32 [B,2,h,w]")
+        b, _, h, w = pred.shape
+        if target.dtype != torch.int64 or not target.is_contiguous() or target.dim() != 3 or target.shape[0] != b:
+            raise ValueError("upsample_ce_bwd: target must be contiguous int64 [B,Ho,Wo]")
+        ho, wo = target.shape[-2:]
+        if stats.dtype != torch.float64 or tuple(stats.shape) != (b, 8) or not stats.is_contiguous():
+            raise ValueError("upsample_ce_bwd: stats must be the contiguous float64 [B,8] of eval_tail")
+        if weight is not None and (weight.dtype != torch.float32 or not weight.is_contiguous() or tuple(weight.shape) != (b, ho, wo)):
+            raise ValueError("upsample_ce_bwd: weight must be contiguous fp32 [B,Ho,Wo]")
+        dev = pred.device
+    if out is None:
+        out = torch.empty((b, 2, int(h), int(w)), dtype=torch.float32, device=dev)
+    if tuple(out.shape) != (b, 2, int(h), int(w)) or not out.is_contiguous() or out.dtype != torch.float32:
+        raise ValueError("upsample_ce_bwd: out must be contiguous fp32 [B,2,h,w]")
+    _lib.check(lib.pemp_upsample_ce_bwd_f32(_p(pred), _p(target), _p(weight), _p(stats), _p(dlogits), _p(out), b, int(h), int(w),
+                                            int(ho), int(wo), _stream()), "upsample_ce_bwd")
+    return out

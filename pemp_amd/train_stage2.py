@@ -159,16 +159,18 @@ class Stage2TrainEngine(Stage1TrainEngine):
     def _drop_bwd(dy, m):
         return dy if m is None else T.channel_scale(dy, m)
 
-    def _tail_forward(self, x, tape):
-        nimg, h, w, _ = x.shape
-        midc = self.midc
-        ya = conv2d(x, self.p0.fwd_params(relu=True))
-        xa, ma = self._drop(ya, nimg, ya.shape[-1], ("encoder.purifier.2",))
-        yb = conv2d(xa, self.p3.fwd_params(relu=True))
-        xb, mb = self._drop(yb, nimg, yb.shape[-1], ("encoder.purifier.5",))
+    #: reference names of the five branches' Dropout2d modules (the keys of ``self.draws``)
+    aspp_drop_names = tuple(f"encoder.purifier.6.aspp_{i}.2" for i in range(5))
+
+    def _aspp_forward(self, xb, tape, out_relu=False):
+        """ASPP without BatchNorm: global branch + four conv branches, each conv -> ReLU -> Dropout2d, and ``layer6`` over their
+        concatenation as two weight slices (the global branch enters as a per-image bias) -> layer6's output (``out_relu``: with a
+        ReLU, CANet's).  Needs ``self.aspp_conv``, ``self.l6``, ``self.midc``."""
+        nimg, h, w, _ = xb.shape
+        midc, names = self.midc, self.aspp_drop_names
         gap = ops.global_avgpool(xb)
         g0 = conv2d(gap.view(nimg, 1, 1, -1), self.aspp_conv[0].fwd_params(relu=True))
-        g0d, m0 = self._drop(g0, nimg, midc, ("encoder.purifier.6.aspp_0.2",))
+        g0d, m0 = self._drop(g0, nimg, midc, (names[0],))
         l6w = self.l6.weight
         w6 = self.flat.krsc(l6w)                                              # [512, 1280]
         w6g = ConvParams(w6[:, :midc].contiguous(), None, self.l6.bias.data, midc, l6w.shape[0], 1, 1, 1, 0, 1, midc, False, False)
@@ -177,14 +179,15 @@ class Stage2TrainEngine(Stage1TrainEngine):
         for i in range(1, 5):
             conv2d(xb, self.aspp_conv[i].fwd_params(relu=True), out=cat[..., (i - 1) * midc:i * midc])
         # the four branch Dropout2d layers at once
-        catd, ms = self._drop(cat, nimg, 4 * midc, tuple(f"encoder.purifier.6.aspp_{i}.2" for i in range(1, 5)))
-        w6m = ConvParams(w6[:, midc:].contiguous(), None, None, 4 * midc, l6w.shape[0], 1, 1, 1, 0, 1, 4 * midc, False, False)
+        catd, ms = self._drop(cat, nimg, 4 * midc, names[1:])
+        w6m = ConvParams(w6[:, midc:].contiguous(), None, None, 4 * midc, l6w.shape[0], 1, 1, 1, 0, 1, 4 * midc, False, out_relu)
         feat = conv2d(catd, w6m, shift_override=bias6.view(nimg, -1), per_image_shift=True)
-        tape.update(p0_in=x, ya=ya, ma=ma, xa=xa, yb=yb, mb=mb, xb=xb, gap=gap, g0=g0, m0=m0, g0d=g0d, cat=cat, catd=catd,
+        tape.update(xb=xb, gap=gap, g0=g0, m0=m0, g0d=g0d, cat=cat, catd=catd,
                     ms=ms, w6=w6, hw=(nimg, h, w))
         return feat
 
-    def _tail_backward(self, dfeat, up=None):
+    def _aspp_backward(self, dfeat):
+        """``dfeat``: the gradient at layer6's pre-activation -> the gradient at the ASPP's input."""
         tp, midc = self.tape, self.midc
         nimg, h, w = tp["hw"]
         l6w = self.l6.weight
@@ -214,6 +217,21 @@ class Stage2TrainEngine(Stage1TrainEngine):
         T.relu_bias_bwd(dg0, tp["g0"], g, relu=True, ws_cache=self.ws, out=conv0.conv.bias.grad)
         conv0.wgrad(tp["gap"].view(nimg, 1, 1, -1), g, self.ws)
         T.gap_bwd_add(conv2d(g, conv0.dgrad_params()).view(nimg, -1), dxb)
+        return dxb
+
+    def _tail_forward(self, x, tape):
+        nimg, h, w, _ = x.shape
+        ya = conv2d(x, self.p0.fwd_params(relu=True))
+        xa, ma = self._drop(ya, nimg, ya.shape[-1], ("encoder.purifier.2",))
+        yb = conv2d(xa, self.p3.fwd_params(relu=True))
+        xb, mb = self._drop(yb, nimg, yb.shape[-1], ("encoder.purifier.5",))
+        feat = self._aspp_forward(xb, tape)
+        tape.update(p0_in=x, ya=ya, ma=ma, xa=xa, yb=yb, mb=mb)
+        return feat
+
+    def _tail_backward(self, dfeat, up=None):
+        tp = self.tape
+        dxb = self._aspp_backward(dfeat)
         dxb = self._drop_bwd(dxb, tp["mb"])
         g = torch.empty_like(tp["yb"])
         T.relu_bias_bwd(dxb, tp["yb"], g, relu=True, ws_cache=self.ws, out=self.p3.conv.bias.grad)
