@@ -35,6 +35,9 @@ extern "C" {
 #define PEMP_CONV_STEM4 4u         /* input is NHWC4, K axis = taps x 4 channels (7x7 stem) */
 #define PEMP_CONV_POOL3S2 8u       /* y = max_pool2d(act(...), 3, stride 2, pad 1, ceil_mode) of the 7x7 / 2 / 3 stem, in one
                                       launch (pemp_conv2d_nhwc_f32 only; see "Fused stem" below)                              */
+#define PEMP_CONV_OUT_SPLIT3 16u   /* y is written PRE-SPLIT: bf16 [M][Cout / 32][3][32], the split3 pieces of the fp32 result
+                                      (see "Pre-split activations" below)                                                     */
+#define PEMP_CONV_IN_SPLIT3 32u    /* x is such a tensor (tile ids 146 / 149 only)                                            */
 
 typedef struct pemp_conv_desc {
     int32_t N, H, W;        /* input images, input spatial size                                  */
@@ -67,6 +70,7 @@ int pemp_abi_version(void);
  *     4x  41..44, 46    split3: fp32 operands as three bf16 pieces on v_mfma_f32_32x32x16_bf16 (pemp_pack_split3_bf16);
  *         47, 49        persistent forms of 43 and 46: a resident grid walks the tiles
  *     5x  51, 52, 54, 56  split3 with the last round split along K
+ *    14x  146, 149        split3 with pre-split ACTIVATIONS (PEMP_CONV_IN_SPLIT3): 46 and 49 without the split in the K loop
  *     7x  71, 72          split3, activation-stationary (1x1 convs without padding, Kpad <= 256, pemp_conv2d_nhwc_f32 only): a
  *                       block of 4 waves keeps 128 output rows x K of split activations in registers and walks ALL of Cout, 128
  *                       (71) or 64 (72) columns at a time, with only the packed weights streaming through LDS; no padding value,
@@ -136,6 +140,18 @@ int pemp_conv2d_group_nhwc_f32(int n, const pemp_conv_desc* d, const float* cons
  * of 43 (64 x 64) and 46 (256 x 128).  The grid is the number of blocks resident at once (at most the tile count) and each block
  * walks a fixed sequence of tiles, issuing the next tile's first operand DMA before the current tile's epilogue; same tiles, same
  * K order, same epilogue arithmetic: bit-identical to 41..46.  (41's shape has no such form: it would spill at 2 waves / SIMD.)
+ * Pre-split activations (pemp_conv2d_nhwc_f32 / _padv_ only).  A conv whose output has ONE reader, a multi-tap split3 conv, can
+ * hand it over already split, so that the reader's K loop has no splitting left to do:
+ *   PEMP_CONV_OUT_SPLIT3 (producer; ids 41..44, 46, 47, 49): after affine (+ ReLU) every output value is split with the arithmetic
+ *   of pemp_pack_split3_bf16 and `y` is written as bf16 [M][Cout / 32][3][32] (M * Cout * 6 bytes): per pixel and 32-channel group
+ *   the planes h, m, l -- h + m + l is the fp32 value the same id writes without the flag, exactly.  ldy == Cout; no residual,
+ *   split-K, workspace, grouped, panel (71 / 72) or fused-stem form.  The persistent ids 47 / 49 / 149 run as the ids they walk
+ *   (43 / 46 / 146: same tiles, same results) -- their kernels have no registers left for the split.
+ *   PEMP_CONV_IN_SPLIT3 (consumer; ids 146 = the form of 46, 149 = the form of 49, and no other id): `x` is such a tensor
+ *   (ldx == Cin, Cin % 32 == 0), a padding value is the [Cin / 32][3][32] bf16 split of the fp32 vector, behind x like the fp32
+ *   one.  Multi-tap convs only; no per-image shift, split-K or workspace; Cout % 128 == 0.  Same MFMA order and epilogue as
+ *   41..49 on the same pieces: bit-identical to them on the fp32 tensor.  (No 128 x 128 form: its A tile of 96 KiB would leave one
+ *   block per CU.)
  * pemp_pack_split3_bf16: [Cout][Kpad] fp32 (Kpad % 32 == 0) -> [Cout][Kpad / 32][3][32] bf16 (Cout * Kpad * 6 bytes): per row and
  * 32-channel K step the h, m and l planes, channel order unchanged.                                                           */
 int pemp_pack_split3_bf16(const float* w, void* out, int cout, int kpad, void* stream);

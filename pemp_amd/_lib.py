@@ -35,6 +35,8 @@ CONV_RELU = 1
 CONV_SHIFT_PER_IMAGE = 2
 CONV_STEM4 = 4
 CONV_POOL3S2 = 8
+CONV_OUT_SPLIT3 = 16
+CONV_IN_SPLIT3 = 32
 
 #: every symbol include/pemp_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {

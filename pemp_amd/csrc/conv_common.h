@@ -121,7 +121,56 @@ __device__ __forceinline__ int xcd_tile_order(int bid, int nblk) {
 // pemp_conv2d_dropblock_nhwc_f32 only: it keeps the four instructions out of every other epilogue.  (Round 4 made it one because
 // the run-time branch "broke" one kernel; the cause was an unrelated wait-state hazard in conv_dma2.hip's inline asm that the
 // branch merely re-scheduled into view -- DESIGN.md section 4, scratch/t31/README.md.)
-template <int TM, int TN, int NPRE, int EPI = 0, bool DB = false>
+// PEMP_CONV_OUT_SPLIT3: the 32 x 32 sub-tile in the wave's patch S (rows m_base .., channels n32 ..) goes out PRE-SPLIT -- bf16
+// [M][Cout / 32][3][32], per row and 32-channel group the planes h, m, l of split3_bf16 -- for a split3 conv that reads it with
+// PEMP_CONV_IN_SPLIT3 (conv_dma2.hip, A3).  A lane owns 8 consecutive channels of one row (4 lanes per row, 16 rows per pass), so
+// that every plane goes out as one 16-byte store and a row's 192 bytes are written by 4 neighbouring lanes.  The value that is
+// split is conv_epilogue_lds_pre's, statement for statement (no residual: the entry refuses one).
+__device__ __forceinline__ void conv_store_split3(const ConvArgs& a, const float* S, int m_base, int n32, int lane) {
+    const bool relu = a.flags & PEMP_CONV_RELU;
+    const bool per_img = a.flags & PEMP_CONV_SHIFT_PER_IMAGE;
+    const int r4 = lane >> 2, c8 = (lane & 3) * 8, n = n32 + c8;
+    v4f sc[2] = {{1.f, 1.f, 1.f, 1.f}, {1.f, 1.f, 1.f, 1.f}}, sh[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+        if (a.scale) sc[u] = *(const v4f*)(a.scale + n + 4 * u);
+        if (a.shift && !per_img) sh[u] = *(const v4f*)(a.shift + n + 4 * u);
+    }
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const int row = r4 + 16 * i;
+        const int m = m_base + row;
+        v4f o[2];
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const v4f v = *(const v4f*)(S + row * 32 + c8 + 4 * u);
+            v4f add = sh[u];
+            if (per_img && m < a.M) add += *(const v4f*)(a.shift + (size_t)(m / a.HoWo) * a.Cout + n + 4 * u);
+            o[u].x = __builtin_fmaf(v.x, sc[u].x, add.x);
+            o[u].y = __builtin_fmaf(v.y, sc[u].y, add.y);
+            o[u].z = __builtin_fmaf(v.z, sc[u].z, add.z);
+            o[u].w = __builtin_fmaf(v.w, sc[u].w, add.w);
+            if (relu) {
+                o[u].x = fmaxf(o[u].x, 0.f);
+                o[u].y = fmaxf(o[u].y, 0.f);
+                o[u].z = fmaxf(o[u].z, 0.f);
+                o[u].w = fmaxf(o[u].w, 0.f);
+            }
+        }
+        if (m < a.M) {
+            bf16x8 h, md, l;
+            split3_bf16(o[0], o[1], h, md, l);
+            unsigned short* y = (unsigned short*)a.y + ((size_t)m * (a.Cout >> 5) + (n32 >> 5)) * 96 + c8;
+            *(bf16x8*)y = h;
+            *(bf16x8*)(y + 32) = md;
+            *(bf16x8*)(y + 64) = l;
+        }
+    }
+}
+
+// OS3: the kernel may be asked for a pre-split output (PEMP_CONV_OUT_SPLIT3: a run-time, wave-uniform branch per sub-tile -- the
+// split3 kernels only, so that the fp32-chain instantiations do not carry it).
+template <int TM, int TN, int NPRE, int EPI = 0, bool DB = false, bool OS3 = false>
 __device__ __forceinline__ void conv_epilogue_lds_pre(const ConvArgs& a, f32x16 (&acc)[TM][TN], float* S, int m_base,
                                                       int n_base, int lane, const v4f (&pre)[NPRE], float* R = nullptr) {
     constexpr bool PRE = NPRE == TM * TN * 4;       // (an array of 1 = "no prefetched residual": registers, never scratch)
@@ -166,6 +215,8 @@ __device__ __forceinline__ void conv_epilogue_lds_pre(const ConvArgs& a, f32x16 
             for (int e = 0; e < 16; ++e) S[((e & 3) + 8 * (e >> 2) + 4 * lh) * 32 + lr] = acc[mi][ni][e];
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // this wave's writes have landed (DS is in-order per wave)
             v4f s1 = {0.f, 0.f, 0.f, 0.f}, s2 = {0.f, 0.f, 0.f, 0.f};
+            if (OS3 && EPI == 0 && !DB && (a.flags & PEMP_CONV_OUT_SPLIT3)) conv_store_split3(a, S, m_base + mi * 32, n_base + ni * 32, lane);
+            else
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const int row = rr + 8 * i;
@@ -248,12 +299,12 @@ __device__ __forceinline__ void conv_stats_store(const ConvArgs& a, const float*
     }
 }
 
-template <int TM, int TN, bool DB = false>
+template <int TM, int TN, bool DB = false, bool OS3 = false>
 __device__ __forceinline__ void conv_epilogue_lds(const ConvArgs& a, f32x16 (&acc)[TM][TN], float* S, int m_base,
                                                   int n_base, int lane) {
     const v4f none[1] = {{0.f, 0.f, 0.f, 0.f}};
     static_assert(TM * TN * 4 != 1, "tile");
-    conv_epilogue_lds_pre<TM, TN, 1, 0, DB>(a, acc, S, m_base, n_base, lane, none);
+    conv_epilogue_lds_pre<TM, TN, 1, 0, DB, OS3>(a, acc, S, m_base, n_base, lane, none);
 }
 
 // Epilogue of the 16-row wave tiles (conv_dma2.hip, R16): TN accumulators of 16 x 16 (rows 4 (lane >> 4) + e, column lane & 15) go
@@ -321,6 +372,8 @@ int launch_conv_dma2_split3(int shape, ConvArgs a, void* ws, size_t ws_bytes, bo
 int launch_conv_dma2_group_split3(int shape, ConvGroupArgs& g, hipStream_t st);
 // its persistent forms (shapes 3 and 6): a resident grid walks the tiles
 int launch_conv_dma2_split3_persist(int shape, const ConvArgs& a, hipStream_t st);
+// ... and the forms whose activations come pre-split (PEMP_CONV_IN_SPLIT3; shape 6 only), one tile per block or persistent
+int launch_conv_dma2_split3_pre(int shape, bool persistent, const ConvArgs& a, hipStream_t st);
 // conv_panel.hip: the activation-stationary split3 form of short-K 1x1 convs (shapes 1 and 2 = 128 / 64 columns at a time)
 bool conv_panel_supported(const ConvArgs& a);
 int launch_conv_panel(int shape, const ConvArgs& a, hipStream_t st);

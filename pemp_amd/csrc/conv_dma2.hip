@@ -22,6 +22,7 @@
 // activations in the same 2 GiB window: the in-image and the out-of-image lanes of a piece must come through ONE
 // descriptor (an exec-masked LDS-DMA does not leave the inactive lanes' 16-byte slots alone -- tried: two masked DMAs per
 // piece give wrong data -- so a piece cannot be assembled from two).
+#include <type_traits>
 #include "conv_tiles.h"
 
 #ifndef PEMP_SK_ACQUIRE
@@ -56,8 +57,14 @@ typedef __attribute__((address_space(3))) void* lptr_t;
 // A K step is two K16 slices of v_mfma_f32_32x32x16_bf16 (lane half lh of slice s: channels 16 s + 8 lh .. + 7); every
 // accumulator sees the slices in ascending K order, so all unsplit S3 variants are bit-identical to each other (not to the
 // fp32-chain variants: a different, equally fp32-accurate, rounding sequence).
+// A3 (tile ids 146 / 149, PEMP_CONV_IN_SPLIT3): S3 whose ACTIVATIONS come pre-split as well -- written by the producer conv's
+// epilogue (PEMP_CONV_OUT_SPLIT3, conv_common.h) in the layout of the packed weights: per pixel and 32-channel K step three
+// 64-byte planes h, m, l.  The A path is then the B path: 192 bytes per row and K step in LDS (12 quads, the B swizzle), DMA'd with
+// the same tap / stride / dilation arithmetic at 6 bytes per element (out-of-image lanes read zeros -- three zero planes -- or the
+// pre-split padding vector), three 16-byte fragment reads per half step that go straight into the MFMAs.  No split3_bf16 in the K
+// loop; MFMA order, accumulators and epilogue are S3's, and the pieces are those split3_bf16 would have made: bit-identical.
 template <int BM, int BN, int WGM, int NW, bool PADV, int EPI = 0, bool SK = false, bool BF16 = false, bool DB = false, bool R16 = false,
-          bool S3 = false>
+          bool S3 = false, bool A3 = false>
 __device__ __forceinline__ void conv_dma2_body(const ConvArgs& a, const int bid, const int nblk) {
 #if defined(__HIP_DEVICE_COMPILE__)     // the host pass only needs the launch stub (buffer-resource builtins / "s" asm operands are device-only)
     constexpr int WGN = NW / WGM;
@@ -65,18 +72,21 @@ __device__ __forceinline__ void conv_dma2_body(const ConvArgs& a, const int bid,
     constexpr int WM = BM / WGM, WN = BN / WGN;
     static_assert(!R16 || (WM == 16 && WN % 16 == 0 && EPI == 0 && !SK && !BF16 && !DB), "R16: 16-row wave tiles, plain epilogue only");
     static_assert(!S3 || (EPI == 0 && !BF16 && !DB && !R16), "S3: plain epilogue, fp32 operands");
+    static_assert(!A3 || (S3 && !SK && (BM * 12) % (NW * 64) == 0), "A3: an unsplit S3 form, whole A DMA rounds");
     constexpr int TM = R16 ? 1 : WM / 32, TN = R16 ? WN / 16 : WN / 32;      // R16: TN counts 16-column MFMA tiles
     constexpr int BQ = S3 ? 12 : 8;             // 16-byte quads of B per row and K step in LDS
     static_assert(!S3 || (BN * BQ) % (NW * 64) == 0, "S3: whole B DMA rounds");
-    constexpr int AL = BM / RPI, BL = S3 ? BN * BQ / (NW * 64) : BN / RPI; // DMA wave-instructions per thread per K step
+    constexpr int AQ = A3 ? 12 : 8;             // ... of A
+    constexpr int XB = A3 ? 6 : 4;              // bytes per activation element in memory
+    constexpr int AL = A3 ? BM * AQ / (NW * 64) : BM / RPI, BL = S3 ? BN * BQ / (NW * 64) : BN / RPI; // DMA wave-instructions per thread per K step
     // per quarter step (S3: per half step): MFMAs, fragment reads; DMAs per step
-    constexpr int NMF = S3 ? 6 * TM * TN : R16 ? 2 * TN : TM * TN * (BF16 ? 1 : 4), NDS = S3 ? 2 * TM + 3 * TN : R16 ? 1 + TN : TM + TN,
+    constexpr int NMF = S3 ? 6 * TM * TN : R16 ? 2 * TN : TM * TN * (BF16 ? 1 : 4), NDS = S3 ? (A3 ? 3 : 2) * TM + 3 * TN : R16 ? 1 + TN : TM + TN,
                   NDMA = AL + BL;
     constexpr int PER = (NDS + NDMA + NMF - 1) / NMF;
 
     extern __shared__ __attribute__((aligned(16))) v4f smem[];
-    v4f* As = smem;                      // [2][BM][8]
-    v4f* Bs = smem + 2 * BM * 8;         // [2][BN][BQ]
+    v4f* As = smem;                      // [2][BM][AQ]
+    v4f* Bs = smem + 2 * BM * AQ;        // [2][BN][BQ]
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -115,18 +125,28 @@ __device__ __forceinline__ void conv_dma2_body(const ConvArgs& a, const int bid,
 
     const int bias_pix = a.pad * a.W + a.pad;
     const __amdgpu_buffer_rsrc_t rx =
-        __builtin_amdgcn_make_buffer_rsrc((void*)(a.x - (ptrdiff_t)bias_pix * a.ldx), 0, 0x80000000u, 0x00020000);
+        __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)a.x - (ptrdiff_t)bias_pix * a.ldx * XB), 0, 0x80000000u, 0x00020000);
     const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void*)a.w, 0, 0x80000000u, 0x00020000);
 
     // PADV (ops.fold_input_affine: a BatchNorm in front of a zero-padded conv): out-of-image taps read a per-channel VALUE
     // instead of zero.  One descriptor must serve both kinds of lane, so this variant needs the [Cin] vector INSIDE the
     // activation descriptor's range, behind the tensor (the engine allocates it there); an out-of-image lane then gets
     // the offset of its channel quad of that vector, minus the tap displacement the SGPR offset is about to add.
-    const unsigned padv_off = PADV ? (unsigned)((const char*)a.padv - (const char*)(a.x - (ptrdiff_t)bias_pix * a.ldx)) + sq * 16 : 0x80000000u;
-    unsigned a_voff[AL], a_inv[AL], b_voff[BL];
+    const unsigned padv_off = PADV ? (unsigned)((const char*)a.padv - ((const char*)a.x - (ptrdiff_t)bias_pix * a.ldx * XB)) + (A3 ? 0 : sq * 16) : 0x80000000u;
+    // A3: six rows per thread instead of four -- the tap masks of two rows share a register (<= 16 taps), and the lane's (swizzled)
+    // quad inside the row's 192 bytes, which differs per DMA round, is a_voff mod 192 (PADV reads it back from there)
+    constexpr int AINV = A3 ? AL / 2 : AL;
+    static_assert(!A3 || AL % 2 == 0, "A3: tap masks in pairs");
+    unsigned a_voff[AL], a_inv[AINV], b_voff[BL];
 #pragma unroll
     for (int i = 0; i < AL; ++i) {
-        const int m = m0 + r + RPI * i;
+        int arow_ = r + RPI * i, asrc_ = sq * 16;
+        if constexpr (A3) {     // LDS quad q of the A tile = row q / 12, position q % 12: the B tile's layout and swizzle
+            const int q = i * NW * 64 + tid, pos = q % 12;
+            arow_ = q / 12;
+            asrc_ = ((pos & ~3) | ((pos & 3) ^ ((arow_ >> 2) & 3))) * 16;
+        }
+        const int m = m0 + arow_;
         const bool ok = m < a.M;
         const int mm = ok ? m : 0;
         const int img = mm / a.HoWo;
@@ -135,7 +155,8 @@ __device__ __forceinline__ void conv_dma2_body(const ConvArgs& a, const int bid,
         const int wo = rem - ho * a.Wo;
         const int hi0 = ho * a.stride - a.pad;
         const int wi0 = wo * a.stride - a.pad;
-        a_voff[i] = (unsigned)(((img * a.H + hi0) * a.W + wi0 + bias_pix) * a.ldx + sq * 4) * 4u;
+        a_voff[i] = A3 ? (unsigned)(((img * a.H + hi0) * a.W + wi0 + bias_pix) * a.ldx * 6 + asrc_)
+                           : (unsigned)(((img * a.H + hi0) * a.W + wi0 + bias_pix) * a.ldx + sq * 4) * 4u;
         unsigned mask = 0;
         int kh = 0, kw = 0;
         for (int t = 0; t < a.ntaps; ++t) {
@@ -146,7 +167,9 @@ __device__ __forceinline__ void conv_dma2_body(const ConvArgs& a, const int bid,
                 ++kh;
             }
         }
-        a_inv[i] = ~mask;
+        if constexpr (!A3) a_inv[i] = ~mask;
+        else if (i & 1) a_inv[i >> 1] |= ~mask << 16;
+        else a_inv[i >> 1] = ~mask & 0xFFFFu;
     }
 #pragma unroll
     for (int i = 0; i < BL; ++i) {
@@ -173,18 +196,19 @@ __device__ __forceinline__ void conv_dma2_body(const ConvArgs& a, const int bid,
             kw_i = __builtin_amdgcn_readfirstlane(tap0 - kh0 * a.KW);
         }
     }
-    const int tapw = a.dil * a.ldx * 4, taph = a.dil * a.W * a.ldx * 4;     // byte displacement of one tap step
+    const int tapw = a.dil * a.ldx * XB, taph = a.dil * a.W * a.ldx * XB;     // byte displacement of one tap step
 
 #define PEMP_DMA2(buf_)                                                                                           \
     do {                                                                                                          \
-        v4f* Ad_ = As + (buf_) * BM * 8 + wave * 64;                                                              \
+        v4f* Ad_ = As + (buf_) * BM * AQ + wave * 64;                                                             \
         v4f* Bd_ = Bs + (buf_) * BN * BQ + wave * 64;                                                             \
-        const int sa_ = kh_i * taph + kw_i * tapw + cb * 128;                                                     \
+        const int sa_ = kh_i * taph + kw_i * tapw + cb * (32 * XB);                                               \
         const int sb_ = (tap * a.Cin + cb * 32) * (S3 ? 6 : 4);                                                   \
         const int sh_ = 31 - tap;                                                                                 \
         const unsigned oob_ = PADV ? padv_off - (unsigned)(kh_i * taph + kw_i * tapw) : 0x80000000u;              \
         _Pragma("unroll") for (int i = 0; i < AL; ++i) {                                                          \
-            const unsigned vo_ = ((int)(a_inv[i] << sh_) < 0) ? oob_ : a_voff[i];                                 \
+            const bool inv_ = A3 ? (int)(a_inv[i >> 1] << (sh_ - ((i & 1) ? 16 : 0))) < 0 : (int)(a_inv[A3 ? 0 : i] << sh_) < 0;  \
+            const unsigned vo_ = inv_ ? oob_ + (A3 && PADV ? a_voff[i] % 192u : 0u) : a_voff[i];                  \
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (lptr_t)(Ad_ + i * RPI * 8), 16, vo_, sa_, 0, 0);        \
         }                                                                                                         \
         _Pragma("unroll") for (int i = 0; i < BL; ++i)                                                            \
@@ -267,16 +291,22 @@ __device__ __forceinline__ void conv_dma2_body(const ConvArgs& a, const int bid,
     const int arow16 = (wm0 + r16) * 32 + (g16 >> 1), brow16 = (wn0 + r16) * 32 + (g16 >> 1);     // in floats
     float a16[2][2], b16[2][R16 ? TN : 1][2];
     // S3: half step j of a lane: fp32 quads 4 j + 2 lh and 4 j + 2 lh + 1 of its A rows, quad 2 j + lh of each weight plane
-    v4f af3[2][S3 ? TM : 1][2], bf3[2][S3 ? TN : 1][3];
-    const int brow3 = (wn0 + lr) * 12, bsw3 = (lr >> 2) & 3;
+    v4f af3[2][S3 && !A3 ? TM : 1][2], bf3[2][S3 ? TN : 1][3];
+    v4f aq3[2][A3 ? TM : 1][3];          // A3: the three planes of the A rows' quad, like bf3
+    const int brow3 = (wn0 + lr) * 12, bsw3 = (lr >> 2) & 3, arow3 = (wm0 + lr) * 12;
 
 #define PEMP_READ(dst_, buf_, j_)                                                                                 \
     do {                                                                                                          \
-        const v4f* Ab_ = As + (buf_) * BM * 8;                                                                    \
+        const v4f* Ab_ = As + (buf_) * BM * AQ;                                                                   \
         const v4f* Bb_ = Bs + (buf_) * BN * BQ;                                                                   \
         if constexpr (S3) {                                                                                       \
             const int p0_ = (4 * (j_) + 2 * lh) ^ rsw, p1_ = (4 * (j_) + 2 * lh + 1) ^ rsw;                       \
             const int pb_ = (2 * (j_) + lh) ^ bsw3;                                                               \
+            if constexpr (A3) {         /* the planes of the row's quad 2 j + lh, as for B (wm0 % 32 == 0: same swizzle) */ \
+                _Pragma("unroll") for (int mi = 0; mi < TM; ++mi)                                                 \
+                    _Pragma("unroll") for (int pl = 0; pl < 3; ++pl)                                              \
+                        aq3[dst_][mi][pl] = Ab_[arow3 + mi * 32 * 12 + pl * 4 + pb_];                             \
+            } else                                                                                                \
             _Pragma("unroll") for (int mi = 0; mi < TM; ++mi) {                                                   \
                 af3[dst_][mi][0] = Ab_[arow + mi * 256 + p0_];                                                    \
                 af3[dst_][mi][1] = Ab_[arow + mi * 256 + p1_];                                                    \
@@ -305,8 +335,13 @@ __device__ __forceinline__ void conv_dma2_body(const ConvArgs& a, const int bid,
     do {                                                                                                          \
         if constexpr (S3) {                                                                                       \
             bf16x8 ah_[TM], am_[TM], al_[TM];                                                                     \
-            _Pragma("unroll") for (int mi = 0; mi < TM; ++mi)                                                     \
-                split3_bf16(af3[src_][mi][0], af3[src_][mi][1], ah_[mi], am_[mi], al_[mi]);                       \
+            _Pragma("unroll") for (int mi = 0; mi < TM; ++mi) {                                                   \
+                if constexpr (A3) {                                                                               \
+                    ah_[mi] = __builtin_bit_cast(bf16x8, aq3[src_][mi][0]);                                       \
+                    am_[mi] = __builtin_bit_cast(bf16x8, aq3[src_][mi][1]);                                       \
+                    al_[mi] = __builtin_bit_cast(bf16x8, aq3[src_][mi][2]);                                       \
+                } else split3_bf16(af3[src_][mi][0], af3[src_][mi][1], ah_[mi], am_[mi], al_[mi]);                \
+            }                                                                                                     \
             _Pragma("unroll") for (int mi = 0; mi < TM; ++mi) _Pragma("unroll") for (int ni = 0; ni < TN; ++ni) { \
                 const bf16x8 bh_ = __builtin_bit_cast(bf16x8, bf3[src_][ni][0]);                                  \
                 const bf16x8 bm_ = __builtin_bit_cast(bf16x8, bf3[src_][ni][1]);                                  \
@@ -529,11 +564,11 @@ __device__ __forceinline__ void conv_dma2_body(const ConvArgs& a, const int bid,
     static_assert(EPI == 0 || NW * 1024 + NW * TN * 512 <= 64 * (BM + BN), "LDS: statistics area");
     static_assert(NW * 1024 <= 64 * (BM + BN), "LDS: one 4 KB transpose patch per wave");
     if constexpr (R16) conv_epilogue_r16<TN>(a, acc16, (float*)smem + wave * 1024, m0 + wm0, n0 + wn0, lane);
-    else if constexpr (PRE) conv_epilogue_lds_pre<TM, TN, TM * TN * 4, EPI, DB>(a, acc, (float*)smem + wave * 1024, m0 + wm0, n0 + wn0, lane, rpre, Rall + wave * TN * 512);
+    else if constexpr (PRE) conv_epilogue_lds_pre<TM, TN, TM * TN * 4, EPI, DB, S3>(a, acc, (float*)smem + wave * 1024, m0 + wm0, n0 + wn0, lane, rpre, Rall + wave * TN * 512);
     else if constexpr (EPI != 0) {
         const v4f none[1] = {{0.f, 0.f, 0.f, 0.f}};
         conv_epilogue_lds_pre<TM, TN, 1, EPI>(a, acc, (float*)smem + wave * 1024, m0 + wm0, n0 + wn0, lane, none, Rall + wave * TN * 512);
-    } else conv_epilogue_lds<TM, TN, DB>(a, acc, (float*)smem + wave * 1024, m0 + wm0, n0 + wn0, lane);
+    } else conv_epilogue_lds<TM, TN, DB, S3>(a, acc, (float*)smem + wave * 1024, m0 + wm0, n0 + wn0, lane);
     if constexpr (EPI != 0) {
         __syncthreads();
         conv_stats_store<BN, WGM, NW, TN>(a, Rall, bm, n0, tid);
@@ -612,7 +647,7 @@ __device__ __forceinline__ void conv_epilogue_s3p(const ConvArgs& a, f32x16 (&ac
     }
 }
 
-template <int BM, int BN, int WGM, int NW, bool PADV>
+template <int BM, int BN, int WGM, int NW, bool PADV, bool A3 = false>
 __device__ __forceinline__ void conv_dma2_s3p_body(const ConvArgs& a) {
 #if defined(__HIP_DEVICE_COMPILE__)
     constexpr bool S3 = true, R16 = false, BF16 = false;       // the K-loop macros' switches
@@ -622,16 +657,18 @@ __device__ __forceinline__ void conv_dma2_s3p_body(const ConvArgs& a) {
     constexpr int TM = WM / 32, TN = WN / 32;
     constexpr int BQ = 12;
     static_assert((BN * BQ) % (NW * 64) == 0, "S3: whole B DMA rounds");
-    constexpr int AL = BM / RPI, BL = BN * BQ / (NW * 64);
-    constexpr int NMF = 6 * TM * TN, NDS = 2 * TM + 3 * TN, NDMA = AL + BL;
+    constexpr int AQ = A3 ? 12 : 8, XB = A3 ? 6 : 4;
+    static_assert(!A3 || (BM * 12) % (NW * 64) == 0, "A3: whole A DMA rounds");
+    constexpr int AL = A3 ? BM * AQ / (NW * 64) : BM / RPI, BL = BN * BQ / (NW * 64);
+    constexpr int NMF = 6 * TM * TN, NDS = (A3 ? 3 : 2) * TM + 3 * TN, NDMA = AL + BL;
     constexpr int PER = (NDS + NDMA + NMF - 1) / NMF;
     constexpr int NST = TM * TN * 4;            // epilogue stores per thread of a wave tile inside the output
     static_assert(NDMA + NST <= 63, "vmcnt range");
     static_assert(NW <= BM / 32 + 3 * BN / 64, "one 4 KB transpose patch per wave inside ONE stage buffer");
 
     extern __shared__ __attribute__((aligned(16))) v4f smem[];
-    v4f* As = smem;                      // [2][BM][8]
-    v4f* Bs = smem + 2 * BM * 8;         // [2][BN][BQ]
+    v4f* As = smem;                      // [2][BM][AQ]
+    v4f* Bs = smem + 2 * BM * AQ;        // [2][BN][BQ]
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -657,15 +694,25 @@ __device__ __forceinline__ void conv_dma2_s3p_body(const ConvArgs& a) {
     const int sq = p ^ ((r >> 1) & 7);
     const int bias_pix = a.pad * a.W + a.pad;
     const __amdgpu_buffer_rsrc_t rx =
-        __builtin_amdgcn_make_buffer_rsrc((void*)(a.x - (ptrdiff_t)bias_pix * a.ldx), 0, 0x80000000u, 0x00020000);
+        __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)a.x - (ptrdiff_t)bias_pix * a.ldx * XB), 0, 0x80000000u, 0x00020000);
     const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void*)a.w, 0, 0x80000000u, 0x00020000);
-    const unsigned padv_off = PADV ? (unsigned)((const char*)a.padv - (const char*)(a.x - (ptrdiff_t)bias_pix * a.ldx)) + sq * 16 : 0x80000000u;
-    unsigned a_voff[AL], a_inv[AL], b_voff[BL];
+    const unsigned padv_off = PADV ? (unsigned)((const char*)a.padv - ((const char*)a.x - (ptrdiff_t)bias_pix * a.ldx * XB)) + (A3 ? 0 : sq * 16) : 0x80000000u;
+    // A3: six rows per thread instead of four -- the tap masks of two rows share a register (<= 16 taps), and the lane's (swizzled)
+    // quad inside the row's 192 bytes, which differs per DMA round, is a_voff mod 192 (PADV reads it back from there)
+    constexpr int AINV = A3 ? AL / 2 : AL;
+    static_assert(!A3 || AL % 2 == 0, "A3: tap masks in pairs");
+    unsigned a_voff[AL], a_inv[AINV], b_voff[BL];
     // per-row byte offsets and tap masks of the tile at (m0_, n0_): conv_dma2_body's, expression for expression
     auto offsets = [&](const int m0_, const int n0_) {
 #pragma unroll
         for (int i = 0; i < AL; ++i) {
-            const int m = m0_ + r + RPI * i;
+            int arow_ = r + RPI * i, asrc_ = sq * 16;
+            if constexpr (A3) {     // LDS quad q of the A tile = row q / 12, position q % 12: the B tile's layout and swizzle
+                const int q = i * NW * 64 + tid, pos = q % 12;
+                arow_ = q / 12;
+                asrc_ = ((pos & ~3) | ((pos & 3) ^ ((arow_ >> 2) & 3))) * 16;
+            }
+            const int m = m0_ + arow_;
             const bool ok = m < a.M;
             const int mm = ok ? m : 0;
             const int img = mm / a.HoWo;
@@ -674,7 +721,8 @@ __device__ __forceinline__ void conv_dma2_s3p_body(const ConvArgs& a) {
             const int wo = rem - ho * a.Wo;
             const int hi0 = ho * a.stride - a.pad;
             const int wi0 = wo * a.stride - a.pad;
-            a_voff[i] = (unsigned)(((img * a.H + hi0) * a.W + wi0 + bias_pix) * a.ldx + sq * 4) * 4u;
+            a_voff[i] = A3 ? (unsigned)(((img * a.H + hi0) * a.W + wi0 + bias_pix) * a.ldx * 6 + asrc_)
+                           : (unsigned)(((img * a.H + hi0) * a.W + wi0 + bias_pix) * a.ldx + sq * 4) * 4u;
             unsigned mask = 0;
             int kh = 0, kw = 0;
             for (int t = 0; t < a.ntaps; ++t) {
@@ -685,7 +733,9 @@ __device__ __forceinline__ void conv_dma2_s3p_body(const ConvArgs& a) {
                     ++kh;
                 }
             }
-            a_inv[i] = ~mask;
+            if constexpr (!A3) a_inv[i] = ~mask;
+            else if (i & 1) a_inv[i >> 1] |= ~mask << 16;
+            else a_inv[i >> 1] = ~mask & 0xFFFFu;
         }
 #pragma unroll
         for (int i = 0; i < BL; ++i) {
@@ -697,7 +747,7 @@ __device__ __forceinline__ void conv_dma2_s3p_body(const ConvArgs& a) {
     offsets(m0, n0);
 
     int tap = 0, cb = 0, kh_i = 0, kw_i = 0;
-    const int tapw = a.dil * a.ldx * 4, taph = a.dil * a.W * a.ldx * 4;
+    const int tapw = a.dil * a.ldx * XB, taph = a.dil * a.W * a.ldx * XB;
     int multi, s_kw, s_ntaps;
     asm volatile("s_nop 0\n\tv_readfirstlane_b32 %0, %3\n\tv_readfirstlane_b32 %1, %4\n\tv_readfirstlane_b32 %2, %5\n\ts_nop 4"
                  : "=s"(multi), "=s"(s_kw), "=s"(s_ntaps)
@@ -723,8 +773,9 @@ __device__ __forceinline__ void conv_dma2_s3p_body(const ConvArgs& a) {
     const int arow16 = (wm0 + r16) * 32 + (g16 >> 1), brow16 = (wn0 + r16) * 32 + (g16 >> 1);
     float a16[2][2], b16[2][1][2];
     v4f acc16[1];
-    v4f af3[2][TM][2], bf3[2][TN][3];
-    const int brow3 = (wn0 + lr) * 12, bsw3 = (lr >> 2) & 3;
+    v4f af3[2][A3 ? 1 : TM][2], bf3[2][TN][3];
+    v4f aq3[2][A3 ? TM : 1][3];
+    const int brow3 = (wn0 + lr) * 12, bsw3 = (lr >> 2) & 3, arow3 = (wm0 + lr) * 12;
     const int rr_ = lane >> 3, c4_ = (lane & 7) * 4;
 
     int pb = 0;                                  // stage buffer of the tile's K step 0
@@ -753,10 +804,9 @@ __device__ __forceinline__ void conv_dma2_s3p_body(const ConvArgs& a) {
             offsets(m0n, n0n);
         } else {
 #pragma unroll
-            for (int i = 0; i < AL; ++i) {
-                a_voff[i] = 0x80000000u;
-                a_inv[i] = 0u;
-            }
+            for (int i = 0; i < AL; ++i) a_voff[i] = 0x80000000u;
+#pragma unroll
+            for (int i = 0; i < AINV; ++i) a_inv[i] = 0u;
 #pragma unroll
             for (int i = 0; i < BL; ++i) b_voff[i] = 0x80000000u;
         }
@@ -798,7 +848,7 @@ __device__ __forceinline__ void conv_dma2_s3p_body(const ConvArgs& a) {
         epi_loads();             // behind the last step's MFMAs: in front of that step they would cost 64 x 64 its fourth wave per
                                  // SIMD (scratch at 128 VGPRs), and 256 x 128 has no registers left under them
 
-        float* patch = wave < BM / 32 ? (float*)(As + bl * BM * 8 + wave * 256) : (float*)(Bs + bl * BN * BQ + (wave - BM / 32) * 256);
+        float* patch = wave < BM / 32 ? (float*)(As + bl * BM * AQ + wave * 256) : (float*)(Bs + bl * BN * BQ + (wave - BM / 32) * 256);
         conv_epilogue_s3p<TM, TN>(a, acc, patch, m0 + wm0, n0 + wn0, lane, rres, scv, shv);
         if (!more) {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // no LDS-DMA outlives the block
@@ -831,6 +881,18 @@ __device__ __forceinline__ void conv_dma2_s3p_body(const ConvArgs& a) {
 template <int BM, int BN, int WGM, int NW, bool PADV>
 __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(BM == 64 ? 4 : 2))) void conv_dma2_s3p_kernel(ConvArgs a) {
     conv_dma2_s3p_body<BM, BN, WGM, NW, PADV>(a);
+}
+
+// pre-split activations (A3): the one-tile and the persistent form, ids 146 / 149 (kernels of their own: the instantiations of
+// conv_dma2_kernel / conv_dma2_s3p_kernel keep their names)
+template <int BM, int BN, int WGM, int NW, bool PADV>
+__global__ __launch_bounds__(NW * 64) void conv_dma2_a3_kernel(ConvArgs a) {
+    conv_dma2_body<BM, BN, WGM, NW, PADV, 0, false, false, false, false, true, true>(a, blockIdx.x, gridDim.x);
+}
+
+template <int BM, int BN, int WGM, int NW, bool PADV>
+__global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2))) void conv_dma2_a3p_kernel(ConvArgs a) {
+    conv_dma2_s3p_body<BM, BN, WGM, NW, PADV, true>(a);
 }
 #undef PEMP_STEP_X
 #undef PEMP_STEP
@@ -1031,11 +1093,15 @@ int launch_conv_dma2_split3(int shape, ConvArgs a, void* ws, size_t ws_bytes, bo
     });
 }
 
-// persistent forms (ids 47, 49): grid = resident blocks (occupancy of the instantiation x CUs, taken once), at most the tile count
-template <class T>
+// persistent forms (ids 47, 49; A3: 149): grid = resident blocks (occupancy of the instantiation x CUs, taken once), at most the tile count
+template <class T, bool A3 = false>
 static int launch_dma2_s3p(const ConvArgs& a, hipStream_t st) {
-    constexpr size_t lds = tile_lds_s3<T>();
-    auto kern = a.padv ? conv_dma2_s3p_kernel<T::BM, T::BN, T::WGM, T::NW, true> : conv_dma2_s3p_kernel<T::BM, T::BN, T::WGM, T::NW, false>;
+    constexpr size_t lds = A3 ? tile_lds_a3<T>() : tile_lds_s3<T>();
+    auto s3p_kernel = [](auto padv) {
+        if constexpr (A3) return conv_dma2_a3p_kernel<T::BM, T::BN, T::WGM, T::NW, decltype(padv)::value>;
+        else return conv_dma2_s3p_kernel<T::BM, T::BN, T::WGM, T::NW, decltype(padv)::value>;
+    };
+    auto kern = a.padv ? s3p_kernel(std::true_type{}) : s3p_kernel(std::false_type{});
     static int occ[2] = {0, 0};          // blocks per CU of the two instantiations (racing fills write the same value)
     int& o = occ[a.padv ? 1 : 0];
     if (!o) {
@@ -1059,6 +1125,20 @@ static int launch_dma2_s3p(const ConvArgs& a, hipStream_t st) {
 int launch_conv_dma2_split3_persist(int shape, const ConvArgs& a, hipStream_t st) {
     if (split3_check(true, shape, a)) return -1;
     return with_tile<FamPersist>(shape, [&](auto t) { return launch_dma2_s3p<decltype(t)>(a, st); });
+}
+
+struct TileA3 { static constexpr int BM = 256, BN = 128, NW = 8, WGM = 4; };
+// pre-split activations (ids 146 / 149): the 256 x 128 8-wave shape only.  (128 x 128 would hold 2 x 12 x 256 quads = 96 KiB of
+// LDS per block: one block per CU, where its fp32-input form has two -- no id.)
+int launch_conv_dma2_split3_pre(int shape, bool persistent, const ConvArgs& a, hipStream_t st) {
+    if (split3_check(shape == 6, shape, a)) return -1;
+    // the wave grid: 4 x 2 waves of 64 x 64, not the fp32-input form's 8 full-width strips of 32 x 128 -- those exist to split each
+    // activation once per block; with nothing to split, the squarer wave tile reads 24 KB of LDS per K step instead of 30
+    using T = TileA3;
+    static_assert(T::BM == kTileShapes[6].bm && T::BN == kTileShapes[6].bn && T::NW == kTileShapes[6].nw, "shape 6");
+    if (persistent) return launch_dma2_s3p<T, true>(a, st);
+    auto kern = a.padv ? conv_dma2_a3_kernel<T::BM, T::BN, T::WGM, T::NW, true> : conv_dma2_a3_kernel<T::BM, T::BN, T::WGM, T::NW, false>;
+    return launch_with_lds(kern, tile_grid<T>(a), T::NW * 64, tile_lds_a3<T>(), st, a, "conv_dma2/split3/presplit");
 }
 
 int launch_conv_dma2_group_split3(int shape, ConvGroupArgs& g, hipStream_t st) {
@@ -1092,15 +1172,16 @@ int pack_split3(const float* w, void* out, int cout, int kpad, hipStream_t st) {
 // true when the geometry / operands fit this variant (the caller falls back to conv_dma.hip otherwise)
 bool conv_dma2_supported(const ConvArgs& a) {
     if ((a.flags & PEMP_CONV_STEM4) || a.ntaps > 32 || (a.stats && a.padv)) return false;
+    const long long eb = (a.flags & PEMP_CONV_IN_SPLIT3) ? 6 : 4;       // bytes per activation element (pre-split: three bf16)
     const long long xbytes = ((long long)a.N * a.H * a.W + (long long)a.pad * a.W + a.pad + (long long)a.dil * (a.KH - 1) * a.W +
-                              (long long)a.dil * (a.KW - 1)) * a.ldx * 4;
+                              (long long)a.dil * (a.KW - 1)) * a.ldx * eb;
     const long long wbytes = (long long)a.Cout * a.Kpad * 4;
     if (a.padv) {           // the padding vector must sit behind the activations, inside the 2 GiB window of their descriptor,
                             // and far enough in that subtracting the largest tap displacement leaves a non-negative offset
-        const long long behind = (const char*)a.padv - (const char*)a.x - (long long)a.N * a.H * a.W * a.ldx * 4;
-        const long long d = (const char*)a.padv - (const char*)a.x + ((long long)a.pad * a.W + a.pad) * a.ldx * 4;
-        const long long tapmax = ((long long)a.dil * (a.KH - 1) * a.W + (long long)a.dil * (a.KW - 1)) * a.ldx * 4;
-        if (behind < 0 || d < tapmax || d + (long long)a.Cin * 4 >= (1ll << 31)) return false;
+        const long long behind = (const char*)a.padv - (const char*)a.x - (long long)a.N * a.H * a.W * a.ldx * eb;
+        const long long d = (const char*)a.padv - (const char*)a.x + ((long long)a.pad * a.W + a.pad) * a.ldx * eb;
+        const long long tapmax = ((long long)a.dil * (a.KH - 1) * a.W + (long long)a.dil * (a.KW - 1)) * a.ldx * eb;
+        if (behind < 0 || d < tapmax || d + (long long)a.Cin * eb >= (1ll << 31)) return false;
     }
     return xbytes < (1ll << 31) && wbytes < (1ll << 31);
 }

@@ -280,6 +280,8 @@ extern "C" int pemp_conv2d_padv_splitk_nhwc_f32(const pemp_conv_desc* d, const f
 static int conv_fill(const pemp_conv_desc* d, const float* x, const float* w, float* y, const float* scale, const float* shift,
                      const float* residual, const float* pad_value, ConvArgs& a, bool any_taps = false, bool pooled = false) {
     PEMP_REQUIRE(d && x && w && y, "conv2d: null pointer");
+    PEMP_REQUIRE(pooled || !(d->flags & (PEMP_CONV_OUT_SPLIT3 | PEMP_CONV_IN_SPLIT3)),
+                 "conv2d: pre-split activations belong to pemp_conv2d_nhwc_f32 / _padv_ (no grouped / dropblock / statistics / bf16 form)");
     PEMP_REQUIRE(pooled || !(d->flags & PEMP_CONV_POOL3S2), "conv2d: PEMP_CONV_POOL3S2 belongs to pemp_conv2d_nhwc_f32 (no grouped / dropblock / statistics / bf16 form)");
     PEMP_REQUIRE(!pad_value || (!(d->flags & PEMP_CONV_STEM4) && (any_taps || d->KH * d->KW > 1) && ((uintptr_t)pad_value & 15) == 0),
                  "conv2d: pad_value needs a multi-tap non-stem conv and a 16-byte aligned [Cin] vector");
@@ -338,6 +340,12 @@ static int conv2d_impl(const pemp_conv_desc* d, const float* x, const float* w, 
         tile = 3;
     }
     TileId t = decode_tile(tile);
+    // y: bf16 [M][Cout / 32][3][32].  The persistent kernels have no registers left for the split in their epilogue (it would
+    // cost them scratch): with this flag 47 / 49 / 149 run as the ids they walk, 43 / 46 / 146 -- same tiles, same results
+    const bool out_split3 = d->flags & PEMP_CONV_OUT_SPLIT3;
+    if (out_split3)
+        PEMP_REQUIRE(t.family == TILE_SPLIT3 && !t.splitk && !t.panel && !ws && !stem && !residual && a.Cout % 32 == 0 && a.ldy == a.Cout,
+                     "conv2d: PEMP_CONV_OUT_SPLIT3 needs an unsplit split3 tile id (41..44, 46, 47, 49, 146, 149), ldy == Cout, no residual / workspace");
     if (d->flags & PEMP_CONV_POOL3S2) {     // the fused stem (conv_stem_pool.hip): y is the pooled tensor
         PEMP_REQUIRE(stem && t.family == TILE_SPLIT3 && !t.splitk && !t.panel && !residual && !pad_value,
                      "conv2d: PEMP_CONV_POOL3S2 needs PEMP_CONV_STEM4 with split3 weights (a tile id 41..49), no residual, no padding value");
@@ -348,6 +356,15 @@ static int conv2d_impl(const pemp_conv_desc* d, const float* x, const float* w, 
     PEMP_REQUIRE(tile != 48, "conv2d: no persistent split3 form of the 128 x 128 4-wave tile");
     PEMP_REQUIRE(t.exists, "conv2d: unknown tile id %d", tile);
     hipStream_t st = (hipStream_t)stream;
+    PEMP_REQUIRE(t.presplit == ((d->flags & PEMP_CONV_IN_SPLIT3) != 0), "conv2d: tile ids 146 / 149 and PEMP_CONV_IN_SPLIT3 come together (tile %d)", tile);
+    if (t.presplit) {                    // conv_dma2.hip, A3: x bf16 [N][H][W][Cin / 32][3][32], w from pemp_pack_split3_bf16
+        PEMP_REQUIRE(!stem && !ws && a.ntaps > 1 && a.ntaps <= 16 && a.ldx == a.Cin && !(d->flags & PEMP_CONV_SHIFT_PER_IMAGE),
+                     "conv2d: tile %d takes convs of 2..16 taps with ldx == Cin, no per-image shift, no workspace", tile);
+        PEMP_REQUIRE(conv_dma2_supported(a) && (long long)a.Cout * a.Kpad * 6 < (1ll << 31),
+                     "conv2d: tile %d needs <= 32 taps and operands < 2 GiB (a padding value behind the activations)", tile);
+        PEMP_REQUIRE_COUT("conv2d", t.shape, a.Cout);
+        return launch_conv_dma2_split3_pre(t.shape, t.persistent && !out_split3, a, st);
+    }
     if (t.family == TILE_SPLIT3) {       // conv_dma2.hip, S3: w from pemp_pack_split3_bf16
         PEMP_REQUIRE(!stem && conv_dma2_supported(a) && (long long)a.Cout * a.Kpad * 6 < (1ll << 31),
                      "conv2d: split3 tile %d needs a geometry of the buffer-addressed kernels (no stem, <= 32 taps, operands < 2 GiB)", tile);
@@ -357,7 +374,7 @@ static int conv2d_impl(const pemp_conv_desc* d, const float* x, const float* w, 
                          "conv2d: tile %d needs a 1x1 conv without padding, Kpad <= 256, no padding value / per-image shift / workspace, operands < 2 GiB", tile);
             return launch_conv_panel(t.shape, a, st);
         }
-        if (t.persistent) return launch_conv_dma2_split3_persist(t.shape, a, st);      // same results as the id it walks
+        if (t.persistent && !out_split3) return launch_conv_dma2_split3_persist(t.shape, a, st);      // same results as the id it walks
         return launch_conv_dma2_split3(t.shape, a, ws, ws_bytes, t.splitk, st);
     }
     // the fp32 chain: every id falls back towards the pointer-addressed kernels where its own do not apply (same results)
@@ -400,7 +417,7 @@ extern "C" int pemp_conv2d_group_nhwc_f32(int n, const pemp_conv_desc* d, const 
     g.n = n;
     const int tile = d[0].tile;
     const TileId t = decode_tile(tile);
-    const bool s3 = t.family == TILE_SPLIT3 && t.exists && !t.splitk && !t.persistent && !t.panel;
+    const bool s3 = t.family == TILE_SPLIT3 && t.exists && !t.splitk && !t.persistent && !t.panel && !t.presplit;
     PEMP_REQUIRE((t.family == TILE_DMA2 && !t.splitk && t.shape <= 8) || s3, "conv2d_group: tile must be one of the buffer-addressed variants 21..28 or 41..44, 46, got %d", tile);
     for (int i = 0; i < n; ++i) {
         PEMP_REQUIRE(d[i].tile == tile, "conv2d_group: every member must name the same tile variant");
@@ -499,7 +516,7 @@ extern "C" int pemp_conv2d_bf16_nhwc(const pemp_conv_desc* d, const void* x, con
 static TileId stats_tile(const pemp_conv_desc* d) { return decode_tile(d->tile == 0 ? 23 : d->tile); }
 
 static int conv_stats_fill(const char* what, const pemp_conv_desc* d, ConvArgs& a) {
-    PEMP_REQUIRE(!(d->flags & (PEMP_CONV_STEM4 | PEMP_CONV_RELU | PEMP_CONV_SHIFT_PER_IMAGE | PEMP_CONV_POOL3S2)), "%s: plain conv only (no stem / ReLU / per-image shift)", what);
+    PEMP_REQUIRE(!(d->flags & (PEMP_CONV_STEM4 | PEMP_CONV_RELU | PEMP_CONV_SHIFT_PER_IMAGE | PEMP_CONV_POOL3S2 | PEMP_CONV_OUT_SPLIT3 | PEMP_CONV_IN_SPLIT3)), "%s: plain conv only (no stem / ReLU / per-image shift)", what);
     PEMP_REQUIRE(d->N > 0 && d->H > 0 && d->W > 0 && d->Cin > 0 && d->Cout > 0 && d->KH > 0 && d->KW > 0 && d->stride > 0 && d->dil > 0 && d->pad >= 0,
                  "%s: bad geometry", what);
     const int ho = (d->H + 2 * d->pad - d->dil * (d->KH - 1) - 1) / d->stride + 1;

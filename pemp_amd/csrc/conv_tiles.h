@@ -71,11 +71,16 @@ struct TileId {
     bool persistent;   // 47, 49
     bool exists;       // some entry point takes the id
     bool panel;        // 71, 72: the activation-stationary 1x1 form (conv_panel.hip)
+    bool presplit;     // 146, 149: the activations come pre-split (PEMP_CONV_IN_SPLIT3); the forms of 46 / 49
 };
 
 inline TileId decode_tile(int id) {
-    TileId t = {TILE_NONE, 0, false, false, false, false};
+    TileId t = {TILE_NONE, 0, false, false, false, false, false};
     const int decade = id / 10, s = id % 10;
+    if (id == 146 || id == 149) {
+        t.family = TILE_SPLIT3, t.shape = 6, t.exists = t.presplit = true, t.persistent = id == 149;
+        return t;
+    }
     if (decade == 7 && in_family<FamPanel>(s)) {
         t.family = TILE_SPLIT3, t.shape = s, t.exists = t.panel = true;
         return t;
@@ -123,6 +128,8 @@ int launch_with_lds(Kern kern, int grid, int threads, size_t lds, hipStream_t st
 // carry their three bf16 planes: 12 quads)
 template <class T> constexpr size_t tile_lds() { return (size_t)2 * 8 * (T::BM + T::BN) * sizeof(v4f); }
 template <class T> constexpr size_t tile_lds_s3() { return (size_t)2 * (8 * T::BM + 12 * T::BN) * sizeof(v4f); }
+// ... with pre-split activations (ids 146 / 149): A rows carry their three planes too
+template <class T> constexpr size_t tile_lds_a3() { return (size_t)2 * 12 * (T::BM + T::BN) * sizeof(v4f); }
 template <class T> int tile_grid(const ConvArgs& a) { return cdiv(a.M, T::BM) * (a.Cout / T::BN); }
 
 // points `a` at the split-K workspace of `plan` (counters first, then the partial tiles); -> the grid, or -1 (error set)

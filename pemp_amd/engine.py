@@ -111,6 +111,26 @@ def pack_episode(arena, groups, priors=None):
 GROUP_MAX_ROWS = int(os.environ.get("PEMP_EVAL_GROUP_ROWS", "12000"))
 
 
+#: Output widths at which a single-reader conv -> 3x3 conv pair hands its intermediate tensor over PRE-SPLIT (the producer's epilogue
+#: writes the split3 pieces, the consumer's K loop has no splitting left: ops.conv2d out_split3 / x_split3, DESIGN.md "Pre-split
+#: activations").  A width is listed where the consumer's pre-split form beat the layer's best fp32-input id when measured.
+PRESPLIT_WIDTHS = (128, 256)
+#: ... and only where the consumer has at least this many 256 x 128 tiles (None: one per CU).  The pre-split form has that one block
+#: shape; a one-episode step (5202 rows: 42 tiles on 256 CUs) ran 13 % slower with it than on the small tiles of the fp32-input ids.
+PRESPLIT_MIN_TILES = None
+
+
+def presplit_pair(prod, cons, x, rows, enabled=True):
+    """Whether ``prod`` (fed ``x``) may hand its output to its ONLY reader ``cons`` (``rows`` output rows) pre-split: both split3
+    layers on fp32 activations, ``cons`` multi-tap with a pre-split form for its width, enough tiles to fill the chip.
+    PEMP_SPLIT3_PRESPLIT=0 withholds it."""
+    if not (enabled and ops.SPLIT3_PRESPLIT and x.dtype == torch.float32 and x.is_cuda and prod.w3 is not None and cons.w3 is not None
+            and not prod.stem and cons.kh * cons.kw > 1 and cons.cin % 32 == 0 and cons.cout % 128 == 0 and cons.cout in PRESPLIT_WIDTHS):
+        return False
+    least = torch.cuda.get_device_properties(x.device).multi_processor_count if PRESPLIT_MIN_TILES is None else PRESPLIT_MIN_TILES
+    return -(-rows // 256) * (cons.cout // 128) >= least
+
+
 class Arena:
     """Named activation buffers reused across calls (static addresses make hipGraph replay valid)."""
 
@@ -156,6 +176,8 @@ class _BottleneckTrunk:
     #: a block's conv1 and downsample conv go out as one grouped launch on small steps.  The deep-base trunk launches them one
     #: by one: switching the grouping on there changes PFENet's speed and is therefore a change of its own.
     GROUP_DS = True
+    #: conv1 hands y1 to conv2 pre-split (presplit_pair).  Off on the deep-base trunk for the same reason.
+    PRESPLIT = True
 
     def _block(self, x, bp, tag, c1_shift=None, ds_shift=None, out=None):
         """``out``: where the block's result goes (an NHWC view, e.g. a channel slice of a wider buffer); None: the arena's
@@ -166,16 +188,17 @@ class _BottleneckTrunk:
         ho, wo = (ops.conv_out_size(v, k, bp.c2.stride, bp.c2.pad, bp.c2.dil) for v, k in ((h1, bp.c2.kh), (w1, bp.c2.kw)))
         if out is None:
             out = a.get(("blk", tag), (n, ho, wo, bp.c3.cout))
-        y1 = a.get("y1", (n, h1, w1, bp.c1.cout))
         res = a.get("res", (n, ho, wo, bp.ds.cout)) if bp.ds is not None else x
         # small step: conv1 and the downsample conv read the same x -- one grouped launch
         grouped = self.GROUP_DS and bp.ds is not None and c1_shift is None and ds_shift is None \
             and 0 < n * ho * wo <= GROUP_MAX_ROWS and x.dtype == torch.float32
+        pre = presplit_pair(bp.c1, bp.c2, x, n * ho * wo, self.PRESPLIT and not grouped)       # y1 has one reader: conv2
+        y1 = a.get("y1s", ops.split3_shape(n, h1, w1, bp.c1.cout), torch.bfloat16) if pre else a.get("y1", (n, h1, w1, bp.c1.cout))
         if grouped:
             ops.conv2d_group([x, x], [bp.c1, bp.ds], [y1, res])
         else:
-            ops.conv2d(x, bp.c1, out=y1, shift_override=c1_shift, per_image_shift=c1_shift is not None)
-        y2 = ops.conv2d(y1, bp.c2, out=a.get("y2", (n, ho, wo, bp.c2.cout)))
+            ops.conv2d(x, bp.c1, out=y1, shift_override=c1_shift, per_image_shift=c1_shift is not None, out_split3=pre)
+        y2 = ops.conv2d(y1, bp.c2, out=a.get("y2", (n, ho, wo, bp.c2.cout)), x_split3=pre)
         if bp.ds is not None and not grouped:
             ops.conv2d(x, bp.ds, out=res, shift_override=ds_shift, per_image_shift=ds_shift is not None)
         return ops.conv2d(y2, bp.c3, out=out, residual=res)
@@ -433,12 +456,14 @@ class PurifierEngine:
     def forward(self, x):
         a = self.arena
         n, h, w, _ = x.shape
-        y = ops.conv2d(x, self.p0, out=a.get("pur0", (n, h, w, self.p0.cout)))
+        pre = presplit_pair(self.p0, self.p3, x, n * h * w)         # p0's output has one reader: p3
+        y = ops.conv2d(x, self.p0, out_split3=pre, out=a.get("pur0s", ops.split3_shape(n, h, w, self.p0.cout), torch.bfloat16) if pre
+                       else a.get("pur0", (n, h, w, self.p0.cout)))
         # the ASPP input carries 8 spare pixel rows behind it: the folded-BatchNorm branches keep their per-channel
         # padding vectors there, inside the buffer-descriptor window of the tensor (conv_dma2.hip, PADV)
         c = self.p3.cout
         flat = a.get("pur3+tail", (n * h * w + 8, c))
-        y = ops.conv2d(y, self.p3, out=flat[:n * h * w].view(n, h, w, c))
+        y = ops.conv2d(y, self.p3, out=flat[:n * h * w].view(n, h, w, c), x_split3=pre)
         if isinstance(self.aspp, ASPPV2Engine):
             return self.aspp.forward(y, tail=flat[n * h * w:])
         return self.aspp.forward(y)

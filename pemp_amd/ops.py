@@ -13,7 +13,7 @@ import os
 import torch
 
 from . import _lib
-from ._lib import ConvDesc, CONV_RELU, CONV_SHIFT_PER_IMAGE, CONV_STEM4, CONV_POOL3S2  # noqa: F401
+from ._lib import ConvDesc, CONV_RELU, CONV_SHIFT_PER_IMAGE, CONV_STEM4, CONV_POOL3S2, CONV_OUT_SPLIT3, CONV_IN_SPLIT3  # noqa: F401
 
 
 def _stream():
@@ -84,6 +84,9 @@ TILES.update({t: TILES[of]._replace(persistent_of=of) for t, of in SPLIT3_PERSIS
 #: the activation-stationary split3 form of short-K 1x1 convs (csrc/conv_panel.hip): a block keeps 128 rows x K of split activations in
 #: registers and walks all of Cout, 128 (71) or 64 (72) columns at a time
 TILES.update({70 + s: Tile(_SHAPES[s], "split3", False, None) for s in (1, 2)})
+#: split3 with pre-split ACTIVATIONS (csrc/conv_dma2.hip, A3): the forms of 46 / 49 whose input was written split by its producer's
+#: epilogue (conv2d(out_split3=True)), so that their K loop has no splitting left to do
+TILES.update({146: Tile(_SHAPES[6], "split3", False, None), 149: Tile(_SHAPES[6], "split3", False, 146)})
 _NO_TILE = Tile(None, None, False, None)        # an id outside the registry: the library refuses it
 
 
@@ -107,6 +110,11 @@ SPLIT3_DEFAULT_TILE = 43
 #: their own, offered to timing-based picks only, where ``_panel_ok`` holds (PEMP_SPLIT3_PANEL=0: never, the A/B switch)
 SPLIT3_PANEL_TILES = (71, 72)
 SPLIT3_PANEL = os.environ.get("PEMP_SPLIT3_PANEL", "1") != "0"
+#: ... and the forms that read pre-split activations (bit-identical to the ids above on the fp32 tensor): the only ids of a call
+#: with ``x_split3``, and of no other call -- a registry and a pick key of their own.  PEMP_SPLIT3_PRESPLIT=0: the engines never
+#: hand a tensor over pre-split (the A/B switch)
+SPLIT3_PRESPLIT_TILES = (146, 149)
+SPLIT3_PRESPLIT = os.environ.get("PEMP_SPLIT3_PRESPLIT", "1") != "0"
 AUTOTUNE = True
 #: test hook: ``PICK_HOOK(kind, cands, key) -> one of cands`` decides every kernel-variant pick INSTEAD of timing (kind "conv":
 #: tile ids, "wgrad": block counts / (tile kind, block count) pairs), at any problem size.  Timing-based picks differ from box
@@ -296,15 +304,41 @@ def pack_conv_weight(w_oihw, stem4=False):
     return w.reshape(co, kh * kw * ci), kh * kw * ci
 
 
-def _conv_geom(who, x, p, out, residual, dtype=torch.float32, out_dtype=None):
+def split3_shape(n, h, w, c):
+    """Shape of the pre-split form of an [n, h, w, c] fp32 activation tensor: bf16, per pixel and 32-channel group the planes h, m, l."""
+    return (n, h, w, c // 32, 3, 32)
+
+
+def _split3_dims(t, name):
+    if t.dim() != 6 or t.dtype != torch.bfloat16 or tuple(t.shape[4:]) != (3, 32) or not t.is_contiguous():
+        raise ValueError(f"{name}: expected a contiguous bf16 [N, H, W, C / 32, 3, 32] pre-split tensor, got {tuple(t.shape)} {t.dtype} {t.stride()}")
+    return tuple(t.shape[:3]) + (t.shape[3] * 32,)
+
+
+def _conv_geom(who, x, p, out, residual, dtype=torch.float32, out_dtype=None, x_split3=False, out_split3=False):
     """What every conv wrapper checks of its tensors: x an NHWC view of the layer's channel count, ``out`` (allocated when None)
-    and ``residual`` NHWC views of the output's shape.  -> (n, h, w, cin, ldx, ho, wo, out, ldy, ldr)"""
-    ldx = _nhwc(x, "x", dtype)
-    n, h, w, cin = x.shape
+    and ``residual`` NHWC views of the output's shape.  ``x_split3`` / ``out_split3``: that tensor is in the pre-split form
+    (``split3_shape``: dense, so its per-pixel stride is the channel count).  -> (n, h, w, cin, ldx, ho, wo, out, ldy, ldr)"""
+    if x_split3:
+        n, h, w, cin = _split3_dims(x, "x")
+        ldx = cin
+    else:
+        ldx = _nhwc(x, "x", dtype)
+        n, h, w, cin = x.shape
     if cin != p.cin:
         raise ValueError(f"{who}: input has {cin} channels, layer expects {p.cin}")
     ho = conv_out_size(h, p.kh, p.stride, p.pad, p.dil)
     wo = conv_out_size(w, p.kw, p.stride, p.pad, p.dil)
+    if out_split3:
+        if p.cout % 32:
+            raise ValueError(f"{who}: a pre-split output needs Cout % 32 == 0, got {p.cout}")
+        if out is None:
+            out = torch.empty(split3_shape(n, ho, wo, p.cout), dtype=torch.bfloat16, device=x.device)
+        if _split3_dims(out, "out") != (n, ho, wo, p.cout):
+            raise ValueError(f"{who}: out shape {tuple(out.shape)} != {split3_shape(n, ho, wo, p.cout)}")
+        if residual is not None:
+            raise ValueError(f"{who}: no residual with a pre-split output")
+        return n, h, w, cin, ldx, ho, wo, out, p.cout, 0
     if out is None:
         out = torch.empty((n, ho, wo, p.cout), dtype=out_dtype or dtype, device=x.device)
     ldy = _nhwc(out, "out", out_dtype or dtype)
@@ -319,35 +353,62 @@ def _conv_geom(who, x, p, out, residual, dtype=torch.float32, out_dtype=None):
 
 
 def conv2d(x, p, out=None, residual=None, shift_override=None, per_image_shift=False, relu=None, tile=0,
-           pad_value=None, splitk=False, dropblock=None):
+           pad_value=None, splitk=False, dropblock=None, out_split3=False, x_split3=False):
     """y = act(scale * conv(x, w) + shift (+ residual)).  x: NHWC view, returns NHWC tensor/view ``out``.
+    ``out_split3``: ``out`` is written PRE-SPLIT (bf16 ``split3_shape``: the split3 pieces of the fp32 result, for ONE reader that
+    takes it with ``x_split3``); split3 layers only, no residual / split-K / DropBlock, never the panel ids.
+    ``x_split3``: ``x`` is such a tensor (a ``pad_value`` then the same split of the [Cin] vector, bf16 [Cin / 32, 3, 32]); multi-tap
+    split3 layers with Cout % 128 == 0 only, no per-image shift / split-K / DropBlock -- the ids of SPLIT3_PRESPLIT_TILES, bit-
+    identical to the layer on the fp32 tensor.
     ``pad_value`` [Cin]: what out-of-image taps read instead of zero (multi-tap convs; see fold_input_affine).
     ``splitk``: the autotuner may also pick the split-K variants (training path: they are not bit-identical to the rest).
     ``dropblock`` (mask fp32 [N,Ho,Wo], kept count int32 [1]) -- a DropBlock2D record of train_ops.dropblock_mask: the layer's
     scaling of the output rows happens in the conv's epilogue (pemp_conv2d_dropblock_nhwc_f32; same arithmetic as
     train_ops.pixel_scale on the conv's result)."""
-    if x.dtype == torch.bfloat16:
+    if out_split3 or x_split3:       # what the library refuses for these forms (csrc/conv_igemm.hip: conv2d_impl)
+        what = "a pre-split output" if out_split3 else "a pre-split input"
+        if p.w3 is None or p.stem:
+            raise ValueError(f"conv2d: {what} needs a split3 layer (ConvParams.w3), not the fp32 chain or a stem")
+        if splitk or dropblock is not None:
+            raise ValueError(f"conv2d: {what} has no split-K / DropBlock form")
+        if out_split3 and tile and (tile not in SPLIT3_TILES + SPLIT3_PRESPLIT_TILES):
+            raise ValueError(f"conv2d: a pre-split output needs an unsplit split3 tile id, got {tile}")
+        if x_split3 and (p.kh * p.kw == 1 or per_image_shift or p.cin % 32 or p.cout % 128):
+            raise ValueError("conv2d: a pre-split input needs a multi-tap conv with Cin % 32 == 0 and Cout % 128 == 0, no per-image shift")
+    if (tile in SPLIT3_PRESPLIT_TILES) != bool(x_split3) and (tile or not x_split3):
+        raise ValueError(f"conv2d: the tile ids {SPLIT3_PRESPLIT_TILES} and x_split3 come together (tile {tile})")
+    if x.dtype == torch.bfloat16 and not x_split3:
         return _conv2d_bf16(x, p, out, residual, shift_override, per_image_shift, relu, tile, pad_value)
+    n, h, w, cin, ldx, ho, wo, out, ldy, ldr = _conv_geom("conv2d", x, p, out, residual, x_split3=x_split3, out_split3=out_split3)
     lib = _lib.load()
     _chk_dev(x, p.w, out, residual)
-    n, h, w, cin, ldx, ho, wo, out, ldy, ldr = _conv_geom("conv2d", x, p, out, residual)
     shift = p.shift if shift_override is None else shift_override
     if pad_value is not None:
         _chk_dev(pad_value)
-        if pad_value.numel() != cin or pad_value.dtype != torch.float32 or not pad_value.is_contiguous():
+        if x_split3:
+            if tuple(pad_value.shape) != (cin // 32, 3, 32) or pad_value.dtype != torch.bfloat16 or not pad_value.is_contiguous():
+                raise ValueError(f"conv2d: with x_split3, pad_value must be a contiguous bf16 [{cin // 32}, 3, 32] split vector")
+        elif pad_value.numel() != cin or pad_value.dtype != torch.float32 or not pad_value.is_contiguous():
             raise ValueError(f"conv2d: pad_value must be a contiguous fp32 [{cin}] vector")
-    flags = 0
+    flags = (CONV_OUT_SPLIT3 if out_split3 else 0) | (CONV_IN_SPLIT3 if x_split3 else 0)
     if (p.relu if relu is None else relu):
         flags |= CONV_RELU
     if per_image_shift:
         flags |= CONV_SHIFT_PER_IMAGE
     if p.stem:
         flags |= CONV_STEM4
-    splitk = ((splitk and SPLITK) or (EVAL_SPLITK and n * ho * wo <= EVAL_SPLITK_MAX_ROWS)) and not p.stem
+    splitk = ((splitk and SPLITK) or (EVAL_SPLITK and n * ho * wo <= EVAL_SPLITK_MAX_ROWS)) and not p.stem \
+        and not out_split3 and not x_split3
     # split3: the layer carries split weights (inference engines; the layer's geometry decided it) and plain epilogue.  A call
     # outside the buffer-addressed kernels (an input of 2 GiB or more; a padding vector that does not sit far enough behind a
     # small map under a large dilation) runs the fp32 chain, whose pointer-addressed fall-back takes it
-    s3 = p.w3 is not None and dropblock is None and dma2_supported(x, p) and _group_member_ok(x, p, pad_value)
+    if x_split3:
+        s3 = _presplit_ok(x, p, pad_value)
+    else:
+        s3 = p.w3 is not None and dropblock is None and dma2_supported(x, p) and _group_member_ok(x, p, pad_value)
+    if (out_split3 or x_split3) and not s3:
+        raise ValueError("conv2d: pre-split activations need a geometry of the buffer-addressed kernels (<= 32 taps, operands < 2 GiB, "
+                         "a padding value behind the activations)")
 
     if dropblock is not None:
         dmask, dcnt = dropblock
@@ -389,7 +450,13 @@ def conv2d(x, p, out=None, residual=None, shift_override=None, per_image_shift=F
     if tile == 0:
         key = (p.cin, p.cout, p.kh, p.kw, p.stride, p.pad, p.dil, (6 if dropblock is not None else 4) if splitk else int(p.stem) + (7 if dropblock is not None else 0),
                n, h, w, int(residual is not None), int(pad_value is not None)) + ((3,) if s3 else ())    # 3: split3 picks
-        if s3:
+        if x_split3 or out_split3:
+            # keys of their own: a pick made on the fp32 tensor is never replayed on the split one, nor the reverse
+            key += (146,) * int(x_split3) + (16,) * int(out_split3)
+            # (with a pre-split output the persistent ids run as the ids they walk: not offered twice)
+            cands = lambda: _fits([t for t in (SPLIT3_PRESPLIT_TILES if x_split3 else SPLIT3_TILES)
+                                   if not (out_split3 and TILES[t].persistent_of)], p.cout)
+        elif s3:
             # a pick among candidates that include the panel ids is remembered under a key of its own (71): a call of the same
             # geometry that they do not take (a per-image shift, operands of 2 GiB) must never replay it
             panel = _panel_ok(p, n, ho, wo, ldx, ldy, ldr, h, w, pad_value, splitk, per_image_shift)
@@ -404,7 +471,7 @@ def conv2d(x, p, out=None, residual=None, shift_override=None, per_image_shift=F
                     ids.remove(29)         # no hybrid launch for this geometry / layer: id 29 would run as 23 (or 13)
                 return _fits(ids, p.cout)
         tile = _choose_tile(key, n * ho * wo, launch, cands,
-                            SPLIT3_DEFAULT_TILE if s3 else DEFAULT_TILE + (10 if dropblock is not None else 0))
+                            SPLIT3_PRESPLIT_TILES[0] if x_split3 else SPLIT3_DEFAULT_TILE if s3 else DEFAULT_TILE + (10 if dropblock is not None else 0))
     launch(tile)
     return out
 
@@ -502,6 +569,21 @@ def _group_member_ok(x, p, pad_value):
         off = pad_value.data_ptr() - x.data_ptr()
         d = off + (p.pad * w + p.pad) * ldx * 4
         if off < n * h * w * ldx * 4 or d < tapmax or d + p.cin * 4 >= 2 ** 31:
+            return False
+    return True
+
+
+def _presplit_ok(x, p, pad_value):
+    """conv_dma2_supported for a pre-split input (6 bytes per element; ``pad_value`` the split vector)."""
+    n, h, w = x.shape[:3]
+    row = p.cin * 6
+    tapmax = (p.dil * (p.kh - 1) * w + p.dil * (p.kw - 1)) * row
+    if p.kh * p.kw > 32 or (n * h * w + p.pad * w + p.pad) * row + tapmax >= 2 ** 31 or p.w3.numel() * 2 >= 2 ** 31:
+        return False
+    if pad_value is not None:
+        off = pad_value.data_ptr() - x.data_ptr()
+        d = off + (p.pad * w + p.pad) * row
+        if off < n * h * w * row or d < tapmax or d + row >= 2 ** 31:
             return False
     return True
 

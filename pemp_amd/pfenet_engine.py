@@ -30,6 +30,7 @@ MERGE_CIN = REDUCE + 32                 # query channels + the prior channel, ze
 class DeepBaseResNetEngine(_BottleneckTrunk):
     """pfe_resent.ResNet(Bottleneck, [3, 4, 6, 3], deep_base=True) with PFENet's dilations (pfenet.py:68-77): a three-conv stem, a
     max-pool without ceil_mode and v1.5 bottlenecks (the stride sits on the 3x3 conv; layer 3 / 4 dilated with stride 1)."""
+    PRESPLIT = False
     GROUP_DS = False                    # see _BottleneckTrunk: grouping conv1 with the downsample conv would change PFENet's speed
 
     def __init__(self, model, arena):

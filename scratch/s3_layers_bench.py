@@ -1,8 +1,10 @@
 """The heavy layers of the 25-episode eval step (M = 130 050 rows: 50 maps of 51 x 51) alone on the chip, per split3 tile id: us,
 TFLOP/s, bit-identity of every unsplit id with id 43, and a hash of every output (ids 51..56 included) so that two builds can be
-compared.  GPU.
+compared.  The multi-tap layers also run the ids that read PRE-SPLIT activations (146 / 149, the input split on the device by the
+reference arithmetic), and the 1x1 layers without a residual also run as producers of a pre-split output ("43s" = id 43 with
+out_split3; its result must be the split of id 43's).  Every cell carries the fastest and the slowest of its --reps timings.  GPU.
 
-    python3 scratch/s3_layers_bench.py [--only 256-256-k3] [--reps N]
+    python3 scratch/s3_layers_bench.py [--only 256-256-k3[,...]] [--ids 49,149] [--reps N]
 
 Inputs come from a seeded CPU generator: the hashes are functions of the kernels alone."""
 import argparse
@@ -18,28 +20,42 @@ from pemp_amd import ops  # noqa: E402
 UNSPLIT = (43, 42, 41, 44, 46, 47, 49)     # 47 / 49: persistent forms of 43 / 46
 SPLIT = (52, 51, 54, 56)
 PANEL = ops.SPLIT3_PANEL_TILES             # 71 / 72: activation-stationary forms (1x1, Kpad <= 256; conv_panel.hip)
+PRESPLIT = ops.SPLIT3_PRESPLIT_TILES       # 146 / 149: the forms of 46 / 49 on pre-split activations
 # (cin, cout, k, dil, residual, padding value[, stride, maps of HW x HW]): the six geometries that carry ~81 % of the step's conv time, and the 3 x 3 layer
 # once more with a padding value (the PADV instantiation)
 LAYERS = ((256, 1024, 1, 1, True, False), (512, 1024, 1, 1, False, False), (1024, 256, 1, 1, False, False),
           (256, 256, 3, 2, False, False), (128, 512, 1, 1, True, False), (1024, 512, 1, 1, False, False),
           (256, 256, 3, 2, False, True),
           # the short-K expand convs of layer1 / layer2 at the headline's M (510 050 rows: 50 maps of 101 x 101), the stride-2 downsample
-          (64, 256, 1, 1, True, False, 1, 101), (64, 256, 1, 1, False, False, 1, 101), (256, 512, 1, 1, False, False, 2, 101))
+          (64, 256, 1, 1, True, False, 1, 101), (64, 256, 1, 1, False, False, 1, 101), (256, 512, 1, 1, False, False, 2, 101),
+          # the other 3x3 widths (layer2: stride 1 at 51 x 51 and stride 2 from 101 x 101; layer1 at 101 x 101) and layer2's conv1
+          (128, 128, 3, 1, False, False), (128, 128, 3, 1, False, False, 2, 101), (64, 64, 3, 1, False, False, 1, 101),
+          (512, 128, 1, 1, False, False))
 
 
 def timed(fn, reps, n=5):
     for _ in range(2):
         fn()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    best = 1e9
+    best, worst = 1e9, 0.0
     for _ in range(reps):
         e0.record()
         for _ in range(n):
             fn()
         e1.record()
         e1.synchronize()
-        best = min(best, e0.elapsed_time(e1) / n * 1e3)
-    return best
+        us = e0.elapsed_time(e1) / n * 1e3
+        best, worst = min(best, us), max(worst, us)
+    return best, worst
+
+
+def presplit(x):
+    """fp32 [..., C] -> bf16 [..., C / 32, 3, 32]: the planes h, m, l of pemp_pack_split3_bf16's arithmetic."""
+    h = x.to(torch.bfloat16)
+    r = x - h.float()
+    m = r.to(torch.bfloat16)
+    lo = (r - m.float()).to(torch.bfloat16)
+    return torch.stack([p.reshape(*x.shape[:-1], x.shape[-1] // 32, 32) for p in (h, m, lo)], dim=-2).contiguous()
 
 
 def digest(t):
@@ -50,16 +66,18 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", default="", help="cin-cout-kK[-padv]: one layer")
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--ids", default="", help="comma-separated tile ids: only these are timed (a counter run of one kernel)")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     N = 50
+    keep = lambda ids: tuple(t for t in ids if not args.ids or str(t) in args.ids.split(","))
     for layer in LAYERS:
         cin, cout, k, dil, has_res, padv = layer[:6]
         stride, HW = layer[6:] if len(layer) > 6 else (1, 51)
         M = N * HW * HW
-        HO = (HW - 1) // stride + 1 if k == 1 else HW
+        HO = (HW - 1) // stride + 1
         name = f"{cin}-{cout}-k{k}" + ("-padv" if padv else "") + (f"-s{stride}" if stride > 1 else "") + (f"-hw{HW}-res{int(has_res)}" if HW != 51 else "")
-        if args.only and args.only != name:
+        if args.only and name not in args.only.split(","):
             continue
         g = torch.Generator().manual_seed(cin * 7 + cout * 3 + k)
         buf = torch.empty(M + 4, cin, device=dev)
@@ -78,7 +96,7 @@ def main():
         ref = ops.conv2d(x, prm, residual=res, pad_value=pad_value, tile=43).clone()
         cells, hashes = [], [f"43={digest(ref)}"]
         panel = PANEL if k == 1 and kpad <= 256 and not padv else ()
-        for tile in UNSPLIT + panel + SPLIT:
+        for tile in keep(UNSPLIT + panel + SPLIT):
             if cout % ops._tile_bn(tile):
                 continue
             run = lambda: ops.conv2d(x, prm, residual=res, pad_value=pad_value, out=out, tile=tile)
@@ -86,13 +104,37 @@ def main():
             same = torch.equal(out, ref)
             if tile in SPLIT:
                 hashes.append(f"{tile}=" + ("43" if same else digest(out)))
-            us = timed(run, args.reps)
+            us, worst = timed(run, args.reps)
             mark = "" if same else (" ~" if tile in SPLIT else " !")
-            cells.append(f"{tile}: {us:7.1f}us {fl / us / 1e6:5.1f}TF{mark}")
+            cells.append(f"{tile}: {us:7.1f}..{worst:6.1f}us {fl / us / 1e6:5.1f}TF{mark}")
             if tile not in SPLIT and not same:
                 hashes.append(f"{tile}=MISMATCH:{digest(out)}")
+        if k > 1 and cout % 128 == 0:            # the same layer on pre-split activations
+            sbuf = torch.zeros((M + 4) * cin * 3, dtype=torch.bfloat16, device=dev)
+            sbuf[:(M + 1) * cin * 3] = presplit(buf[:M + 1]).reshape(-1)
+            xs, pvs = sbuf[:M * cin * 3].view(N, HW, HW, cin // 32, 3, 32), sbuf[M * cin * 3:(M + 1) * cin * 3].view(cin // 32, 3, 32)
+            for tile in keep(PRESPLIT):
+                run = lambda: ops.conv2d(xs, prm, residual=res, pad_value=pvs if padv else None, out=out, tile=tile, x_split3=True)
+                run()
+                same = torch.equal(out, ref)
+                us, worst = timed(run, args.reps)
+                cells.append(f"{tile}: {us:7.1f}..{worst:6.1f}us {fl / us / 1e6:5.1f}TF{'' if same else ' !'}")
+            del sbuf, xs, pvs
+        if k == 1 and not has_res:               # the same layer as the producer of a pre-split output
+            want = presplit(ref)
+            outs = torch.empty_like(want)
+            for tile in keep((43, 42, 41, 44, 46) if not args.ids else ()):
+                if cout % ops._tile_bn(tile):
+                    continue
+                run = lambda: ops.conv2d(x, prm, out=outs, tile=tile, out_split3=True)
+                run()
+                same = torch.equal(outs.view(torch.int16), want.view(torch.int16))
+                us, worst = timed(run, args.reps)
+                cells.append(f"{tile}s: {us:7.1f}..{worst:6.1f}us{'' if same else ' !'}")
+            del want, outs
         print(f"{name:>16} k{k} d{dil} res{int(has_res)} | " + " | ".join(cells), flush=True)
         print(f"{'':>16} hash " + " ".join(hashes), flush=True)
+    print("(146 / 149: on the pre-split input; NNs: id NN writing a pre-split output, ! = not the split of id 43's)")
     print("(! = an unsplit id differs from id 43; ~ = a split-K id differs from id 43, expected where it splits)")
 
 
