@@ -9,22 +9,34 @@
 //    stride and the input's channel stride go into the row offset (a stride-2 downsample is a row gather); rows >= M read zeros
 //    through the buffer range check;
 //  * the block then walks the N tiles (BN columns each).  Only the packed weights stream through LDS: one stage = the 32-channel
-//    K step of BN weight rows in the S3 image of conv_dma2.hip (12 quads per row, same swizzle, same LDS-DMA), three stages in a
-//    ring, the DMA of stage t + 3 issued behind the barrier in the middle of stage t.  The K loop is MFMAs, B fragment reads and
-//    DMA issue: no A reads, no split;
+//    K step of BN weight rows in the S3 image of conv_dma2.hip (12 quads per row, same swizzle, same LDS-DMA), NS stages in a
+//    ring (panel_stages), the DMA of stage t + NS issued behind the barrier in the middle of stage t.  The K loop is MFMAs, B
+//    fragment reads and DMA issue: no A reads, no split;
 //  * per accumulator the order is K16 slices ascending, inside a slice lh, hl, mm, mh, hm, hh: BIT-IDENTICAL to ids 41..49 (the
 //    accumulators of one slice are interleaved product by product, so that consecutive MFMAs do not depend on each other);
-//  * the epilogue is conv_epilogue_lds_pre's arithmetic, statement for statement.  The residual / scale / shift quads of N tile n
-//    are requested behind the barrier of its last K step; its stores are buffer stores that are ALWAYS issued (a row >= M gets an
-//    offset behind the descriptor's range and is dropped), so that their number is a constant and the wait for a weight stage
-//    can be counted past them: they drain under the MFMAs of tile n + 1.
-// Vector memory operations of a wave retire in order (the persistent kernels of conv_dma2.hip count on the same), in issue
-// order:  DMA(t+1) | .. | DMA(t+2) | .. | <- the wait in the middle of stage t wants everything up to DMA(t+1):
-//   K step 0 of a tile, or its K step 1:  one batch of NST stores of the previous tile lies behind DMA(t+1)  -> vmcnt(BL + NST)
-//   NK == 1:                              two batches                                                         -> vmcnt(BL + 2 NST)
-//   any other step:                                                                                           -> vmcnt(BL)
-// (loads of the epilogue lie in front of the stores that use them and may be left out of the count: that only waits longer.
-// The first three stages are waited for in full before the loop, which covers the steps that have no such history yet.)
+//  * the epilogue is conv_epilogue_lds_pre's arithmetic, statement for statement.  Its stores are buffer stores that are ALWAYS
+//    issued (a row >= M gets an offset behind the descriptor's range and is dropped), so that their number is a constant and the
+//    wait for a weight stage can be counted past them: they drain under the MFMAs of tile n + 1.
+// Vector memory operations of a wave retire in issue order (the persistent kernels of conv_dma2.hip count on the same), so the
+// wait in the middle of stage t, which wants DMA(t + 1), is vmcnt(everything issued behind DMA(t + 1)).  DMA(t + 1) went out in
+// the middle of step t + 1 - NS; the steps u = t + 1 - NS .. t - 1 have since put behind it (panel_behind):
+//   BL DMAs of stage u + NS    for every u but the first (whose DMA is the one waited for),
+//   NST stores                 after every u that is the last K step of its tile.
+// The number depends on t through kt = t % NK alone.  The loads of a tile's residual / scale / shift quads are conditional and
+// stay out of the count wherever they are issued: a count that is too small only waits longer, for the oldest operations behind
+// DMA(t + 1) as well.
+//  * NK < 4 (layer1's K = 64: at the HBM bound, too few steps per tile) keeps three stages and asks for those quads behind the
+//    barrier of the tile's LAST K step, in front of the DMA: vmcnt(BL + NST) in K steps 0 and 1, vmcnt(BL + 2 NST) at NK == 1,
+//    vmcnt(BL) elsewhere.
+//  * NK >= 4 asks for them in K step 0 of the tile that uses them, behind that step's DMA: a whole tile ahead of the epilogue
+//    instead of half a K step.  Its ring is 5 to 8 stages deep (panel_stages: what LDS and the 6 bits of vmcnt allow), so that
+//    a store has NS - 1 K steps to retire before a weight wait sits behind it, not 2.  Its vector memory instructions of a K
+//    step -- the stage's DMAs, in K step 0 the residual loads behind them -- go out one behind each MFMA of the step's second
+//    K16 slice: issued in a burst behind the barrier, by four waves at once, they held every wave's MFMAs up while the address
+//    unit worked through them (residual loads issued for nothing cost 2 - 3 % of a 256 -> 1024 launch).
+// The first NS stages are waited for in full before the loop.  That covers the steps t <= NS - 2, whose window reaches in front
+// of step 0 and whose count names operations that were never issued: their stage has landed whatever the count says.  From
+// t = NS - 1 on every step of the window is a real one and issues exactly the operations above.
 // Stages past the last one are still issued, with every offset behind the range: the hardware writes zeros into a free buffer
 // and reads no memory -- one form of the step, constant counts.
 #include "conv_tiles.h"
@@ -34,6 +46,42 @@ namespace pemp {
 typedef __attribute__((address_space(3))) void* lptr_t;
 typedef __attribute__((ext_vector_type(4))) unsigned int v4u;
 
+// the long-K schedule: epilogue operands a tile ahead, a deep ring, vector memory instructions issued between the MFMAs
+template <int NK> constexpr bool panel_early() { return NK >= 4; }
+// two blocks per CU (registers and LDS): the 64-column form up to K = 128
+template <int NK, int BN> constexpr bool panel_two_blocks() { return BN == 64 && NK <= 4; }
+// stages in the ring: stages are 12 KB (BN = 64) / 24 KB (BN = 128), the patches 16 KB, a CU has 160 KB; and panel_behind <= 63
+template <int NK, int BN> constexpr int panel_stages() {
+    if (!panel_early<NK>()) return 3;
+    if (NK == 4) return 5;                          // BN = 64: two blocks of 76 KB each; a tile is 4 steps long
+    return BN == 64 ? 8 : 6;                        // 112 KB; 160 KB
+}
+// vector memory operations behind DMA(t + 1) at the wait of K step kt = t % NK (the derivation in the file header)
+template <int NK, int NS, int BL, int NST>
+constexpr int panel_behind(int kt) {
+    int c = 0;
+    for (int u = kt + 1 - NS; u <= kt - 1; ++u) {
+        const int ku = ((u % NK) + NK) % NK;
+        if (u > kt + 1 - NS) c += BL;
+        if (ku == NK - 1) c += NST;
+    }
+    return c;
+}
+template <int NK, int NS, int BL, int NST>
+constexpr int panel_behind_max() {
+    int m = 0;
+    for (int kt = 0; kt < NK; ++kt) m = panel_behind<NK, NS, BL, NST>(kt) > m ? panel_behind<NK, NS, BL, NST>(kt) : m;
+    return m;
+}
+// every LDS read of this wave has returned; its pieces of stage t + 1 have landed
+template <int NK, int NS, int BL, int NST, int KT = 0>
+__device__ __forceinline__ void panel_wait(int kt) {
+    if constexpr (KT < NK) {
+        if (kt == KT) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(panel_behind<NK, NS, BL, NST>(KT)) : "memory");
+        else panel_wait<NK, NS, BL, NST, KT + 1>(kt);
+    }
+}
+
 template <int NK, int BN, int NW>
 __device__ __forceinline__ void conv_panel_body(const ConvArgs& a) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -42,8 +90,11 @@ __device__ __forceinline__ void conv_panel_body(const ConvArgs& a) {
     static_assert(SQ % (NW * 64) == 0, "whole DMA rounds");
     constexpr int BL = SQ / (NW * 64);              // DMA instructions per thread and stage
     constexpr int NST = TN * 4;                     // stores per thread and N tile
-    constexpr int NS = 3;                           // stages in the ring
-    static_assert(BL + 2 * NST <= 63, "vmcnt range");
+    constexpr int NS = panel_stages<NK, BN>();      // stages in the ring
+    constexpr bool EARLY = panel_early<NK>();
+    static_assert(panel_behind_max<NK, NS, BL, NST>() <= 63, "vmcnt range");
+    static_assert(NK >= 4 || (panel_behind<NK, NS, BL, NST>(0) == BL + (NK == 1 ? 2 : 1) * NST && panel_behind<NK, NS, BL, NST>(NK - 1) == BL + (NK == 1 ? 2 : NK == 2 ? 1 : 0) * NST),
+                  "the short-K counts");
 
     extern __shared__ __attribute__((aligned(16))) v4f smem[];
     v4f* Bs = smem;                                 // [NS][BN][12]
@@ -70,17 +121,20 @@ __device__ __forceinline__ void conv_panel_body(const ConvArgs& a) {
         b_voff[i] = (unsigned)(row * a.Kpad * 6 + src * 16);
     }
     const int tile_bytes = BN * a.Kpad * 6;         // weight bytes of one N tile
-    // stage t_ = (n_, kt_) into ring buffer buf_
+    // stage t_ = (n_, kt_) into ring buffer buf_: the stage's constants, then its BL instructions one by one
+#define PEMP_PANEL_DMA_SETUP(buf_, t_, n_, kt_)                                                                   \
+    v4f* const Bd_ = Bs + (buf_) * SQ + wave * 64;                                                                \
+    const int so_ = __builtin_amdgcn_readfirstlane((t_) < T ? (n_) * tile_bytes + (kt_) * 192 : 0);              \
+    const bool in_ = (t_) < T
+#define PEMP_PANEL_DMA_ONE(i_) \
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (lptr_t)(Bd_ + (i_) * NW * 64), 16, in_ ? b_voff[i_] : 0x80000000u, so_, 0, 0)
 #define PEMP_PANEL_DMA(buf_, t_, n_, kt_)                                                                         \
     do {                                                                                                          \
-        v4f* Bd_ = Bs + (buf_) * SQ + wave * 64;                                                                  \
-        const int so_ = __builtin_amdgcn_readfirstlane((t_) < T ? (n_) * tile_bytes + (kt_) * 192 : 0);          \
-        const bool in_ = (t_) < T;                                                                                \
-        _Pragma("unroll") for (int i = 0; i < BL; ++i)                                                            \
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (lptr_t)(Bd_ + i * NW * 64), 16, in_ ? b_voff[i] : 0x80000000u, so_, 0, 0); \
+        PEMP_PANEL_DMA_SETUP(buf_, t_, n_, kt_);                                                                  \
+        _Pragma("unroll") for (int i = 0; i < BL; ++i) PEMP_PANEL_DMA_ONE(i);                                     \
     } while (0)
 
-    // the first three stages fly while the activation panel is loaded and split
+    // the first NS stages fly while the activation panel is loaded and split
 #pragma unroll
     for (int t = 0; t < NS; ++t) PEMP_PANEL_DMA(t, t, t / NK, t % NK);
 
@@ -104,7 +158,7 @@ __device__ __forceinline__ void conv_panel_body(const ConvArgs& a) {
 #pragma unroll
         for (int s = 0; s < 2 * NK; ++s) split3_bf16(x0[s], x1[s], ah[s], am[s], al[s]);
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // stages 0..2 have landed (this thread's pieces)
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // the first NS stages have landed (this thread's pieces)
     __builtin_amdgcn_s_barrier();                              // ... everybody's
     __builtin_amdgcn_sched_barrier(0);
 
@@ -119,16 +173,37 @@ __device__ __forceinline__ void conv_panel_body(const ConvArgs& a) {
             _Pragma("unroll") for (int pl = 0; pl < 3; ++pl)                                                      \
                 bfr[dst_][ni][pl] = Bb_[brow3 + ni * 32 * 12 + pl * 4 + pb_];                                     \
     } while (0)
-    // K16 slice s_: per accumulator lh, hl, mm, mh, hm, hh; the TN accumulators take turns
-#define PEMP_PANEL_MMA(src_, s_)                                                                                  \
+    // K16 slice s_: per accumulator lh, hl, mm, mh, hm, hh; the TN accumulators take turns.  HOOK_(j) follows MFMA j of the slice.
+#define PEMP_PANEL_MMA_HOOKED(src_, s_, HOOK_)                                                                    \
     do {                                                                                                          \
         _Pragma("unroll") for (int pr = 0; pr < 6; ++pr)                                                          \
             _Pragma("unroll") for (int ni = 0; ni < TN; ++ni) {                                                   \
                 const bf16x8 av_ = pr == 0 ? al[s_] : (pr == 2 || pr == 3) ? am[s_] : ah[s_];                     \
                 const bf16x8 bv_ = __builtin_bit_cast(bf16x8, bfr[src_][ni][pr == 1 ? 2 : (pr == 2 || pr == 4) ? 1 : 0]); \
                 acc[ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av_, bv_, acc[ni], 0, 0, 0);                    \
+                HOOK_(pr * TN + ni);                                                                              \
             }                                                                                                     \
     } while (0)
+#define PEMP_PANEL_HOOK_NONE(j_)
+#define PEMP_PANEL_MMA(src_, s_) PEMP_PANEL_MMA_HOOKED(src_, s_, PEMP_PANEL_HOOK_NONE)
+    // the stage's DMA instructions, one behind each of the slice's first MFMAs: a wave's vector memory instructions issue under
+    // its own MFMAs instead of in a burst of all four waves behind the barrier, during which the MFMA pipes stand still
+#define PEMP_PANEL_HOOK_DMA(j_)                                                                                   \
+    if ((j_) < BL) {                                                                                              \
+        __builtin_amdgcn_sched_barrier(0);                                                                        \
+        PEMP_PANEL_DMA_ONE((j_) < BL ? (j_) : 0);                                                                 \
+        __builtin_amdgcn_sched_barrier(0);                                                                        \
+    }
+    // ... and behind them the residual quads of the tile, one per MFMA
+#define PEMP_PANEL_HOOK_DMA_RES(j_)                                                                               \
+    PEMP_PANEL_HOOK_DMA(j_)                                                                                       \
+    else if ((j_) - BL < NST && a.res) {                                                                          \
+        const int k_ = (j_) - BL < NST ? (j_) - BL : 0;                                                           \
+        __builtin_amdgcn_sched_barrier(0);                                                                        \
+        rres[k_] = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(rr, r_off[k_ & 3] + (unsigned)(n * BN + (k_ >> 2) * 32) * 4u, 0, 0)); \
+        __builtin_amdgcn_sched_barrier(0);                                                                        \
+    }
+    static_assert(BL + NST <= 6 * TN, "one instruction per MFMA of a slice");
 
     f32x16 acc[TN];
 #pragma unroll
@@ -146,6 +221,16 @@ __device__ __forceinline__ void conv_panel_body(const ConvArgs& a) {
         r_off[i] = m < a.M ? (unsigned)(m * a.ldr + c4) * 4u : 0x80000000u;
     }
 
+    // the scale / shift quads of N tile n_
+#define PEMP_PANEL_AFFINE(n_)                                                                                     \
+    do {                                                                                                          \
+        _Pragma("unroll") for (int ni = 0; ni < TN; ++ni) {                                                       \
+            const int c = (n_) * BN + ni * 32 + c4;                                                               \
+            scv[ni] = a.scale ? *(const v4f*)(a.scale + c) : v4f{1.f, 1.f, 1.f, 1.f};                             \
+            shv[ni] = a.shift ? *(const v4f*)(a.shift + c) : v4f{0.f, 0.f, 0.f, 0.f};                             \
+        }                                                                                                         \
+    } while (0)
+
     int cur = 0;                                               // ring buffer of the current stage
     PEMP_PANEL_READ(0, 0, 0);
     for (int n = 0; n < ntn; ++n) {
@@ -157,38 +242,36 @@ __device__ __forceinline__ void conv_panel_body(const ConvArgs& a) {
             __builtin_amdgcn_sched_barrier(0);
             PEMP_PANEL_MMA(0, 2 * kt);
             __builtin_amdgcn_sched_barrier(0);
-            // every LDS read of `cur` by this wave has returned; this wave's pieces of the next stage have landed
-            if constexpr (NK == 1) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(BL + 2 * NST) : "memory");
-            else if (kt <= 1) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(BL + NST) : "memory");
-            else asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(BL) : "memory");
-            __builtin_amdgcn_s_barrier();       // ... everybody's: `cur` is free for stage t + 3, `nxt` holds stage t + 1
+            panel_wait<NK, NS, BL, NST>(kt);
+            __builtin_amdgcn_s_barrier();       // ... everybody's: `cur` is free for stage t + NS, `nxt` holds stage t + 1
             __builtin_amdgcn_sched_barrier(0);
             PEMP_PANEL_READ(0, nxt, 0);
-            if (kt == NK - 1) {                 // the tile's epilogue operands: in front of the DMA, so behind it in no count
+            const int t3 = n * NK + kt + NS;                        // the stage that goes into `cur`
+            const int n3 = n + (kt + NS) / NK, k3 = (kt + NS) % NK;
+            if constexpr (!EARLY) {
+                if (kt == NK - 1) {             // the tile's epilogue operands: in front of the DMA, so behind it in no count
+                    PEMP_PANEL_AFFINE(n);
 #pragma unroll
-                for (int ni = 0; ni < TN; ++ni) {
-                    const int c = n * BN + ni * 32 + c4;
-                    scv[ni] = a.scale ? *(const v4f*)(a.scale + c) : v4f{1.f, 1.f, 1.f, 1.f};
-                    shv[ni] = a.shift ? *(const v4f*)(a.shift + c) : v4f{0.f, 0.f, 0.f, 0.f};
+                    for (int i = 0; i < NST; ++i) rres[i] = v4f{0.f, 0.f, 0.f, 0.f};
+                    if (a.res) {
+#pragma unroll
+                        for (int ni = 0; ni < TN; ++ni)
+#pragma unroll
+                            for (int i = 0; i < 4; ++i)
+                                rres[ni * 4 + i] = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(rr, r_off[i] + (unsigned)(n * BN + ni * 32) * 4u, 0, 0));
+                    }
                 }
-#pragma unroll
-                for (int i = 0; i < NST; ++i) rres[i] = v4f{0.f, 0.f, 0.f, 0.f};
-                if (a.res) {
-#pragma unroll
-                    for (int ni = 0; ni < TN; ++ni)
-#pragma unroll
-                        for (int i = 0; i < 4; ++i)
-                            rres[ni * 4 + i] = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(rr, r_off[i] + (unsigned)(n * BN + ni * 32) * 4u, 0, 0));
-                }
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            {
-                const int t3 = n * NK + kt + NS;                    // the stage that goes into `cur`
-                const int n3 = n + (kt + NS) / NK, k3 = (kt + NS) % NK;
+                __builtin_amdgcn_sched_barrier(0);
                 PEMP_PANEL_DMA(cur, t3, n3, k3);
+                __builtin_amdgcn_sched_barrier(0);
+                PEMP_PANEL_MMA(1, 2 * kt + 1);
+            } else {
+                PEMP_PANEL_DMA_SETUP(cur, t3, n3, k3);
+                if (kt == 0) PEMP_PANEL_AFFINE(n);                  // a whole tile ahead of the epilogue
+                __builtin_amdgcn_sched_barrier(0);
+                if (kt == 0) PEMP_PANEL_MMA_HOOKED(1, 2 * kt + 1, PEMP_PANEL_HOOK_DMA_RES);
+                else PEMP_PANEL_MMA_HOOKED(1, 2 * kt + 1, PEMP_PANEL_HOOK_DMA);
             }
-            __builtin_amdgcn_sched_barrier(0);
-            PEMP_PANEL_MMA(1, 2 * kt + 1);
             __builtin_amdgcn_sched_barrier(0);
             cur = nxt;
         }
@@ -225,20 +308,28 @@ __device__ __forceinline__ void conv_panel_body(const ConvArgs& a) {
         __builtin_amdgcn_sched_barrier(0);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");         // no LDS-DMA outlives the block
+#undef PEMP_PANEL_DMA_SETUP
+#undef PEMP_PANEL_DMA_ONE
 #undef PEMP_PANEL_DMA
+#undef PEMP_PANEL_AFFINE
 #undef PEMP_PANEL_READ
+#undef PEMP_PANEL_MMA_HOOKED
+#undef PEMP_PANEL_HOOK_NONE
+#undef PEMP_PANEL_HOOK_DMA
+#undef PEMP_PANEL_HOOK_DMA_RES
 #undef PEMP_PANEL_MMA
 #endif
 }
 
 // waves per SIMD: one block of 4 waves per CU = 1; the 64-column form up to K = 128 fits two blocks (registers and LDS)
 template <int NK, int BN, int NW>
-__global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu((BN == 64 && NK <= 4) ? 2 : 1))) void conv_panel_kernel(ConvArgs a) {
+__global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(panel_two_blocks<NK, BN>() ? 2 : 1))) void conv_panel_kernel(ConvArgs a) {
     conv_panel_body<NK, BN, NW>(a);
 }
 
 constexpr int PANEL_NW = 4;
-template <int BN> constexpr size_t panel_lds() { return (size_t)(3 * BN * 12 + PANEL_NW * 256) * sizeof(v4f); }
+template <int NK, int BN> constexpr size_t panel_lds() { return (size_t)(panel_stages<NK, BN>() * BN * 12 + PANEL_NW * 256) * sizeof(v4f); }
+static_assert(panel_lds<8, 128>() <= 160 * 1024 && 2 * panel_lds<4, 64>() <= 160 * 1024, "LDS of a CU");
 
 template <int BN, int NK = 1>
 static int launch_panel_nk(const ConvArgs& a, hipStream_t st) {
@@ -247,7 +338,7 @@ static int launch_panel_nk(const ConvArgs& a, hipStream_t st) {
         return -1;
     } else {
         if (a.nk == NK)
-            return launch_with_lds(conv_panel_kernel<NK, BN, PANEL_NW>, cdiv(a.M, 32 * PANEL_NW), PANEL_NW * 64, panel_lds<BN>(), st, a,
+            return launch_with_lds(conv_panel_kernel<NK, BN, PANEL_NW>, cdiv(a.M, 32 * PANEL_NW), PANEL_NW * 64, panel_lds<NK, BN>(), st, a,
                                    "conv_panel");
         return launch_panel_nk<BN, NK + 1>(a, st);
     }

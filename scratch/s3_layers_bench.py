@@ -4,7 +4,7 @@ compared.  The multi-tap layers also run the ids that read PRE-SPLIT activations
 reference arithmetic), and the 1x1 layers without a residual also run as producers of a pre-split output ("43s" = id 43 with
 out_split3; its result must be the split of id 43's).  Every cell carries the fastest and the slowest of its --reps timings.  GPU.
 
-    python3 scratch/s3_layers_bench.py [--only 256-256-k3[,...]] [--ids 49,149] [--reps N]
+    python3 scratch/s3_layers_bench.py [--only 256-256-k3[,...]] [--ids 49,149] [--reps N] [--res 0|1]
 
 Inputs come from a seeded CPU generator: the hashes are functions of the kernels alone."""
 import argparse
@@ -67,6 +67,7 @@ def main():
     ap.add_argument("--only", default="", help="cin-cout-kK[-padv]: one layer")
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--ids", default="", help="comma-separated tile ids: only these are timed (a counter run of one kernel)")
+    ap.add_argument("--res", type=int, choices=(0, 1), default=None, help="run the selected layers without / with a residual, whatever their row says")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     N = 50
@@ -74,6 +75,7 @@ def main():
     for layer in LAYERS:
         cin, cout, k, dil, has_res, padv = layer[:6]
         stride, HW = layer[6:] if len(layer) > 6 else (1, 51)
+        has_res = has_res if args.res is None else bool(args.res)
         M = N * HW * HW
         HO = (HW - 1) // stride + 1
         name = f"{cin}-{cout}-k{k}" + ("-padv" if padv else "") + (f"-s{stride}" if stride > 1 else "") + (f"-hw{HW}-res{int(has_res)}" if HW != 51 else "")
