@@ -38,6 +38,8 @@ extern "C" {
 #define PEMP_CONV_OUT_SPLIT3 16u   /* y is written PRE-SPLIT: bf16 [M][Cout / 32][3][32], the split3 pieces of the fp32 result
                                       (see "Pre-split activations" below)                                                     */
 #define PEMP_CONV_IN_SPLIT3 32u    /* x is such a tensor (tile ids 146 / 149 only)                                            */
+#define PEMP_CONV_OUT_SPLIT3_ALSO 64u /* y is written as fp32 as usual AND the same values pre-split, through the pointer passed as
+                                      `residual`: no residual is read (tile ids 146 / 149, pemp_conv2d_nhwc_f32 / _padv_ only)   */
 
 typedef struct pemp_conv_desc {
     int32_t N, H, W;        /* input images, input spatial size                                  */
@@ -145,13 +147,21 @@ int pemp_conv2d_group_nhwc_f32(int n, const pemp_conv_desc* d, const float* cons
  *   PEMP_CONV_OUT_SPLIT3 (producer; ids 41..44, 46, 47, 49): after affine (+ ReLU) every output value is split with the arithmetic
  *   of pemp_pack_split3_bf16 and `y` is written as bf16 [M][Cout / 32][3][32] (M * Cout * 6 bytes): per pixel and 32-channel group
  *   the planes h, m, l -- h + m + l is the fp32 value the same id writes without the flag, exactly.  ldy == Cout; no residual,
- *   split-K, workspace, grouped, panel (71 / 72) or fused-stem form.  The persistent ids 47 / 49 / 149 run as the ids they walk
- *   (43 / 46 / 146: same tiles, same results) -- their kernels have no registers left for the split.
+ *   split-K, workspace, grouped, panel (71 / 72) or fused-stem form.  The persistent ids have PRODUCER variants of their kernels,
+ *   chosen at compile time, with no residual path at all (that is what leaves them registers for the split): 47 and 49 run
+ *   conv_dma2_s3po_kernel<64, 64, ...> / <256, 128, ...>, 149 runs conv_dma2_a3po_kernel<256, 128, ...>; a persistent shape without
+ *   such a variant would run as the id it walks (none today).  Same tiles, K order and split: the bf16 tensor ids 43 / 46 write.
  *   PEMP_CONV_IN_SPLIT3 (consumer; ids 146 = the form of 46, 149 = the form of 49, and no other id): `x` is such a tensor
  *   (ldx == Cin, Cin % 32 == 0), a padding value is the [Cin / 32][3][32] bf16 split of the fp32 vector, behind x like the fp32
  *   one.  Multi-tap convs only; no per-image shift, split-K or workspace; Cout % 128 == 0.  Same MFMA order and epilogue as
  *   41..49 on the same pieces: bit-identical to them on the fp32 tensor.  (No 128 x 128 form: its A tile of 96 KiB would leave one
  *   block per CU.)
+ *   PEMP_CONV_OUT_SPLIT3_ALSO (ids 146 / 149 only: a consumer whose own output has readers of both forms): `y` is written as fp32
+ *   exactly as without the flag (ldy, channel windows included) AND the same values go out pre-split, bf16 [M][Cout / 32][3][32]
+ *   dense, through the pointer passed in the `residual` argument (16-byte aligned; d->ldr is ignored).  Under this flag NO residual
+ *   is read.  Compile-time variants: conv_dma2_a3o_kernel (146) and conv_dma2_a3po_kernel<..., 2> (149).  Refused with
+ *   PEMP_CONV_OUT_SPLIT3, split-K, a workspace, the grouped / DropBlock / statistics / bf16 entries, the stem and every other tile
+ *   id (the panel ids included), and when the two outputs overlap.
  * pemp_pack_split3_bf16: [Cout][Kpad] fp32 (Kpad % 32 == 0) -> [Cout][Kpad / 32][3][32] bf16 (Cout * Kpad * 6 bytes): per row and
  * 32-channel K step the h, m and l planes, channel order unchanged.                                                           */
 int pemp_pack_split3_bf16(const float* w, void* out, int cout, int kpad, void* stream);

@@ -37,6 +37,7 @@ CONV_STEM4 = 4
 CONV_POOL3S2 = 8
 CONV_OUT_SPLIT3 = 16
 CONV_IN_SPLIT3 = 32
+CONV_OUT_SPLIT3_ALSO = 64
 
 #: every symbol include/pemp_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {

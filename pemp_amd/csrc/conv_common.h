@@ -126,16 +126,24 @@ __device__ __forceinline__ int xcd_tile_order(int bid, int nblk) {
 // PEMP_CONV_IN_SPLIT3 (conv_dma2.hip, A3).  A lane owns 8 consecutive channels of one row (4 lanes per row, 16 rows per pass), so
 // that every plane goes out as one 16-byte store and a row's 192 bytes are written by 4 neighbouring lanes.  The value that is
 // split is conv_epilogue_lds_pre's, statement for statement (no residual: the entry refuses one).
-__device__ __forceinline__ void conv_store_split3(const ConvArgs& a, const float* S, int m_base, int n32, int lane) {
-    const bool relu = a.flags & PEMP_CONV_RELU;
+// (conv_split3_affine: the scale / shift quads of the lane's 8 channels n .. n + 7; conv_store_split3_to: the store itself, to y3,
+// with those quads given -- the persistent kernels load them once per tile, beside their other epilogue loads)
+__device__ __forceinline__ void conv_split3_affine(const ConvArgs& a, int n, v4f (&sc)[2], v4f (&sh)[2]) {
     const bool per_img = a.flags & PEMP_CONV_SHIFT_PER_IMAGE;
-    const int r4 = lane >> 2, c8 = (lane & 3) * 8, n = n32 + c8;
-    v4f sc[2] = {{1.f, 1.f, 1.f, 1.f}, {1.f, 1.f, 1.f, 1.f}}, sh[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
+        sc[u] = v4f{1.f, 1.f, 1.f, 1.f};
+        sh[u] = v4f{0.f, 0.f, 0.f, 0.f};
         if (a.scale) sc[u] = *(const v4f*)(a.scale + n + 4 * u);
         if (a.shift && !per_img) sh[u] = *(const v4f*)(a.shift + n + 4 * u);
     }
+}
+
+__device__ __forceinline__ void conv_store_split3_to(const ConvArgs& a, unsigned short* y3, const float* S, int m_base, int n32, int lane,
+                                                     const v4f (&sc)[2], const v4f (&sh)[2]) {
+    const bool relu = a.flags & PEMP_CONV_RELU;
+    const bool per_img = a.flags & PEMP_CONV_SHIFT_PER_IMAGE;
+    const int r4 = lane >> 2, c8 = (lane & 3) * 8, n = n32 + c8;
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
         const int row = r4 + 16 * i;
@@ -160,7 +168,7 @@ __device__ __forceinline__ void conv_store_split3(const ConvArgs& a, const float
         if (m < a.M) {
             bf16x8 h, md, l;
             split3_bf16(o[0], o[1], h, md, l);
-            unsigned short* y = (unsigned short*)a.y + ((size_t)m * (a.Cout >> 5) + (n32 >> 5)) * 96 + c8;
+            unsigned short* y = y3 + ((size_t)m * (a.Cout >> 5) + (n32 >> 5)) * 96 + c8;
             *(bf16x8*)y = h;
             *(bf16x8*)(y + 32) = md;
             *(bf16x8*)(y + 64) = l;
@@ -168,9 +176,18 @@ __device__ __forceinline__ void conv_store_split3(const ConvArgs& a, const float
     }
 }
 
-// OS3: the kernel may be asked for a pre-split output (PEMP_CONV_OUT_SPLIT3: a run-time, wave-uniform branch per sub-tile -- the
+__device__ __forceinline__ void conv_store_split3(const ConvArgs& a, const float* S, int m_base, int n32, int lane) {
+    v4f sc[2], sh[2];
+    conv_split3_affine(a, n32 + (lane & 3) * 8, sc, sh);
+    conv_store_split3_to(a, (unsigned short*)a.y, S, m_base, n32, lane, sc, sh);
+}
+
+// OS3 1: the kernel may be asked for a pre-split output (PEMP_CONV_OUT_SPLIT3: a run-time, wave-uniform branch per sub-tile -- the
 // split3 kernels only, so that the fp32-chain instantiations do not carry it).
-template <int TM, int TN, int NPRE, int EPI = 0, bool DB = false, bool OS3 = false>
+// OS3 2 (PEMP_CONV_OUT_SPLIT3_ALSO, a compile-time variant): y is written as fp32 AND the same values go out pre-split, through
+// the pointer that arrives in a.res -- which is therefore never read as a residual.  After a sub-tile's fp32 stores the patch is
+// still intact (until the trailing lgkmcnt(0)), and conv_store_split3_to recomputes the stored value from it, same statements.
+template <int TM, int TN, int NPRE, int EPI = 0, bool DB = false, int OS3 = 0>
 __device__ __forceinline__ void conv_epilogue_lds_pre(const ConvArgs& a, f32x16 (&acc)[TM][TN], float* S, int m_base,
                                                       int n_base, int lane, const v4f (&pre)[NPRE], float* R = nullptr) {
     constexpr bool PRE = NPRE == TM * TN * 4;       // (an array of 1 = "no prefetched residual": registers, never scratch)
@@ -215,7 +232,7 @@ __device__ __forceinline__ void conv_epilogue_lds_pre(const ConvArgs& a, f32x16 
             for (int e = 0; e < 16; ++e) S[((e & 3) + 8 * (e >> 2) + 4 * lh) * 32 + lr] = acc[mi][ni][e];
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // this wave's writes have landed (DS is in-order per wave)
             v4f s1 = {0.f, 0.f, 0.f, 0.f}, s2 = {0.f, 0.f, 0.f, 0.f};
-            if (OS3 && EPI == 0 && !DB && (a.flags & PEMP_CONV_OUT_SPLIT3)) conv_store_split3(a, S, m_base + mi * 32, n_base + ni * 32, lane);
+            if (OS3 == 1 && EPI == 0 && !DB && (a.flags & PEMP_CONV_OUT_SPLIT3)) conv_store_split3(a, S, m_base + mi * 32, n_base + ni * 32, lane);
             else
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
@@ -225,7 +242,7 @@ __device__ __forceinline__ void conv_epilogue_lds_pre(const ConvArgs& a, f32x16 
                 if (m < a.M) {
                     v4f add = sh;
                     if (per_img) add += *(const v4f*)(a.shift + (size_t)(m / a.HoWo) * a.Cout + n);
-                    if (a.res) {
+                    if (OS3 != 2 && a.res) {
                         if constexpr (PRE) add += pre[(mi * TN + ni) * 4 + i];
                         else add += load_quad(a.res, (size_t)m * a.ldr + n, a.flags & PEMP_CONV_BF16_IO);
                     }
@@ -269,6 +286,12 @@ __device__ __forceinline__ void conv_epilogue_lds_pre(const ConvArgs& a, f32x16 
                 t1 += s1;
                 t2 += s2;
             }
+            if constexpr (OS3 == 2) {
+                static_assert(EPI == 0 && !DB && !PRE, "the second, pre-split output: plain epilogue");
+                v4f sc8[2], sh8[2];
+                conv_split3_affine(a, n_base + ni * 32 + (lane & 3) * 8, sc8, sh8);
+                conv_store_split3_to(a, (unsigned short*)a.res, S, m_base + mi * 32, n_base + ni * 32, lane, sc8, sh8);
+            }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // reads done before the patch is rewritten
         }
         if constexpr (EPI != 0) {
@@ -299,7 +322,7 @@ __device__ __forceinline__ void conv_stats_store(const ConvArgs& a, const float*
     }
 }
 
-template <int TM, int TN, bool DB = false, bool OS3 = false>
+template <int TM, int TN, bool DB = false, int OS3 = 0>
 __device__ __forceinline__ void conv_epilogue_lds(const ConvArgs& a, f32x16 (&acc)[TM][TN], float* S, int m_base,
                                                   int n_base, int lane) {
     const v4f none[1] = {{0.f, 0.f, 0.f, 0.f}};
@@ -372,7 +395,10 @@ int launch_conv_dma2_split3(int shape, ConvArgs a, void* ws, size_t ws_bytes, bo
 int launch_conv_dma2_group_split3(int shape, ConvGroupArgs& g, hipStream_t st);
 // its persistent forms (shapes 3 and 6): a resident grid walks the tiles
 int launch_conv_dma2_split3_persist(int shape, const ConvArgs& a, hipStream_t st);
-// ... and the forms whose activations come pre-split (PEMP_CONV_IN_SPLIT3; shape 6 only), one tile per block or persistent
+// (with PEMP_CONV_OUT_SPLIT3: the producer variant of the shape, which has no residual path; whether a shape has one)
+bool conv_dma2_persist_out_split3(int shape);
+// ... and the forms whose activations come pre-split (PEMP_CONV_IN_SPLIT3; shape 6 only), one tile per block or persistent; with
+// PEMP_CONV_OUT_SPLIT3 / _ALSO in a.flags the variants that store pre-split (_ALSO: the second output's pointer in a.res)
 int launch_conv_dma2_split3_pre(int shape, bool persistent, const ConvArgs& a, hipStream_t st);
 // conv_panel.hip: the activation-stationary split3 form of short-K 1x1 convs (shapes 1 and 2 = 128 / 64 columns at a time)
 bool conv_panel_supported(const ConvArgs& a);

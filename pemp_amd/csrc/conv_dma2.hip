@@ -64,7 +64,7 @@ typedef __attribute__((address_space(3))) void* lptr_t;
 // pre-split padding vector), three 16-byte fragment reads per half step that go straight into the MFMAs.  No split3_bf16 in the K
 // loop; MFMA order, accumulators and epilogue are S3's, and the pieces are those split3_bf16 would have made: bit-identical.
 template <int BM, int BN, int WGM, int NW, bool PADV, int EPI = 0, bool SK = false, bool BF16 = false, bool DB = false, bool R16 = false,
-          bool S3 = false, bool A3 = false>
+          bool S3 = false, bool A3 = false, bool ALSO = false>
 __device__ __forceinline__ void conv_dma2_body(const ConvArgs& a, const int bid, const int nblk) {
 #if defined(__HIP_DEVICE_COMPILE__)     // the host pass only needs the launch stub (buffer-resource builtins / "s" asm operands are device-only)
     constexpr int WGN = NW / WGM;
@@ -73,6 +73,7 @@ __device__ __forceinline__ void conv_dma2_body(const ConvArgs& a, const int bid,
     static_assert(!R16 || (WM == 16 && WN % 16 == 0 && EPI == 0 && !SK && !BF16 && !DB), "R16: 16-row wave tiles, plain epilogue only");
     static_assert(!S3 || (EPI == 0 && !BF16 && !DB && !R16), "S3: plain epilogue, fp32 operands");
     static_assert(!A3 || (S3 && !SK && (BM * 12) % (NW * 64) == 0), "A3: an unsplit S3 form, whole A DMA rounds");
+    static_assert(!ALSO || A3, "a second, pre-split output (PEMP_CONV_OUT_SPLIT3_ALSO; a.res is its pointer): the A3 forms only");
     constexpr int TM = R16 ? 1 : WM / 32, TN = R16 ? WN / 16 : WN / 32;      // R16: TN counts 16-column MFMA tiles
     constexpr int BQ = S3 ? 12 : 8;             // 16-byte quads of B per row and K step in LDS
     static_assert(!S3 || (BN * BQ) % (NW * 64) == 0, "S3: whole B DMA rounds");
@@ -436,6 +437,7 @@ __device__ __forceinline__ void conv_dma2_body(const ConvArgs& a, const int bid,
     // Residual (shortcut) quads of small tiles are requested HERE, in front of the last K step's MFMAs, instead of inside
     // the epilogue where every tile would wait out a full memory latency between its LDS transpose and its stores.
     constexpr bool PRE = !R16 && TM * TN <= 2;
+    static_assert(!ALSO || !PRE, "ALSO: a.res is no residual");
     v4f rpre[PRE ? TM * TN * 4 : 1];
 #pragma unroll
     for (int i = 0; i < (PRE ? TM * TN * 4 : 1); ++i) rpre[i] = v4f{0.f, 0.f, 0.f, 0.f};
@@ -564,11 +566,11 @@ __device__ __forceinline__ void conv_dma2_body(const ConvArgs& a, const int bid,
     static_assert(EPI == 0 || NW * 1024 + NW * TN * 512 <= 64 * (BM + BN), "LDS: statistics area");
     static_assert(NW * 1024 <= 64 * (BM + BN), "LDS: one 4 KB transpose patch per wave");
     if constexpr (R16) conv_epilogue_r16<TN>(a, acc16, (float*)smem + wave * 1024, m0 + wm0, n0 + wn0, lane);
-    else if constexpr (PRE) conv_epilogue_lds_pre<TM, TN, TM * TN * 4, EPI, DB, S3>(a, acc, (float*)smem + wave * 1024, m0 + wm0, n0 + wn0, lane, rpre, Rall + wave * TN * 512);
+    else if constexpr (PRE) conv_epilogue_lds_pre<TM, TN, TM * TN * 4, EPI, DB, S3 ? 1 : 0>(a, acc, (float*)smem + wave * 1024, m0 + wm0, n0 + wn0, lane, rpre, Rall + wave * TN * 512);
     else if constexpr (EPI != 0) {
         const v4f none[1] = {{0.f, 0.f, 0.f, 0.f}};
         conv_epilogue_lds_pre<TM, TN, 1, EPI>(a, acc, (float*)smem + wave * 1024, m0 + wm0, n0 + wn0, lane, none, Rall + wave * TN * 512);
-    } else conv_epilogue_lds<TM, TN, DB, S3>(a, acc, (float*)smem + wave * 1024, m0 + wm0, n0 + wn0, lane);
+    } else conv_epilogue_lds<TM, TN, DB, ALSO ? 2 : S3 ? 1 : 0>(a, acc, (float*)smem + wave * 1024, m0 + wm0, n0 + wn0, lane);
     if constexpr (EPI != 0) {
         __syncthreads();
         conv_stats_store<BN, WGM, NW, TN>(a, Rall, bm, n0, tid);
@@ -647,7 +649,62 @@ __device__ __forceinline__ void conv_epilogue_s3p(const ConvArgs& a, f32x16 (&ac
     }
 }
 
-template <int BM, int BN, int WGM, int NW, bool PADV, bool A3 = false>
+// OUT 1 / 2 (below): the tile goes out pre-split (conv_store_split3_to on every 32 x 32 sub-tile, the scale / shift quads of the lane's
+// 8 channels given), with ALSO behind the fp32 stores of conv_epilogue_s3p's loop -- no residual in either.
+template <int TM, int TN, bool ALSO>
+__device__ __forceinline__ void conv_epilogue_s3p_split(const ConvArgs& a, f32x16 (&acc)[TM][TN], float* S, int m_base, int n_base, int lane,
+                                                        const v4f (&scv)[ALSO ? TN : 1], const v4f (&shv)[ALSO ? TN : 1],
+                                                        const v4f (&sc8)[TN][2], const v4f (&sh8)[TN][2]) {
+    const bool relu = a.flags & PEMP_CONV_RELU;
+    const bool per_img = a.flags & PEMP_CONV_SHIFT_PER_IMAGE;
+    const int lr = lane & 31, lh = lane >> 5;
+    const int rr = lane >> 3, c4 = (lane & 7) * 4;
+    unsigned short* y3 = (unsigned short*)(ALSO ? (void*)a.res : (void*)a.y);
+#pragma unroll
+    for (int ni = 0; ni < TN; ++ni) {
+        const int n = n_base + ni * 32 + c4;
+#pragma unroll
+        for (int mi = 0; mi < TM; ++mi) {
+#pragma unroll
+            for (int e = 0; e < 16; ++e) S[((e & 3) + 8 * (e >> 2) + 4 * lh) * 32 + lr] = acc[mi][ni][e];
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // this wave's writes have landed (DS is in-order per wave)
+            if constexpr (ALSO) {
+                const v4f sc = scv[ni], sh = shv[ni];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const int row = rr + 8 * i;
+                    const int m = m_base + mi * 32 + row;
+                    const v4f v = *(const v4f*)(S + row * 32 + c4);
+                    if (m < a.M) {
+                        v4f add = sh;
+                        if (per_img) add += *(const v4f*)(a.shift + (size_t)(m / a.HoWo) * a.Cout + n);
+                        v4f o;
+                        o.x = __builtin_fmaf(v.x, sc.x, add.x);      // explicit: every epilogue variant must round identically
+                        o.y = __builtin_fmaf(v.y, sc.y, add.y);
+                        o.z = __builtin_fmaf(v.z, sc.z, add.z);
+                        o.w = __builtin_fmaf(v.w, sc.w, add.w);
+                        if (relu) {
+                            o.x = fmaxf(o.x, 0.f);
+                            o.y = fmaxf(o.y, 0.f);
+                            o.z = fmaxf(o.z, 0.f);
+                            o.w = fmaxf(o.w, 0.f);
+                        }
+                        store_quad(a.y, (size_t)m * a.ldy + n, o, 0);
+                    }
+                }
+            }
+            conv_store_split3_to(a, y3, S, m_base + mi * 32, n_base + ni * 32, lane, sc8[ni], sh8[ni]);
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // reads done before the patch is rewritten
+        }
+    }
+}
+
+// OUT: what a tile's epilogue writes.  0: y as fp32 (+ residual), through conv_epilogue_s3p.  1 (PEMP_CONV_OUT_SPLIT3, the PRODUCER
+// variant): y pre-split and nothing else; the kernel has no residual path at all -- no batched residual quads live across the tile
+// loop, no a.res test -- which is what keeps the split store out of scratch (as a run-time branch of OUT 0 it cost the 256 x 128
+// shape 9-23 spilled registers).  2 (PEMP_CONV_OUT_SPLIT3_ALSO): y as fp32 and the same values pre-split through a.res, no residual
+// either.  Tiles, K order and MFMA order do not depend on OUT.
+template <int BM, int BN, int WGM, int NW, bool PADV, bool A3 = false, int OUT = 0>
 __device__ __forceinline__ void conv_dma2_s3p_body(const ConvArgs& a) {
 #if defined(__HIP_DEVICE_COMPILE__)
     constexpr bool S3 = true, R16 = false, BF16 = false;       // the K-loop macros' switches
@@ -662,7 +719,8 @@ __device__ __forceinline__ void conv_dma2_s3p_body(const ConvArgs& a) {
     constexpr int AL = A3 ? BM * AQ / (NW * 64) : BM / RPI, BL = BN * BQ / (NW * 64);
     constexpr int NMF = 6 * TM * TN, NDS = (A3 ? 3 : 2) * TM + 3 * TN, NDMA = AL + BL;
     constexpr int PER = (NDS + NDMA + NMF - 1) / NMF;
-    constexpr int NST = TM * TN * 4;            // epilogue stores per thread of a wave tile inside the output
+    // epilogue stores per thread of a wave tile inside the output: per sub-tile 4 fp32 quads and / or 2 rows x 3 planes
+    constexpr int NST = TM * TN * (OUT == 0 ? 4 : OUT == 1 ? 6 : 10);
     static_assert(NDMA + NST <= 63, "vmcnt range");
     static_assert(NW <= BM / 32 + 3 * BN / 64, "one 4 KB transpose patch per wave inside ONE stage buffer");
 
@@ -820,17 +878,25 @@ __device__ __forceinline__ void conv_dma2_s3p_body(const ConvArgs& a) {
             ++kt;
         }
         const int bl = (kt + pb) & 1;            // the last step's buffer: the transpose patches go there
-        v4f rres[TM * TN * 4], scv[TN], shv[TN];
+        v4f rres[OUT == 0 ? TM * TN * 4 : 1], scv[OUT == 1 ? 1 : TN], shv[OUT == 1 ? 1 : TN];
+        v4f sc8[OUT == 0 ? 1 : TN][2], sh8[OUT == 0 ? 1 : TN][2];      // OUT != 0: the quads of conv_store_split3_to's 8 channels per lane
         auto epi_loads = [&]() {
             const bool per_img = a.flags & PEMP_CONV_SHIFT_PER_IMAGE;
+            if constexpr (OUT != 1) {
 #pragma unroll
-            for (int ni = 0; ni < TN; ++ni) {
-                const int n = n0 + wn0 + ni * 32 + c4_;
-                scv[ni] = a.scale ? *(const v4f*)(a.scale + n) : v4f{1.f, 1.f, 1.f, 1.f};
-                shv[ni] = (a.shift && !per_img) ? *(const v4f*)(a.shift + n) : v4f{0.f, 0.f, 0.f, 0.f};
+                for (int ni = 0; ni < TN; ++ni) {
+                    const int n = n0 + wn0 + ni * 32 + c4_;
+                    scv[ni] = a.scale ? *(const v4f*)(a.scale + n) : v4f{1.f, 1.f, 1.f, 1.f};
+                    shv[ni] = (a.shift && !per_img) ? *(const v4f*)(a.shift + n) : v4f{0.f, 0.f, 0.f, 0.f};
+                }
+            }
+            if constexpr (OUT != 0) {
+#pragma unroll
+                for (int ni = 0; ni < TN; ++ni) conv_split3_affine(a, n0 + wn0 + ni * 32 + (lane & 3) * 8, sc8[ni], sh8[ni]);
+                return;
             }
 #pragma unroll
-            for (int i = 0; i < TM * TN * 4; ++i) rres[i] = v4f{0.f, 0.f, 0.f, 0.f};
+            for (int i = 0; i < (OUT == 0 ? TM * TN * 4 : 1); ++i) rres[i] = v4f{0.f, 0.f, 0.f, 0.f};
             if (a.res) {
 #pragma unroll
                 for (int mi = 0; mi < TM; ++mi)
@@ -849,7 +915,8 @@ __device__ __forceinline__ void conv_dma2_s3p_body(const ConvArgs& a) {
                                  // SIMD (scratch at 128 VGPRs), and 256 x 128 has no registers left under them
 
         float* patch = wave < BM / 32 ? (float*)(As + bl * BM * AQ + wave * 256) : (float*)(Bs + bl * BN * BQ + (wave - BM / 32) * 256);
-        conv_epilogue_s3p<TM, TN>(a, acc, patch, m0 + wm0, n0 + wn0, lane, rres, scv, shv);
+        if constexpr (OUT == 0) conv_epilogue_s3p<TM, TN>(a, acc, patch, m0 + wm0, n0 + wn0, lane, rres, scv, shv);
+        else conv_epilogue_s3p_split<TM, TN, OUT == 2>(a, acc, patch, m0 + wm0, n0 + wn0, lane, scv, shv, sc8, sh8);
         if (!more) {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // no LDS-DMA outlives the block
             break;
@@ -893,6 +960,23 @@ __global__ __launch_bounds__(NW * 64) void conv_dma2_a3_kernel(ConvArgs a) {
 template <int BM, int BN, int WGM, int NW, bool PADV>
 __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2))) void conv_dma2_a3p_kernel(ConvArgs a) {
     conv_dma2_s3p_body<BM, BN, WGM, NW, PADV, true>(a);
+}
+
+// the variants that store pre-split (kernels of their own again): the producer forms of 47 / 49 (conv_dma2_s3po_kernel, OUT 1) and
+// of 149 (conv_dma2_a3po_kernel, OUT 1), and 146 / 149 with the second, pre-split output (conv_dma2_a3o_kernel; _a3po_, OUT 2)
+template <int BM, int BN, int WGM, int NW, bool PADV, int OUT>
+__global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(BM == 64 ? 4 : 2))) void conv_dma2_s3po_kernel(ConvArgs a) {
+    conv_dma2_s3p_body<BM, BN, WGM, NW, PADV, false, OUT>(a);
+}
+
+template <int BM, int BN, int WGM, int NW, bool PADV, int OUT>
+__global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2))) void conv_dma2_a3po_kernel(ConvArgs a) {
+    conv_dma2_s3p_body<BM, BN, WGM, NW, PADV, true, OUT>(a);
+}
+
+template <int BM, int BN, int WGM, int NW, bool PADV>
+__global__ __launch_bounds__(NW * 64) void conv_dma2_a3o_kernel(ConvArgs a) {
+    conv_dma2_body<BM, BN, WGM, NW, PADV, 0, false, false, false, false, true, true, true>(a, blockIdx.x, gridDim.x);
 }
 #undef PEMP_STEP_X
 #undef PEMP_STEP
@@ -1094,11 +1178,13 @@ int launch_conv_dma2_split3(int shape, ConvArgs a, void* ws, size_t ws_bytes, bo
 }
 
 // persistent forms (ids 47, 49; A3: 149): grid = resident blocks (occupancy of the instantiation x CUs, taken once), at most the tile count
-template <class T, bool A3 = false>
+template <class T, bool A3 = false, int OUT = 0>
 static int launch_dma2_s3p(const ConvArgs& a, hipStream_t st) {
     constexpr size_t lds = A3 ? tile_lds_a3<T>() : tile_lds_s3<T>();
     auto s3p_kernel = [](auto padv) {
-        if constexpr (A3) return conv_dma2_a3p_kernel<T::BM, T::BN, T::WGM, T::NW, decltype(padv)::value>;
+        if constexpr (OUT != 0 && A3) return conv_dma2_a3po_kernel<T::BM, T::BN, T::WGM, T::NW, decltype(padv)::value, OUT>;
+        else if constexpr (OUT != 0) return conv_dma2_s3po_kernel<T::BM, T::BN, T::WGM, T::NW, decltype(padv)::value, OUT>;
+        else if constexpr (A3) return conv_dma2_a3p_kernel<T::BM, T::BN, T::WGM, T::NW, decltype(padv)::value>;
         else return conv_dma2_s3p_kernel<T::BM, T::BN, T::WGM, T::NW, decltype(padv)::value>;
     };
     auto kern = a.padv ? s3p_kernel(std::true_type{}) : s3p_kernel(std::false_type{});
@@ -1122,8 +1208,13 @@ static int launch_dma2_s3p(const ConvArgs& a, hipStream_t st) {
     return launch_with_lds(kern, (int)grid, T::NW * 64, lds, st, a, "conv_dma2/split3/persistent");
 }
 
+// the shapes whose persistent form has a producer variant (PEMP_CONV_OUT_SPLIT3): both -- 64 x 64 keeps its 128 registers
+struct FamPersistOut { static constexpr unsigned shapes = shape_bits({3, 6}); static constexpr bool s3 = true; };
+bool conv_dma2_persist_out_split3(int shape) { return in_family<FamPersistOut>(shape); }
+
 int launch_conv_dma2_split3_persist(int shape, const ConvArgs& a, hipStream_t st) {
     if (split3_check(true, shape, a)) return -1;
+    if (a.flags & PEMP_CONV_OUT_SPLIT3) return with_tile<FamPersistOut>(shape, [&](auto t) { return launch_dma2_s3p<decltype(t), false, 1>(a, st); });
     return with_tile<FamPersist>(shape, [&](auto t) { return launch_dma2_s3p<decltype(t)>(a, st); });
 }
 
@@ -1136,8 +1227,10 @@ int launch_conv_dma2_split3_pre(int shape, bool persistent, const ConvArgs& a, h
     // activation once per block; with nothing to split, the squarer wave tile reads 24 KB of LDS per K step instead of 30
     using T = TileA3;
     static_assert(T::BM == kTileShapes[6].bm && T::BN == kTileShapes[6].bn && T::NW == kTileShapes[6].nw, "shape 6");
-    if (persistent) return launch_dma2_s3p<T, true>(a, st);
-    auto kern = a.padv ? conv_dma2_a3_kernel<T::BM, T::BN, T::WGM, T::NW, true> : conv_dma2_a3_kernel<T::BM, T::BN, T::WGM, T::NW, false>;
+    const bool also = a.flags & PEMP_CONV_OUT_SPLIT3_ALSO;
+    if (persistent) return also ? launch_dma2_s3p<T, true, 2>(a, st) : (a.flags & PEMP_CONV_OUT_SPLIT3) ? launch_dma2_s3p<T, true, 1>(a, st) : launch_dma2_s3p<T, true>(a, st);
+    auto kern = also ? (a.padv ? conv_dma2_a3o_kernel<T::BM, T::BN, T::WGM, T::NW, true> : conv_dma2_a3o_kernel<T::BM, T::BN, T::WGM, T::NW, false>)
+                     : (a.padv ? conv_dma2_a3_kernel<T::BM, T::BN, T::WGM, T::NW, true> : conv_dma2_a3_kernel<T::BM, T::BN, T::WGM, T::NW, false>);
     return launch_with_lds(kern, tile_grid<T>(a), T::NW * 64, tile_lds_a3<T>(), st, a, "conv_dma2/split3/presplit");
 }
 

@@ -280,7 +280,7 @@ extern "C" int pemp_conv2d_padv_splitk_nhwc_f32(const pemp_conv_desc* d, const f
 static int conv_fill(const pemp_conv_desc* d, const float* x, const float* w, float* y, const float* scale, const float* shift,
                      const float* residual, const float* pad_value, ConvArgs& a, bool any_taps = false, bool pooled = false) {
     PEMP_REQUIRE(d && x && w && y, "conv2d: null pointer");
-    PEMP_REQUIRE(pooled || !(d->flags & (PEMP_CONV_OUT_SPLIT3 | PEMP_CONV_IN_SPLIT3)),
+    PEMP_REQUIRE(pooled || !(d->flags & (PEMP_CONV_OUT_SPLIT3 | PEMP_CONV_IN_SPLIT3 | PEMP_CONV_OUT_SPLIT3_ALSO)),
                  "conv2d: pre-split activations belong to pemp_conv2d_nhwc_f32 / _padv_ (no grouped / dropblock / statistics / bf16 form)");
     PEMP_REQUIRE(pooled || !(d->flags & PEMP_CONV_POOL3S2), "conv2d: PEMP_CONV_POOL3S2 belongs to pemp_conv2d_nhwc_f32 (no grouped / dropblock / statistics / bf16 form)");
     PEMP_REQUIRE(!pad_value || (!(d->flags & PEMP_CONV_STEM4) && (any_taps || d->KH * d->KW > 1) && ((uintptr_t)pad_value & 15) == 0),
@@ -320,7 +320,7 @@ static int conv_fill(const pemp_conv_desc* d, const float* x, const float* w, fl
     a.ntaps = ntaps;
     a.cin_steps = stem ? 1 : d->Cin / 32;
     a.nk = d->Kpad / 32;
-    if (residual) PEMP_REQUIRE(d->ldr >= d->Cout && d->ldr % 4 == 0 && ((uintptr_t)residual & 15) == 0, "conv2d: ldr must be >= Cout and x4, residual 16-byte aligned");
+    if (residual && !(d->flags & PEMP_CONV_OUT_SPLIT3_ALSO)) PEMP_REQUIRE(d->ldr >= d->Cout && d->ldr % 4 == 0 && ((uintptr_t)residual & 15) == 0, "conv2d: ldr must be >= Cout and x4, residual 16-byte aligned");
     a.sk_ws = nullptr; a.sk_cnt = nullptr; a.sk_full = 0; a.sk_S = 1;
     a.bm_first = 0;
     return 0;
@@ -340,12 +340,24 @@ static int conv2d_impl(const pemp_conv_desc* d, const float* x, const float* w, 
         tile = 3;
     }
     TileId t = decode_tile(tile);
-    // y: bf16 [M][Cout / 32][3][32].  The persistent kernels have no registers left for the split in their epilogue (it would
-    // cost them scratch): with this flag 47 / 49 / 149 run as the ids they walk, 43 / 46 / 146 -- same tiles, same results
+    // y: bf16 [M][Cout / 32][3][32].  The persistent ids 47 / 49 / 149 run their producer variants (compile-time: no residual path,
+    // which is what leaves registers for the split); a persistent shape without one would run as the id it walks -- same tiles,
+    // same results (conv_dma2_persist_out_split3)
     const bool out_split3 = d->flags & PEMP_CONV_OUT_SPLIT3;
     if (out_split3)
         PEMP_REQUIRE(t.family == TILE_SPLIT3 && !t.splitk && !t.panel && !ws && !stem && !residual && a.Cout % 32 == 0 && a.ldy == a.Cout,
                      "conv2d: PEMP_CONV_OUT_SPLIT3 needs an unsplit split3 tile id (41..44, 46, 47, 49, 146, 149), ldy == Cout, no residual / workspace");
+    // y fp32 as without the flag, and the same values pre-split, bf16 [M][Cout / 32][3][32], through `residual` (never read)
+    const bool also_split3 = d->flags & PEMP_CONV_OUT_SPLIT3_ALSO;
+    if (also_split3) {
+        PEMP_REQUIRE(t.presplit && !out_split3 && !ws && !stem && a.Cout % 32 == 0,
+                     "conv2d: PEMP_CONV_OUT_SPLIT3_ALSO needs tile id 146 / 149, no PEMP_CONV_OUT_SPLIT3 / split-K / workspace / stem");
+        PEMP_REQUIRE(residual && ((uintptr_t)residual & 15) == 0,
+                     "conv2d: PEMP_CONV_OUT_SPLIT3_ALSO takes the pre-split tensor (16-byte aligned) in the residual argument; a residual is never read");
+        const char *y0 = (const char*)y, *y1 = y0 + ((size_t)(a.M - 1) * a.ldy + a.Cout) * 4;
+        const char *s0 = (const char*)residual, *s1 = s0 + (size_t)a.M * a.Cout * 6;
+        PEMP_REQUIRE(y1 <= s0 || s1 <= y0, "conv2d: PEMP_CONV_OUT_SPLIT3_ALSO: y and the pre-split tensor overlap");
+    }
     if (d->flags & PEMP_CONV_POOL3S2) {     // the fused stem (conv_stem_pool.hip): y is the pooled tensor
         PEMP_REQUIRE(stem && t.family == TILE_SPLIT3 && !t.splitk && !t.panel && !residual && !pad_value,
                      "conv2d: PEMP_CONV_POOL3S2 needs PEMP_CONV_STEM4 with split3 weights (a tile id 41..49), no residual, no padding value");
@@ -363,7 +375,7 @@ static int conv2d_impl(const pemp_conv_desc* d, const float* x, const float* w, 
         PEMP_REQUIRE(conv_dma2_supported(a) && (long long)a.Cout * a.Kpad * 6 < (1ll << 31),
                      "conv2d: tile %d needs <= 32 taps and operands < 2 GiB (a padding value behind the activations)", tile);
         PEMP_REQUIRE_COUT("conv2d", t.shape, a.Cout);
-        return launch_conv_dma2_split3_pre(t.shape, t.persistent && !out_split3, a, st);
+        return launch_conv_dma2_split3_pre(t.shape, t.persistent, a, st);      // (+ the variants of both ids that store pre-split)
     }
     if (t.family == TILE_SPLIT3) {       // conv_dma2.hip, S3: w from pemp_pack_split3_bf16
         PEMP_REQUIRE(!stem && conv_dma2_supported(a) && (long long)a.Cout * a.Kpad * 6 < (1ll << 31),
@@ -374,7 +386,7 @@ static int conv2d_impl(const pemp_conv_desc* d, const float* x, const float* w, 
                          "conv2d: tile %d needs a 1x1 conv without padding, Kpad <= 256, no padding value / per-image shift / workspace, operands < 2 GiB", tile);
             return launch_conv_panel(t.shape, a, st);
         }
-        if (t.persistent && !out_split3) return launch_conv_dma2_split3_persist(t.shape, a, st);      // same results as the id it walks
+        if (t.persistent && (!out_split3 || conv_dma2_persist_out_split3(t.shape))) return launch_conv_dma2_split3_persist(t.shape, a, st);      // same results as the id it walks
         return launch_conv_dma2_split3(t.shape, a, ws, ws_bytes, t.splitk, st);
     }
     // the fp32 chain: every id falls back towards the pointer-addressed kernels where its own do not apply (same results)
@@ -490,7 +502,7 @@ extern "C" int pemp_conv2d_dropblock_nhwc_f32(const pemp_conv_desc* d, const flo
 extern "C" int pemp_conv2d_bf16_nhwc(const pemp_conv_desc* d, const void* x, const void* w, void* y, const float* scale,
                                      const float* shift, const void* residual, const void* pad_value, int out_f32, void* stream) {
     PEMP_REQUIRE(d && x && w && y, "conv2d_bf16: null pointer");
-    PEMP_REQUIRE(!(d->flags & (PEMP_CONV_STEM4 | PEMP_CONV_BF16_IO | PEMP_CONV_POOL3S2)), "conv2d_bf16: no stem variant; unknown flags");
+    PEMP_REQUIRE(!(d->flags & (PEMP_CONV_STEM4 | PEMP_CONV_BF16_IO | PEMP_CONV_POOL3S2 | PEMP_CONV_OUT_SPLIT3_ALSO)), "conv2d_bf16: no stem variant; unknown flags");
     PEMP_REQUIRE(d->Cin % 64 == 0 && d->ldx % 8 == 0 && d->ldx >= d->Cin && d->Kpad == d->KH * d->KW * d->Cin,
                  "conv2d_bf16: Cin must be a multiple of 64, ldx of 8 (bf16 elements), Kpad = KH*KW*Cin");
     PEMP_REQUIRE(!residual || !out_f32, "conv2d_bf16: a residual comes with a bf16 output");
@@ -516,7 +528,7 @@ extern "C" int pemp_conv2d_bf16_nhwc(const pemp_conv_desc* d, const void* x, con
 static TileId stats_tile(const pemp_conv_desc* d) { return decode_tile(d->tile == 0 ? 23 : d->tile); }
 
 static int conv_stats_fill(const char* what, const pemp_conv_desc* d, ConvArgs& a) {
-    PEMP_REQUIRE(!(d->flags & (PEMP_CONV_STEM4 | PEMP_CONV_RELU | PEMP_CONV_SHIFT_PER_IMAGE | PEMP_CONV_POOL3S2 | PEMP_CONV_OUT_SPLIT3 | PEMP_CONV_IN_SPLIT3)), "%s: plain conv only (no stem / ReLU / per-image shift)", what);
+    PEMP_REQUIRE(!(d->flags & (PEMP_CONV_STEM4 | PEMP_CONV_RELU | PEMP_CONV_SHIFT_PER_IMAGE | PEMP_CONV_POOL3S2 | PEMP_CONV_OUT_SPLIT3 | PEMP_CONV_IN_SPLIT3 | PEMP_CONV_OUT_SPLIT3_ALSO)), "%s: plain conv only (no stem / ReLU / per-image shift)", what);
     PEMP_REQUIRE(d->N > 0 && d->H > 0 && d->W > 0 && d->Cin > 0 && d->Cout > 0 && d->KH > 0 && d->KW > 0 && d->stride > 0 && d->dil > 0 && d->pad >= 0,
                  "%s: bad geometry", what);
     const int ho = (d->H + 2 * d->pad - d->dil * (d->KH - 1) - 1) / d->stride + 1;

@@ -131,6 +131,19 @@ def presplit_pair(prod, cons, x, rows, enabled=True):
     return -(-rows // 256) * (cons.cout // 128) >= least
 
 
+#: p3's output has five readers: the three dilated ASPP branches, the 1x1 branch and the global pool.  With this on, p3 writes it
+#: twice -- fp32 and pre-split (ops.conv2d also_split3) -- and the dilated branches read the split copy; the other readers keep the
+#: fp32 one.  DESIGN.md "Pre-split activations" has what was measured; False leaves the kernels in place and the engines off them.
+PRESPLIT_ASPP = True
+
+
+def presplit_readers(prod, readers, x, rows, enabled=True):
+    """Whether ``prod`` (fed ``x``) may write a second, pre-split copy of its output for the multi-tap layers among ``readers``:
+    every one of them qualifies under ``presplit_pair``'s rule."""
+    multi = [c for c in readers if c.kh * c.kw > 1]
+    return bool(multi) and all(presplit_pair(prod, c, x, rows, enabled and PRESPLIT_ASPP) for c in multi)
+
+
 class Arena:
     """Named activation buffers reused across calls (static addresses make hipGraph replay valid)."""
 
@@ -371,9 +384,17 @@ class ASPPV2Engine:
                 q.w = q.w.to(arena.dtype)
             self.l6_main.w = self.l6_main.w.to(arena.dtype)
 
-    def forward(self, x, tail=None):
+    def branches(self):
+        """The four spatial branch layers as ``forward`` runs them, or None on the copy path / the bf16 variant."""
+        if self.folded is None or self.arena.dtype != torch.float32:
+            return None
+        return [self.folded[i + 1][0] for i in range(4)]
+
+    def forward(self, x, tail=None, xs=None, tail_s=None):
         """``tail`` [>= 4, c]: spare rows right behind ``x`` in the same allocation; the padding vectors are parked there
-        (once per buffer) so that the buffer-addressed conv kernels reach them through the activations' descriptor."""
+        (once per buffer) so that the buffer-addressed conv kernels reach them through the activations' descriptor.
+        ``xs`` / ``tail_s`` [>= 4, c / 32, 3, 32]: the pre-split copy of ``x`` and the spare rows behind it; the multi-tap branches
+        then read ``xs``, with the split of their padding vectors parked in ``tail_s`` the same way."""
         a = self.arena
         n, h, w, c = x.shape
         midc = self.midc
@@ -391,7 +412,17 @@ class ASPPV2Engine:
             qs = [self.folded[i + 1][0] for i in range(4)]
             pvs = [tail[i] if tail is not None else self.folded[i + 1][1] for i in range(4)]
             outs = [cat[..., i * midc:(i + 1) * midc] for i in range(4)]
-            if tail is not None and 0 < n * h * w <= GROUP_MAX_ROWS and x.dtype == f32:
+            if xs is not None:
+                if tail_s.data_ptr() not in self._tails:
+                    for i in range(4):          # the ABI's padding value of a pre-split input: the [Cin / 32][3][32] split of the fp32 vector
+                        tail_s[i].copy_(ops.pack_split3(self.folded[i + 1][1].view(1, c))[0])
+                    self._tails.add(tail_s.data_ptr())
+                for i in range(4):
+                    if qs[i].kh * qs[i].kw > 1:
+                        ops.conv2d(xs, qs[i], out=outs[i], pad_value=tail_s[i], x_split3=True)
+                    else:
+                        ops.conv2d(x, qs[i], out=outs[i])
+            elif tail is not None and 0 < n * h * w <= GROUP_MAX_ROWS and x.dtype == f32:
                 # small step: the four branches read the same x -- one grouped launch, the dilated 3x3 convs first (their
                 # tiles are the long ones; the 1x1 branch's short tiles fill in behind them)
                 order = sorted(range(4), key=lambda i: -qs[i].kh * qs[i].kw)
@@ -426,7 +457,11 @@ class ASPPEngine:
         self.l6_main.shift = None
         self.midc = midc
 
-    def forward(self, x):
+    def branches(self):
+        return self.br[1:] if self.arena.dtype == torch.float32 else None
+
+    def forward(self, x, xs=None):
+        """``xs``: the pre-split copy of ``x``; the multi-tap branches then read it."""
         a = self.arena
         n, h, w, c = x.shape
         midc = self.midc
@@ -435,7 +470,11 @@ class ASPPEngine:
         bias6 = ops.conv2d(g2, self.l6_global, out=a.get("bias6", (n, 1, 1, self.l6_global.cout)))
         cat = a.get("aspp_cat", (n, h, w, 4 * midc))
         outs = [cat[..., i * midc:(i + 1) * midc] for i in range(4)]
-        if 0 < n * h * w <= GROUP_MAX_ROWS:          # small step: one grouped launch (see ASPPV2Engine.forward)
+        if xs is not None:
+            for i in range(4):
+                multi = self.br[i + 1].kh * self.br[i + 1].kw > 1
+                ops.conv2d(xs if multi else x, self.br[i + 1], out=outs[i], x_split3=multi)
+        elif 0 < n * h * w <= GROUP_MAX_ROWS:          # small step: one grouped launch (see ASPPV2Engine.forward)
             order = sorted(range(4), key=lambda i: -self.br[i + 1].kh * self.br[i + 1].kw)
             ops.conv2d_group([x] * 4, [self.br[i + 1] for i in order], [outs[i] for i in order])
         else:
@@ -463,10 +502,16 @@ class PurifierEngine:
         # padding vectors there, inside the buffer-descriptor window of the tensor (conv_dma2.hip, PADV)
         c = self.p3.cout
         flat = a.get("pur3+tail", (n * h * w + 8, c))
-        y = ops.conv2d(y, self.p3, out=flat[:n * h * w].view(n, h, w, c), x_split3=pre)
+        # p3's output has five readers.  Where the dilated ASPP branches qualify (presplit_readers) p3 writes it twice, fp32 and
+        # pre-split -- that copy with its 8 spare rows too, for the split padding vectors -- and they read the split one
+        br = self.aspp.branches() if isinstance(self.aspp, (ASPPV2Engine, ASPPEngine)) else None
+        dual = pre and br is not None and presplit_readers(self.p3, br, x, n * h * w)
+        flat_s = a.get("pur3s+tail", (n * h * w + 8, c // 32, 3, 32), torch.bfloat16) if dual else None
+        ys = flat_s[:n * h * w].view(ops.split3_shape(n, h, w, c)) if dual else None
+        y = ops.conv2d(y, self.p3, out=flat[:n * h * w].view(n, h, w, c), x_split3=pre, also_split3=ys)
         if isinstance(self.aspp, ASPPV2Engine):
-            return self.aspp.forward(y, tail=flat[n * h * w:])
-        return self.aspp.forward(y)
+            return self.aspp.forward(y, tail=flat[n * h * w:], xs=ys, tail_s=flat_s[n * h * w:] if dual else None)
+        return self.aspp.forward(y, xs=ys) if dual else self.aspp.forward(y)
 
 
 class VGG16Engine:

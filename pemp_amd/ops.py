@@ -13,7 +13,7 @@ import os
 import torch
 
 from . import _lib
-from ._lib import ConvDesc, CONV_RELU, CONV_SHIFT_PER_IMAGE, CONV_STEM4, CONV_POOL3S2, CONV_OUT_SPLIT3, CONV_IN_SPLIT3  # noqa: F401
+from ._lib import ConvDesc, CONV_RELU, CONV_SHIFT_PER_IMAGE, CONV_STEM4, CONV_POOL3S2, CONV_OUT_SPLIT3, CONV_IN_SPLIT3, CONV_OUT_SPLIT3_ALSO  # noqa: F401
 
 
 def _stream():
@@ -353,13 +353,16 @@ def _conv_geom(who, x, p, out, residual, dtype=torch.float32, out_dtype=None, x_
 
 
 def conv2d(x, p, out=None, residual=None, shift_override=None, per_image_shift=False, relu=None, tile=0,
-           pad_value=None, splitk=False, dropblock=None, out_split3=False, x_split3=False):
+           pad_value=None, splitk=False, dropblock=None, out_split3=False, x_split3=False, also_split3=None):
     """y = act(scale * conv(x, w) + shift (+ residual)).  x: NHWC view, returns NHWC tensor/view ``out``.
     ``out_split3``: ``out`` is written PRE-SPLIT (bf16 ``split3_shape``: the split3 pieces of the fp32 result, for ONE reader that
     takes it with ``x_split3``); split3 layers only, no residual / split-K / DropBlock, never the panel ids.
     ``x_split3``: ``x`` is such a tensor (a ``pad_value`` then the same split of the [Cin] vector, bf16 [Cin / 32, 3, 32]); multi-tap
     split3 layers with Cout % 128 == 0 only, no per-image shift / split-K / DropBlock -- the ids of SPLIT3_PRESPLIT_TILES, bit-
     identical to the layer on the fp32 tensor.
+    ``also_split3`` (a bf16 ``split3_shape`` tensor of the output's size): ``out`` is written as fp32 as usual AND the same values
+    go to this tensor pre-split, for readers that take it with ``x_split3`` beside readers of the fp32 form; calls with ``x_split3``
+    only (the ids of SPLIT3_PRESPLIT_TILES), no residual, not with ``out_split3``; the two outputs must not overlap.
     ``pad_value`` [Cin]: what out-of-image taps read instead of zero (multi-tap convs; see fold_input_affine).
     ``splitk``: the autotuner may also pick the split-K variants (training path: they are not bit-identical to the rest).
     ``dropblock`` (mask fp32 [N,Ho,Wo], kept count int32 [1]) -- a DropBlock2D record of train_ops.dropblock_mask: the layer's
@@ -375,13 +378,19 @@ def conv2d(x, p, out=None, residual=None, shift_override=None, per_image_shift=F
             raise ValueError(f"conv2d: a pre-split output needs an unsplit split3 tile id, got {tile}")
         if x_split3 and (p.kh * p.kw == 1 or per_image_shift or p.cin % 32 or p.cout % 128):
             raise ValueError("conv2d: a pre-split input needs a multi-tap conv with Cin % 32 == 0 and Cout % 128 == 0, no per-image shift")
+    if also_split3 is not None and (not x_split3 or out_split3 or residual is not None):
+        raise ValueError("conv2d: a second, pre-split output needs a pre-split input (x_split3), no out_split3, no residual")
     if (tile in SPLIT3_PRESPLIT_TILES) != bool(x_split3) and (tile or not x_split3):
         raise ValueError(f"conv2d: the tile ids {SPLIT3_PRESPLIT_TILES} and x_split3 come together (tile {tile})")
     if x.dtype == torch.bfloat16 and not x_split3:
         return _conv2d_bf16(x, p, out, residual, shift_override, per_image_shift, relu, tile, pad_value)
     n, h, w, cin, ldx, ho, wo, out, ldy, ldr = _conv_geom("conv2d", x, p, out, residual, x_split3=x_split3, out_split3=out_split3)
+    if also_split3 is not None and _split3_dims(also_split3, "also_split3") != (n, ho, wo, p.cout):
+        raise ValueError(f"conv2d: also_split3 shape {tuple(also_split3.shape)} != {split3_shape(n, ho, wo, p.cout)}")
     lib = _lib.load()
-    _chk_dev(x, p.w, out, residual)
+    _chk_dev(x, p.w, out, residual, also_split3)
+    if also_split3 is not None:
+        residual = also_split3              # the library takes it in the residual slot (PEMP_CONV_OUT_SPLIT3_ALSO: never read)
     shift = p.shift if shift_override is None else shift_override
     if pad_value is not None:
         _chk_dev(pad_value)
@@ -390,7 +399,7 @@ def conv2d(x, p, out=None, residual=None, shift_override=None, per_image_shift=F
                 raise ValueError(f"conv2d: with x_split3, pad_value must be a contiguous bf16 [{cin // 32}, 3, 32] split vector")
         elif pad_value.numel() != cin or pad_value.dtype != torch.float32 or not pad_value.is_contiguous():
             raise ValueError(f"conv2d: pad_value must be a contiguous fp32 [{cin}] vector")
-    flags = (CONV_OUT_SPLIT3 if out_split3 else 0) | (CONV_IN_SPLIT3 if x_split3 else 0)
+    flags = (CONV_OUT_SPLIT3 if out_split3 else 0) | (CONV_IN_SPLIT3 if x_split3 else 0) | (CONV_OUT_SPLIT3_ALSO if also_split3 is not None else 0)
     if (p.relu if relu is None else relu):
         flags |= CONV_RELU
     if per_image_shift:
@@ -449,13 +458,13 @@ def conv2d(x, p, out=None, residual=None, shift_override=None, per_image_shift=F
 
     if tile == 0:
         key = (p.cin, p.cout, p.kh, p.kw, p.stride, p.pad, p.dil, (6 if dropblock is not None else 4) if splitk else int(p.stem) + (7 if dropblock is not None else 0),
-               n, h, w, int(residual is not None), int(pad_value is not None)) + ((3,) if s3 else ())    # 3: split3 picks
+               n, h, w, int(residual is not None and also_split3 is None), int(pad_value is not None)) + ((3,) if s3 else ())    # 3: split3 picks
         if x_split3 or out_split3:
             # keys of their own: a pick made on the fp32 tensor is never replayed on the split one, nor the reverse
-            key += (146,) * int(x_split3) + (16,) * int(out_split3)
-            # (with a pre-split output the persistent ids run as the ids they walk: not offered twice)
-            cands = lambda: _fits([t for t in (SPLIT3_PRESPLIT_TILES if x_split3 else SPLIT3_TILES)
-                                   if not (out_split3 and TILES[t].persistent_of)], p.cout)
+            # (a pre-split output: 17 where it was 16 -- the persistent ids 47 / 49 / 149 run producer kernels of their own now and are
+            # offered; a pick remembered under 16 was made without them and is not replayed.  64: with the second output)
+            key += (146,) * int(x_split3) + (17,) * int(out_split3) + (64,) * int(also_split3 is not None)
+            cands = lambda: _fits(list(SPLIT3_PRESPLIT_TILES if x_split3 else SPLIT3_TILES), p.cout)
         elif s3:
             # a pick among candidates that include the panel ids is remembered under a key of its own (71): a call of the same
             # geometry that they do not take (a per-image shift, operands of 2 GiB) must never replay it

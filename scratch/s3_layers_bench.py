@@ -1,8 +1,9 @@
 """The heavy layers of the 25-episode eval step (M = 130 050 rows: 50 maps of 51 x 51) alone on the chip, per split3 tile id: us,
 TFLOP/s, bit-identity of every unsplit id with id 43, and a hash of every output (ids 51..56 included) so that two builds can be
 compared.  The multi-tap layers also run the ids that read PRE-SPLIT activations (146 / 149, the input split on the device by the
-reference arithmetic), and the 1x1 layers without a residual also run as producers of a pre-split output ("43s" = id 43 with
-out_split3; its result must be the split of id 43's).  Every cell carries the fastest and the slowest of its --reps timings.  GPU.
+reference arithmetic) -- without a residual also with the second, pre-split output ("149+s" = id 149 with also_split3: the fp32 tensor
+must be id 43's and the second one its split) -- and the 1x1 layers without a residual also run as producers of a pre-split output
+("43s" = id 43 with out_split3, "49s" = the persistent id's producer kernel; the result must be the split of id 43's).  Every cell carries the fastest and the slowest of its --reps timings.  GPU.
 
     python3 scratch/s3_layers_bench.py [--only 256-256-k3[,...]] [--ids 49,149] [--reps N] [--res 0|1]
 
@@ -30,7 +31,9 @@ LAYERS = ((256, 1024, 1, 1, True, False), (512, 1024, 1, 1, False, False), (1024
           (64, 256, 1, 1, True, False, 1, 101), (64, 256, 1, 1, False, False, 1, 101), (256, 512, 1, 1, False, False, 2, 101),
           # the other 3x3 widths (layer2: stride 1 at 51 x 51 and stride 2 from 101 x 101; layer1 at 101 x 101) and layer2's conv1
           (128, 128, 3, 1, False, False), (128, 128, 3, 1, False, False, 2, 101), (64, 64, 3, 1, False, False, 1, 101),
-          (512, 128, 1, 1, False, False))
+          (512, 128, 1, 1, False, False),
+          # a dilated ASPP branch (dilation 12) with its padding vector
+          (256, 256, 3, 12, False, True))
 
 
 def timed(fn, reps, n=5):
@@ -78,7 +81,7 @@ def main():
         has_res = has_res if args.res is None else bool(args.res)
         M = N * HW * HW
         HO = (HW - 1) // stride + 1
-        name = f"{cin}-{cout}-k{k}" + ("-padv" if padv else "") + (f"-s{stride}" if stride > 1 else "") + (f"-hw{HW}-res{int(has_res)}" if HW != 51 else "")
+        name = f"{cin}-{cout}-k{k}" + (f"-d{dil}" if k == 3 and dil > 2 else "") + ("-padv" if padv else "") + (f"-s{stride}" if stride > 1 else "") + (f"-hw{HW}-res{int(has_res)}" if HW != 51 else "")
         if args.only and name not in args.only.split(","):
             continue
         g = torch.Generator().manual_seed(cin * 7 + cout * 3 + k)
@@ -121,11 +124,22 @@ def main():
                 same = torch.equal(out, ref)
                 us, worst = timed(run, args.reps)
                 cells.append(f"{tile}: {us:7.1f}..{worst:6.1f}us {fl / us / 1e6:5.1f}TF{'' if same else ' !'}")
+            if not has_res:                      # ... writing its output twice: fp32 and pre-split (p3, whose readers take both forms)
+                want = presplit(ref)
+                outs = torch.empty_like(want)
+                for tile in keep(PRESPLIT):
+                    run = lambda: ops.conv2d(xs, prm, pad_value=pvs if padv else None, out=out, tile=tile, x_split3=True, also_split3=outs)
+                    out.zero_()
+                    run()
+                    same = torch.equal(out, ref) and torch.equal(outs.view(torch.int16), want.view(torch.int16))
+                    us, worst = timed(run, args.reps)
+                    cells.append(f"{tile}+s: {us:7.1f}..{worst:6.1f}us{'' if same else ' !'}")
+                del want, outs
             del sbuf, xs, pvs
         if k == 1 and not has_res:               # the same layer as the producer of a pre-split output
             want = presplit(ref)
             outs = torch.empty_like(want)
-            for tile in keep((43, 42, 41, 44, 46) if not args.ids else ()):
+            for tile in keep((43, 42, 41, 44, 46, 47, 49) if not args.ids else ()):
                 if cout % ops._tile_bn(tile):
                     continue
                 run = lambda: ops.conv2d(x, prm, out=outs, tile=tile, out_split3=True)
@@ -136,7 +150,8 @@ def main():
             del want, outs
         print(f"{name:>16} k{k} d{dil} res{int(has_res)} | " + " | ".join(cells), flush=True)
         print(f"{'':>16} hash " + " ".join(hashes), flush=True)
-    print("(146 / 149: on the pre-split input; NNs: id NN writing a pre-split output, ! = not the split of id 43's)")
+    print("(146 / 149: on the pre-split input; NNs: id NN writing a pre-split output, ! = not the split of id 43's;")
+    print(" NNN+s: id NNN writing fp32 and the pre-split copy, ! = either differs)")
     print("(! = an unsplit id differs from id 43; ~ = a split-K id differs from id 43, expected where it splits)")
 
 
