@@ -647,6 +647,35 @@ int pemp_canet_cls_bwd_f32(const float* dpred, const float* x, int ldx, const fl
 int pemp_upsample_ce_bwd_f32(const float* pred, const int64_t* target, const float* weight, const double* stats,
                              const float* dlogits, float* dpred, int B, int h, int w, int Ho, int Wo, void* stream);
 
+/* ---- PFENet head training (csrc/pfenet_bwd.hip): adjoints of the streaming PFENet kernels above.  Every output element is
+ * written once by one thread that gathers its terms in a fixed order, every reduction is a two-stage partial sum of fixed
+ * shape (no atomics): bit-stable run to run.
+ * Adjoint of pemp_weighted_gap_f32: dfeat[b*S+s][p][c] (ldd) = dvec[b][c] * (mask / area / S), area = sum_p mask + 5e-4 added
+ * up and rounded as the forward does.  mask [B*S][h][w]; an all-zero mask gives exact zeros.  C % 4 == 0.                */
+int pemp_weighted_gap_bwd_f32(const float* dvec, const float* mask, float* dfeat, int ldd, int B, int S, int h, int w, int C,
+                              void* stream);
+/* Adjoint of nn.AdaptiveAvgPool2d for up to four output sizes at once: dx NHWC [N][H][W][C] (lddx) = sum_k A_k^T g_k with
+ * g_k NHWC [N][bin_h[k]][bin_w[k]][C] (ldg[k]); g, ldg, bin_h, bin_w: host arrays of nbins entries.  Gather form: a pixel adds,
+ * over the bins in index order and the windows that contain it in row-major order, g / kh / kw; dx is written, never read.
+ * Windows follow pemp_adaptive_avgpool_nhwc_f32 (bins larger or smaller than the map).  C % 4 == 0.                      */
+int pemp_adaptive_avgpool_bwd_multi_nhwc_f32(int nbins, const float* const* g, const int* ldg, const int* bin_h, const int* bin_w,
+                                             float* dx, int lddx, int N, int H, int W, int C, void* stream);
+/* Adjoint of pemp_resize_bilinear_ac_nhwc_f32 (hi x wi -> ho x wo, either direction, 1-pixel sides included): dx [N][hi][wi] =
+ * add + A^T dy, dy [N][ho][wo], over C channels; element (n, pixel, c) of a tensor at n * tn + pixel * ld + c * tc as in the
+ * forward.  add may be NULL, and may be dx itself.  The weights are the forward's.                                        */
+int pemp_resize_bilinear_ac_bwd_nhwc_f32(const float* dy, long long dyn, int lddy, int dyc, const float* add, long long addn,
+                                         int ldadd, int addc, float* dx, long long dxn, int lddx, int dxc, int N, int C, int hi,
+                                         int wi, int ho, int wo, void* stream);
+/* The support half of PFENet's init_merge convs (pfenet.py:251-252; the forward runs it as a per-image shift), all bins in one
+ * launch sequence.  g_k NHWC [B][bin_h[k]][bin_w[k]][Cout] (ldg[k]): the gradient at conv k's pre-activation; W[k] / dW[k]: the
+ * support columns of conv k's [Cout][ldw] weight / weight gradient (the pointer already at the first support column);
+ * svec [B][Cin].  c_k[b][co] = sum_p g_k[b][p][co];  dsvec[b][ci] = sum_k sum_co W_k[co][ci] c_k[b][co];
+ * dW_k[co][ci] = sum_b c_k[b][co] svec[b][ci] (written, not accumulated).  Cout % 4 == 0.                                 */
+size_t pemp_pfenet_merge_support_bwd_workspace_bytes(int nbins, int B, int Cout);
+int pemp_pfenet_merge_support_bwd_f32(int nbins, const float* const* g, const int* ldg, const int* bin_h, const int* bin_w,
+                                      const float* const* W, float* const* dW, int ldw, const float* svec, float* dsvec, void* ws,
+                                      size_t ws_bytes, int B, int Cin, int Cout, void* stream);
+
 /* ---- RPMMs inference (networks/rpmms.py) -----------------------------------------------------------------------------
  * The EM of the prototype mixture models (PMMs.EM :65-86) for the mixtures K = 1 | 3 | 6 side by side (10 columns), foreground
  * (side 0, pixel weight m) and background (side 1, weight 1 - m): feat NHWC [B][h][w][C] (ldf), mask [B][h][w], mu0 [10][C]

@@ -159,6 +159,14 @@ SYMBOLS = {
     "pemp_canet_cls_bwd_workspace_bytes": (c_size, [c_int] * 2),
     "pemp_canet_cls_bwd_f32": (c_int, [c_fp, c_fp, c_int, c_fp, c_fp, c_int, c_fp, c_fp, c_fp, c_size] + [c_int] * 3 + [c_fp]),
     "pemp_upsample_ce_bwd_f32": (c_int, [c_fp] * 6 + [c_int] * 5 + [c_fp]),
+    # PFENet head training
+    "pemp_weighted_gap_bwd_f32": (c_int, [c_fp, c_fp, c_fp] + [c_int] * 6 + [c_fp]),
+    "pemp_adaptive_avgpool_bwd_multi_nhwc_f32": (c_int, [c_int, C.POINTER(c_fp)] + [C.POINTER(c_int)] * 3 + [c_fp] + [c_int] * 5
+                                                 + [c_fp]),
+    "pemp_resize_bilinear_ac_bwd_nhwc_f32": (c_int, [c_fp, C.c_longlong, c_int, c_int] * 3 + [c_int] * 6 + [c_fp]),
+    "pemp_pfenet_merge_support_bwd_workspace_bytes": (c_size, [c_int] * 3),
+    "pemp_pfenet_merge_support_bwd_f32": (c_int, [c_int, C.POINTER(c_fp)] + [C.POINTER(c_int)] * 3 + [C.POINTER(c_fp)] * 2
+                                          + [c_int, c_fp, c_fp, c_fp, c_size] + [c_int] * 3 + [c_fp]),
     # RPMMs inference
     "pemp_rpmms_em_f32": (c_int, [c_fp, c_int, c_fp, c_fp, c_fp, c_fp] + [c_int] * 5 + [c_fp]),
     "pemp_rpmms_prob_map_f32": (c_int, [c_fp, c_int, c_fp, c_fp, c_int, C.c_longlong, c_int, c_int, c_int, c_fp]),

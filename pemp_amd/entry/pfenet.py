@@ -1,6 +1,8 @@
 """PFENet evaluation harness on MI355X (counterpart of the reference's entry/pfenet.py: config :27-45, ``Evaluator.test_step``
 :54-60, ``test`` :129-148).  The stage-1 evaluator (batching, sharding, hipGraph replay, fused upsample + CE + argmax +
-tp/fp/fn tail) runs the model's feature-resolution logits (``PFENet.lowres``).  Training is not ported: ``train`` raises."""
+tp/fp/fn tail) runs the model's feature-resolution logits (``PFENet.lowres``).  ``train_head`` trains the head behind the frozen
+trunk (``pemp_amd.train_pfenet``: the reference runs ``layer0 .. layer4`` under ``no_grad``) on synthetic episodes; ``train``, the
+reference's whole procedure on PASCAL-5i, raises."""
 from ..config import Experiment
 from ..networks.pfenet import WGEN_SEED, ModelClass  # noqa: F401
 from .pemp_stage1 import INGREDIENTS, SyntheticEpisodes, eval_episodes, get_val_labels, num_classes  # noqa: F401
@@ -55,6 +57,36 @@ def test(_config, split, shot, query, exp_id, ckpt):
     loss, miou, biou = ev.start_eval_loop(data, num_classes(d["dataset"]), split, _config["te"]["epochs"], logger,
                                           batch=d["test_bs"], dataset_name=d["dataset"])
     return f"Loss: {loss:.4f}, mIoU: {np.mean(miou) * 100:.2f}, bIoU: {np.mean(biou) * 100:.2f}"
+
+
+def head_train_batches(trainer, dcfg, shot, split, rank, steps_per_epoch, device):
+    """-> ``batches(epoch)`` for ``TrainingLoop``: synthetic episodes with the query label at the input size (the reference resizes
+    a training label with its image)."""
+    from .train_stage1 import synthetic_batches
+    return lambda epoch: synthetic_batches(dcfg["bs"], shot, steps_per_epoch, dcfg["seed"] + 7919 * epoch, rank, dcfg["height"],
+                                           dcfg["width"])
+
+
+@ex.command
+def train_head(_config, split, shot, query, seed, loss, sigma, loss_coef, exp_id, ckpt):
+    """``python -m pemp_amd.entry.pfenet train_head with split=0 ckpt=<checkpoint | wgen> [shot=5] [loss_coef=1.]``: PFENet's
+    training procedure (entry/pfenet.py:63-126) -- the head trains on the HIP path behind the frozen trunk, per-epoch evaluation,
+    ``ckpt.pth`` / ``bestckpt.pth`` (reference-loadable state_dicts) under ``<g.model_dir>/<tag>/<id>``."""
+    from .pemp_stage1 import run_training
+    if query != 1:
+        raise ValueError("PFENet takes exactly one query per episode (query=1)")
+    if _config["data"].get("base_dir"):
+        raise ValueError("train_head reads synthetic episodes only: leave data.base_dir empty")
+
+    def make_trainer(logger, dev):
+        from ..core.snapshots import load_for_eval
+        from ..train_pfenet import PFENetTrainer
+        model = ModelClass(shot, logger)
+        load_for_eval(model, _config, exp_id, ckpt, logger, wgen_seed=WGEN_SEED)     # the frozen trunk comes from a checkpoint
+        return PFENetTrainer(model, lr=_config["tr"]["lr"], device=dev, loss=loss, sigma=sigma, loss_coef=loss_coef)
+
+    return run_training(_config, NAME, make_trainer, lambda tr, dev: Evaluator(tr.model, device=dev), split, shot, seed, exp_id,
+                        batches=head_train_batches)
 
 
 @ex.command

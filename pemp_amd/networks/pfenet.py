@@ -3,8 +3,8 @@
 
 The module tree holds the reference's parameters under the reference's ``state_dict`` keys (tests/golden/
 state_keys_pfenet.json); the forward runs on ``pemp_amd.pfenet_engine`` (HIP kernels only).  Unlike the reference the
-constructor reads no ImageNet checkpoint: a trained model comes from ``load_weights`` / ``ckpt``.  Inference only: a
-``train()``-mode forward raises."""
+constructor reads no ImageNet checkpoint: a trained model comes from ``load_weights`` / ``ckpt``.  The module's forward is
+inference only: a ``train()``-mode forward raises; the head trains through ``pemp_amd.train_pfenet.PFENetTrainer``."""
 from pathlib import Path
 
 import torch

@@ -628,3 +628,100 @@ def upsample_ce_bwd(pred=None, target=None, stats=None, weight=None, dlogits=Non
     _lib.check(lib.pemp_upsample_ce_bwd_f32(_p(pred), _p(target), _p(weight), _p(stats), _p(dlogits), _p(out), b, int(h), int(w),
                                             int(ho), int(wo), _stream()), "upsample_ce_bwd")
     return out
+
+
+# -- PFENet head training (csrc/pfenet_bwd.hip) -------------------------------------------------------------------------------
+def weighted_gap_bwd(dvec, mask, S, df):
+    """Adjoint of ``ops.weighted_gap``: dvec contiguous [B,C], mask contiguous fp32 [B*S,h,w] -> writes df NHWC [B*S,h,w,C] (the
+    support rows of the down_supp-output gradient) = dvec m / (sum m + 5e-4) / S."""
+    lib = _lib.load()
+    _chk_dev(dvec, mask, df)
+    from .ops import _nhwc
+    ldd = _nhwc(df, "df")
+    n, h, w, c = df.shape
+    if n % S or tuple(mask.shape) != (n, h, w) or not mask.is_contiguous() or mask.dtype != torch.float32:
+        raise ValueError(f"weighted_gap_bwd: mask must be contiguous fp32 [B*S,h,w] for df {tuple(df.shape)}, S={S}")
+    if tuple(dvec.shape) != (n // S, c) or not dvec.is_contiguous() or dvec.dtype != torch.float32:
+        raise ValueError("weighted_gap_bwd: dvec must be contiguous fp32 [B,C]")
+    _lib.check(lib.pemp_weighted_gap_bwd_f32(_p(dvec), _p(mask), _p(df), ldd, n // S, S, h, w, c, _stream()), "weighted_gap_bwd")
+    return df
+
+
+def _bin_tables(gs, name, n, c):
+    """ctypes tables (pointers, pixel strides, heights, widths) of NHWC views gs[k] [n,h_k,w_k,c]."""
+    from .ops import _nhwc
+    nb = len(gs)
+    if not 1 <= nb <= 4:
+        raise ValueError(f"{name}: 1 to 4 bins per call, got {nb}")
+    ld = []
+    for g in gs:
+        ld.append(_nhwc(g, "g"))
+        if g.shape[0] != n or g.shape[3] != c:
+            raise ValueError(f"{name}: every g must be [{n},h,w,{c}], got {tuple(g.shape)}")
+    ints = C.c_int * nb
+    return nb, (C.c_void_p * nb)(*[g.data_ptr() for g in gs]), ints(*ld), ints(*[g.shape[1] for g in gs]), ints(*[g.shape[2] for g in gs])
+
+
+def adaptive_avgpool_bwd_multi(gs, dx):
+    """Sum of the adjoints of ``ops.adaptive_avgpool(x, bin_k)`` for up to four bins: gs[k] NHWC [N,bin_k,bin_k',C] -> writes dx NHWC
+    [N,H,W,C] (a channel slice of a wider buffer is fine); dx is written once, not accumulated."""
+    lib = _lib.load()
+    _chk_dev(dx, *gs)
+    from .ops import _nhwc
+    lddx = _nhwc(dx, "dx")
+    n, h, w, c = dx.shape
+    nb, ptrs, ld, bh, bw = _bin_tables(gs, "adaptive_avgpool_bwd_multi", n, c)
+    _lib.check(lib.pemp_adaptive_avgpool_bwd_multi_nhwc_f32(nb, ptrs, ld, bh, bw, _p(dx), lddx, n, h, w, c, _stream()),
+               "adaptive_avgpool_bwd_multi")
+    return dx
+
+
+def resize_bilinear_ac_bwd(dy, size=None, add=None, out=None):
+    """Adjoint of ``ops.resize_bilinear_ac``: dy [N,ho,wo,C] (the gradient at the resized map) -> dx [N,hi,wi,C] = add + A^T dy, with
+    ``size`` = (hi, wi) or taken from ``out``.  Views with any (image, pixel, channel) strides, as the forward takes; ``add`` may be
+    ``out`` itself.  ``out`` None: a new contiguous NHWC tensor."""
+    lib = _lib.load()
+    _chk_dev(dy, add, out)
+    from .ops import _strides4
+    n, ho, wo, c = dy.shape
+    if out is None:
+        hi, wi = (size, size) if isinstance(size, int) else size
+        out = torch.empty((n, hi, wi, c), dtype=torch.float32, device=dy.device)
+    hi, wi = out.shape[1:3]
+    if tuple(out.shape) != (n, hi, wi, c) or (size is not None and (hi, wi) != ((size, size) if isinstance(size, int) else tuple(size))):
+        raise ValueError(f"resize_bilinear_ac_bwd: out {tuple(out.shape)} does not fit dy {tuple(dy.shape)} and size {size}")
+    if add is not None and tuple(add.shape) != tuple(out.shape):
+        raise ValueError("resize_bilinear_ac_bwd: add must have out's shape")
+    yn, yp, yc = _strides4(dy, "dy")
+    xn, xp, xc = _strides4(out, "out")
+    an, ap, ac = _strides4(add, "add") if add is not None else (0, 0, 0)
+    _lib.check(lib.pemp_resize_bilinear_ac_bwd_nhwc_f32(_p(dy), yn, yp, yc, _p(add), an, ap, ac, _p(out), xn, xp, xc, n, c, hi, wi, ho,
+                                                        wo, _stream()), "resize_bilinear_ac_bwd")
+    return out
+
+
+def pfenet_merge_support_bwd(gs, w_s, svec, dw_s, ws_cache=None):
+    """The support half of PFENet's ``init_merge`` convs, all bins at once: gs[k] NHWC [B,bin_k,bin_k,Cout] (the gradient at conv
+    k's pre-activation), w_s[k] / dw_s[k] the support columns of conv k's weight / weight gradient as [Cout,Cin] views of unit
+    column stride and one common row stride, svec contiguous [B,Cin] -> dsvec [B,Cin]; writes every dw_s[k]."""
+    lib = _lib.load()
+    _chk_dev(svec, *gs, *w_s, *dw_s)
+    b, cin = svec.shape
+    if not svec.is_contiguous() or svec.dtype != torch.float32:
+        raise ValueError("pfenet_merge_support_bwd: svec must be contiguous fp32 [B,Cin]")
+    cout = gs[0].shape[3]
+    nb, ptrs, ld, bh, bw = _bin_tables(gs, "pfenet_merge_support_bwd", b, cout)
+    if len(w_s) != nb or len(dw_s) != nb:
+        raise ValueError("pfenet_merge_support_bwd: one weight and one weight gradient per bin")
+    ldw = w_s[0].stride(0)
+    for t in (*w_s, *dw_s):
+        if t.dim() != 2 or t.dtype != torch.float32 or tuple(t.shape) != (cout, cin) or t.stride(1) != 1 or t.stride(0) != ldw:
+            raise ValueError(f"pfenet_merge_support_bwd: weights must be fp32 [{cout},{cin}] views with unit column stride and one "
+                             "row stride")
+    arr = C.c_void_p * nb
+    dsvec = torch.empty((b, cin), dtype=torch.float32, device=svec.device)
+    ws = _ws(lib.pemp_pfenet_merge_support_bwd_workspace_bytes(nb, b, cout), svec.device, ws_cache, ("merge_s_bwd", nb, b, cout))
+    _lib.check(lib.pemp_pfenet_merge_support_bwd_f32(nb, ptrs, ld, bh, bw, arr(*[t.data_ptr() for t in w_s]),
+                                                     arr(*[t.data_ptr() for t in dw_s]), ldw, _p(svec), _p(dsvec), _p(ws), ws.numel(),
+                                                     b, cin, cout, _stream()), "pfenet_merge_support_bwd")
+    return dsvec
