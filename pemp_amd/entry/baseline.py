@@ -4,6 +4,7 @@ stage 1; the model is ``pemp_amd.networks.baseline.Baseline`` (full-resolution m
 through the adjoint of the bilinear upsample)."""
 from ..config import Experiment
 from ..networks.baseline import ModelClass, net_ingredient  # noqa: F401
+from ..train_baseline import BaselineTrainer
 from .pemp_stage1 import INGREDIENTS, Evaluator, SyntheticEpisodes, eval_episodes, get_val_labels, num_classes  # noqa: F401
 
 NAME = "Baseline"
@@ -56,17 +57,11 @@ def train(_config, split, shot, seed, loss, sigma, exp_id):
 
 
 
-class Trainer:
+class Trainer(BaselineTrainer):
     """``train_step(*inputs, qry_msk=...)`` of the reference's baseline Trainer (entry/baseline.py:54-62)."""
 
-    def __new__(cls, model, **kw):
-        from ..train_baseline import BaselineTrainer
-
-        class _Trainer(BaselineTrainer):
-            def train_step(self, *inputs, qry_msk=None):
-                return super().train_step(*inputs, qry_msk=qry_msk.view(-1, *qry_msk.shape[-2:]))
-
-        return _Trainer(model, **kw)
+    def train_step(self, *inputs, qry_msk=None):
+        return super().train_step(*inputs, qry_msk=qry_msk.view(-1, *qry_msk.shape[-2:]))
 
 
 if __name__ == "__main__":

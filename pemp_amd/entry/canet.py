@@ -28,6 +28,7 @@ from .. import ops, synth
 from ..config import Experiment
 from ..core.metrics import Accumulator, FewShotMetric
 from ..networks.canet import WGEN_SEED, ModelClass, net_ingredient  # noqa: F401
+from ..train_canet import CANetTrainer
 from .pemp_stage1 import INGREDIENTS, DeviceRoundTable, SyntheticEpisodes, get_val_labels, num_classes  # noqa: F401
 from .pemp_stage1 import Evaluator as _Evaluator
 
@@ -272,40 +273,34 @@ class HistorySlots:
         return read, [r if last[k] == j else -1 for j, (k, r) in enumerate(zip(keys, rows))]
 
 
-class HeadTrainer:
+class HeadTrainer(CANetTrainer):
     """``train_step(sup_img, sup_mask, qry_img, keys, qry_msk=...)`` of the reference's CANet Trainer (entry/canet.py:107-116,
     130-140) -> (loss, softmax): ``CANetTrainer`` with the history in a device table addressed by ``HistorySlots``."""
 
-    def __new__(cls, model, **kw):
-        from ..train_canet import CANetTrainer
+    def __init__(self, model, **kw):
+        super().__init__(model, **kw)
+        self.history, self.table = HistorySlots(), None
 
-        class _Trainer(CANetTrainer):
-            def __init__(self, model, **kw):
-                super().__init__(model, **kw)
-                self.history, self.table = HistorySlots(), None
+    def start_epoch(self, capacity, H, W):
+        """Forget every key; the table is allocated once per capacity and feature size (rows need no clearing: a key's first
+        episode reads slot -1)."""
+        h, w = self.model.feature_hw(H, W)
+        if self.table is None or self.table.shape[0] < capacity or tuple(self.table.shape[-2:]) != (h, w):
+            self.table = torch.zeros((max(int(capacity), 1), 2, h, w), dtype=torch.float32, device=self.device)
+        self.history.clear()
 
-            def start_epoch(self, capacity, H, W):
-                """Forget every key; the table is allocated once per capacity and feature size (rows need no clearing: a key's
-                first episode reads slot -1)."""
-                h, w = self.model.feature_hw(H, W)
-                if self.table is None or self.table.shape[0] < capacity or tuple(self.table.shape[-2:]) != (h, w):
-                    self.table = torch.zeros((max(int(capacity), 1), 2, h, w), dtype=torch.float32, device=self.device)
-                self.history.clear()
-
-            def train_step(self, sup_img, sup_mask, qry_img, keys, qry_msk=None):
-                qry_msk = qry_msk.view(-1, *qry_msk.shape[-2:])
-                if not self.model.use_history:
-                    return super().train_step(sup_img, sup_mask, qry_img, qry_msk=qry_msk)
-                if self.table is None:
-                    self.start_epoch(len(keys), *sup_img.shape[-2:])
-                read, write = self.history.slots(list(keys))
-                if max(write) >= self.table.shape[0]:
-                    raise ValueError("the history table is too small for this epoch: call start_epoch with its key count")
-                rs = torch.tensor(read, dtype=torch.int32).to(self.device, non_blocking=True)
-                ws = torch.tensor(write, dtype=torch.int32).to(self.device, non_blocking=True)
-                return super().train_step(sup_img, sup_mask, qry_img, qry_msk=qry_msk, table=self.table, read_slot=rs, write_slot=ws)
-
-        return _Trainer(model, **kw)
+    def train_step(self, sup_img, sup_mask, qry_img, keys, qry_msk=None):
+        qry_msk = qry_msk.view(-1, *qry_msk.shape[-2:])
+        if not self.model.use_history:
+            return super().train_step(sup_img, sup_mask, qry_img, qry_msk=qry_msk)
+        if self.table is None:
+            self.start_epoch(len(keys), *sup_img.shape[-2:])
+        read, write = self.history.slots(list(keys))
+        if max(write) >= self.table.shape[0]:
+            raise ValueError("the history table is too small for this epoch: call start_epoch with its key count")
+        rs = torch.tensor(read, dtype=torch.int32).to(self.device, non_blocking=True)
+        ws = torch.tensor(write, dtype=torch.int32).to(self.device, non_blocking=True)
+        return super().train_step(sup_img, sup_mask, qry_img, qry_msk=qry_msk, table=self.table, read_slot=rs, write_slot=ws)
 
 
 def head_train_batches(trainer, dcfg, shot, split, rank, steps_per_epoch, device):

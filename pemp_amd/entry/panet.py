@@ -9,6 +9,7 @@ import torch.distributed as dist
 from .. import ops
 from ..config import Experiment
 from ..networks.panet import ModelClass, align_forward, net_ingredient  # noqa: F401
+from ..train_baseline import PANetTrainer
 from .pemp_stage1 import INGREDIENTS, SyntheticEpisodes, eval_episodes, get_val_labels, num_classes  # noqa: F401
 from .pemp_stage1 import Evaluator as _Evaluator
 
@@ -73,17 +74,11 @@ class Evaluator(_Evaluator):
         return (loss, float((tot[0] / tot[1].clamp(min=1.0)).item())), miou, biou
 
 
-class Trainer:
+class Trainer(PANetTrainer):
     """``train_step(*inputs, qry_msk=...)`` -> (loss, aux_loss) of the reference's PANet Trainer (entry/panet.py:103-110)."""
 
-    def __new__(cls, model, **kw):
-        from ..train_baseline import PANetTrainer
-
-        class _Trainer(PANetTrainer):
-            def train_step(self, *inputs, qry_msk=None):
-                return super().train_step(*inputs, qry_msk=qry_msk.view(-1, *qry_msk.shape[-2:]))
-
-        return _Trainer(model, **kw)
+    def train_step(self, *inputs, qry_msk=None):
+        return super().train_step(*inputs, qry_msk=qry_msk.view(-1, *qry_msk.shape[-2:]))
 
 
 @ex.command

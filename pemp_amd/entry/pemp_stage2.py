@@ -8,6 +8,7 @@ from .. import ops
 from ..core.metrics import Accumulator, FewShotMetric  # noqa: F401
 from ..networks.pemp_stage2 import ModelClass, PriorNet, net_ingredient  # noqa: F401
 from ..config import Experiment
+from ..train_stage2 import Stage2Trainer
 from .pemp_stage1 import Evaluator as _Stage1Evaluator
 from .pemp_stage1 import INGREDIENTS, SyntheticEpisodes, eval_episodes, allreduce_round, get_val_labels, num_classes, shard_indices  # noqa: F401
 
@@ -67,18 +68,12 @@ class Evaluator(_Stage1Evaluator):
         return am.cpu().numpy(), float(st[:, 0].sum() / max(st[:, 1].sum(), 1.0))
 
 
-class Trainer:
+class Trainer(Stage2Trainer):
     """``train_step(*inputs, qry_msk=...)`` of the reference's stage-2 Trainer (entry/pemp_stage2.py:67-83): the
     frozen stage-1 model gives the prior, stage 2 steps on the HIP training path (no clipping for ResNet-50)."""
 
-    def __new__(cls, stage1, model, **kw):
-        from ..train_stage2 import Stage2Trainer
-
-        class _Trainer(Stage2Trainer):
-            def train_step(self, *inputs, qry_msk=None):
-                return super().train_step(*inputs, qry_msk=qry_msk.view(-1, *qry_msk.shape[-2:]))
-
-        return _Trainer(stage1, model, **kw)
+    def train_step(self, *inputs, qry_msk=None):
+        return super().train_step(*inputs, qry_msk=qry_msk.view(-1, *qry_msk.shape[-2:]))
 
 
 def load_stage1(_config, s1, logger=None, device=None):

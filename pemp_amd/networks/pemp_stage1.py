@@ -6,6 +6,7 @@ Same module surface (``net_ingredient``, ``ModelClass``, ``PEMPStage1``, ``pretr
 libpemp_hip.so through ``pemp_amd.engine`` / ``pemp_amd.ops`` and raises if that library is
 missing or the tensors are not on the GPU.
 """
+import gc
 from collections import OrderedDict
 from pathlib import Path
 
@@ -201,6 +202,9 @@ class _HeadMixin:
                     warm(static_in)
             torch.cuda.current_stream().wait_stream(side)
             torch.cuda.synchronize()
+            # a dead model and its engine form a reference cycle that owns hipGraphs; the collection that destroys them must
+            # not happen to run inside a capture (the runtime aborts), and torch.cuda.graph no longer collects on entry
+            gc.collect()
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph), torch.no_grad():
                 out = capture(static_in)

@@ -82,18 +82,10 @@ class BaselineTrainer(Stage1Trainer):
 
     def __init__(self, model, lr=1e-3, momentum=0.9, weight_decay=5e-4, device=None, loss="ce", sigma=5.0,
                  use_graph=False):
-        from .core import losses
         from .networks.baseline import net_ingredient
-        self.device = device if device is not None else torch.device("cuda", torch.cuda.current_device())
-        self.model = model
-        model.train()
+        self._setup(model, device, lr, momentum, weight_decay, 0.0, loss, sigma, use_graph, net_ingredient.cfg["dist_scalar"])
         eng_cls = _VGGEngine if model.backbone_name == "vgg16" else _ResNetProjectionEngine
         self.eng = eng_cls(model, self.device)
-        self.lr, self.momentum, self.wd, self.max_norm = lr, momentum, weight_decay, 0.0
-        self.protos, self.dist_scalar = 0, net_ingredient.cfg["dist_scalar"]
-        self.last_grad_norm, self.nesterov, self.optimizer = None, False, None
-        self.use_graph, self._graphs = use_graph, {}
-        self.loss_obj = losses.get({"loss": loss, "sigma": sigma})
 
     def _head_hip(self, feat, sup_mask, qry_msk, B, S, Q):
         loss, pred, dfeat = self._main_head(feat, sup_mask, qry_msk, B, S, Q)

@@ -7,8 +7,8 @@ residual blocks, the ASPP, ``layer6``, ``layer7``.  The trunk's forward is NOT t
 sets ``requires_grad = False`` (networks/backbones.py:56-62,93-95), the reference never calls ``eval()`` on the encoder, so in a
 training step its BatchNorms normalise with the statistics of the batch -- all B(S+1) images -- and move their running
 statistics (momentum 0.1); the reference-made fixtures (tests/golden/make_golden_canet_train.py) are reproduced only that way.
-The trunk therefore runs on the train-mode conv -> batch-statistics BatchNorm chain of ``Stage1TrainEngine`` (forward only,
-weights packed once), and the per-epoch evaluation sees the moved running statistics, as the reference's does.
+The trunk therefore runs on the train-mode conv -> batch-statistics BatchNorm chain of ``train_engine.HeadTrainEngine`` (forward
+only, weights packed once), and the per-epoch evaluation sees the moved running statistics, as the reference's does.
 
 Layout (forward as ``canet_engine``):
 
@@ -19,8 +19,8 @@ Layout (forward as ``canet_engine``):
 * ``residual_1``'s first conv sees 258 channels (256 features + 2 history): its weight is re-packed every step into a
   288-channel form for the forward conv, its input lives in a 320-channel buffer (channels 258.. zero) that the weight-gradient
   kernel reads whole, and its input gradient uses the first 256 rows of the mirrored weight (the history has no gradient);
-* the ASPP + ``layer6`` are ``Stage2TrainEngine._aspp_forward/_aspp_backward`` (same module shapes) with layer6's ReLU;
-* ``layer7`` (256 -> 2) runs forward as a 64-channel padded conv and backward on ``train_ops.canet_cls_bwd``;
+* the ASPP + ``layer6`` are ``train_stage2._ASPPNoBN`` (the mixin of the stage-2 engine: same module shapes) with layer6's ReLU;
+* ``layer7`` (256 -> 2) is a ``train_engine._Cls2``: forward as a 64-channel padded conv, backward on ``train_ops.canet_cls_bwd``;
 * loss: bilinear upsample + CE fused (``ops.eval_tail``), its gradient at the low-resolution logits by
   ``train_ops.upsample_ce_bwd``.
 
@@ -28,91 +28,45 @@ Dropout2d follows stage 2: Philox masks per (image, channel), or given uniforms 
 names ``layer5.2, layer55.2, aspp_0.2 .. aspp_4.2, layer6.2``, rows in the engine's image order) for the parity tests.
 """
 import torch
-import torch.nn as nn
 
 from . import canet_engine, ops, train_ops as T
-from .engine import logits_nchw
 from .ops import ConvParams
-from .train_engine import FlatParams, GradBuckets, Stage1Trainer, _BN, _Conv, _enqueue_wgrad, conv2d
-from .train_stage2 import Stage2TrainEngine
+from .train_engine import HeadTrainEngine, Stage1Trainer, _BN, _Cls2, _Conv, _FrozenConv, _SliceWgrad, _enqueue_wgrad, conv2d
+from .train_stage2 import _ASPPNoBN
 
 MID = canet_engine.MID
 HIST_FWD = canet_engine.HIST_CIN        # 288: what the forward conv of residual_1 reads (Cin % 32)
 HIST_WGRAD = 320                        # ... and what its weight-gradient kernel reads (Cin % 64); channels 258.. are zero
 
 
-class _SliceWgradK:
-    """Weight gradient of a k x k conv whose weight is a channel slice of a larger KRSC matrix, or whose input carries zero
-    padding channels: computed into a dense [Cout, taps, cin] temporary, its first ``dst.shape[2]`` channels copied into
-    ``dst`` (a [Cout, taps, channels] view of the parameter's gradient) -- ``_SliceWgrad`` for any kernel size."""
-
-    def __init__(self, dst, cin, conv):
-        self.dst = dst
-        self.prm = ConvParams(None, None, None, cin, conv.cout, conv.kh, conv.kw, 1, conv.pad, conv.dil, conv.kh * conv.kw * cin,
-                              False, False)
-
-    def _wgrad_now(self, x, g, ws):
-        p = self.prm
-        tmp = torch.empty((p.cout, p.kpad), dtype=torch.float32, device=x.device)
-        T.conv_wgrad(x, g, p, tmp, ws_cache=ws)
-        self.dst.copy_(tmp.view(p.cout, p.kh * p.kw, p.cin)[:, :, :self.dst.shape[2]])
+_FROZEN_TRUNK = ("CANet trunk training (freeze_backbone=False) is not built: the HIP path trains the head behind a frozen trunk, "
+                 "as the reference's configuration does")
 
 
-class _FrozenConv(_Conv):
-    """A conv of the frozen trunk: its forward parameters are packed once."""
-
-    def __init__(self, flat, conv, stem=False):
-        super().__init__(flat, conv, stem)
-        self._packed = {}
-
-    def fwd_params(self, relu=False, with_bias=True):
-        key = (relu, with_bias)
-        if key not in self._packed:
-            self._packed[key] = super().fwd_params(relu, with_bias)
-        return self._packed[key]
-
-
-class CANetHeadTrainEngine(Stage2TrainEngine):
-    """Train-mode forward of the frozen trunk (batch-statistics BatchNorm, no tape), forward + backward of CANet's head.  Shares
-    the conv -> BatchNorm forward with the stage-1 engine and ``_drop`` / the ASPP forward and backward with the stage-2 engine;
-    their constructor (a trainable trunk, a purifier) is replaced."""
+class CANetHeadTrainEngine(_ASPPNoBN, HeadTrainEngine):
+    """Train-mode forward of the frozen trunk, forward + backward of CANet's head; the ASPP is stage 2's."""
     aspp_drop_names = tuple(f"aspp_{i}.2" for i in range(5))
 
-    def __init__(self, model, device):                                   # noqa: super().__init__ builds a trainable trunk
+    def __init__(self, model, device):
         if not model.freeze_backbone:
-            raise ValueError("CANet trunk training (freeze_backbone=False) is not built: the HIP path trains the head behind a "
-                             "frozen trunk, as the reference's configuration does")
+            raise ValueError(_FROZEN_TRUNK)
         model.maybe_fix_params()
-        self.model, self.device = model, device
-        self.flat = FlatParams(model, device)
-        for b in model.buffers():
-            b.data = b.data.to(device)
-        for p in model.parameters():
-            if not p.requires_grad:
-                p.data = p.data.to(device)
-        self.ws, self.draws, self.tape = {}, None, None
+        super().__init__(model, device, [model.encoder])
         self.drop_rate2 = float(model.layer5[2].p)
-        self.rng = T.RandomStream(torch.initial_seed(), device)
+        self.use_history = bool(model.use_history)
+        self.w_hist = torch.zeros((MID, 9, HIST_FWD), dtype=torch.float32, device=device) if self.use_history else None
+        self.hist_in = {}
+
+    def _init_handles(self, model):
         f, bb = self.flat, model.encoder
         self.stem = (_FrozenConv(f, bb.conv1, stem=True), _BN(bb.bn1))
-        self.blocks = [dict(c1=_FrozenConv(f, blk.conv1), b1=_BN(blk.bn1), c2=_FrozenConv(f, blk.conv2), b2=_BN(blk.bn2),
-                            c3=_FrozenConv(f, blk.conv3), b3=_BN(blk.bn3),
-                            ds=(_FrozenConv(f, blk.downsample[0]), _BN(blk.downsample[1])) if blk.downsample is not None else None)
-                       for name in ("layer1", "layer2", "layer3") for blk in getattr(bb, name)]
+        self.blocks = self._frozen([*bb.layer1, *bb.layer2, *bb.layer3])
         self.f2_block = len(bb.layer1) + len(bb.layer2) - 1               # layer2's last block: the first half of cat((f2, f3))
-        self.bn_counters = [m.num_batches_tracked for m in bb.modules() if isinstance(m, nn.BatchNorm2d)]
-        self.use_history = bool(model.use_history)
         self.l5, self.l55 = _Conv(f, model.layer5[0]), _Conv(f, model.layer55[0])
         self.res = [(_Conv(f, seq[1]), _Conv(f, seq[3])) for seq in (model.residual_1, model.residual_2, model.residual_3)]
         self.aspp_conv = [_Conv(f, getattr(model, f"aspp_{i}")[0]) for i in range(5)]
-        self.l6, self.l7 = model.layer6[0], model.layer7
+        self.l6, self.l7 = model.layer6[0], _Cls2(f, model.layer7, self.device)
         self.midc = MID
-        self.flat.build_dgrad_mirror()
-        self.w_hist = torch.zeros((MID, 9, HIST_FWD), dtype=torch.float32, device=device) if self.use_history else None
-        self.w_cls = torch.zeros((64, MID), dtype=torch.float32, device=device)
-        self.b_cls = torch.zeros(64, dtype=torch.float32, device=device)
-        self.hist_in = {}
-        self.buckets = GradBuckets(self.flat.grad, [], side_stream=self.flat.side_stream)     # one bucket: the head is 25 MB
 
     # -- forward --------------------------------------------------------------------------------
     def _trunk_forward(self, images_list):
@@ -120,11 +74,8 @@ class CANetHeadTrainEngine(Stage2TrainEngine):
         torch._foreach_add_(self.bn_counters, 1)                          # every BatchNorm runs exactly once per step
         y, _ = self._cbn_fwd(self._pack(images_list), *self.stem, relu=True)
         x, _ = T.maxpool_idx(y, 3, 2, 1, ceil_mode=True)
-        for bi, b in enumerate(self.blocks):
-            x, _ = self._block_fwd(x, b)
-            if bi == self.f2_block:
-                f2 = x
-        return torch.cat((f2, x), dim=3)
+        f3, f2 = self._frozen_blocks(x, self.blocks, tap=self.f2_block)
+        return torch.cat((f2, f3), dim=3)
 
     def forward(self, sup_img, sup_mask, qry_img, history=None, slot=None):
         """sup_img [B,S,3,H,W], sup_mask [B,S,2,H,W], qry_img [B,1,3,H,W]; ``history``: None (zeros), [B,2,h,w], or -- with
@@ -140,7 +91,7 @@ class CANetHeadTrainEngine(Stage2TrainEngine):
         self.last_cat23 = cat23
         msk = sup_mask.reshape(ns, 2, H, W).float().contiguous()
         y5 = conv2d(cat23, self.l5.fwd_params(relu=True))
-        f5, m5 = self._drop(y5, n, MID, ("layer5.2",))
+        f5, m5 = self._drop(y5, ("layer5.2",), self.drop_rate2)
         z = ops.canet_support_vector(f5[:ns], msk, S)
         c55 = self.l55
         w55 = f.krsc(c55.conv.weight).view(MID, 9, 2 * MID)
@@ -148,7 +99,7 @@ class CANetHeadTrainEngine(Stage2TrainEngine):
         pq = ConvParams(w55[:, :, :MID].reshape(MID, 9 * MID), None, c55.conv.bias.data, MID, MID, 3, 3, 1, c55.pad, c55.dil, 9 * MID,
                         False, True)
         y55 = conv2d(f5[ns:], pq, residual=R)
-        out, m55 = self._drop(y55, B, MID, ("layer55.2",))
+        out, m55 = self._drop(y55, ("layer55.2",), self.drop_rate2)
         tape.update(cat23=cat23, y5=y5, m5=m5, f5=f5, msk=msk, z=z, w55=w55, y55=y55, m55=m55, S=S, blocks=[])
         for k, (c1, c2) in enumerate(self.res):
             if k == 0 and self.use_history:
@@ -167,11 +118,8 @@ class CANetHeadTrainEngine(Stage2TrainEngine):
             tape["blocks"].append(dict(inp=inp, t=t))
             out = nxt
         y6 = self._aspp_forward(out, tape, out_relu=True)
-        x6, m6 = self._drop(y6, B, MID, ("layer6.2",))
-        self.w_cls[:2].copy_(f.krsc(self.l7.weight))
-        self.b_cls[:2].copy_(self.l7.bias.data)
-        c = conv2d(x6, ConvParams(self.w_cls, None, self.b_cls, MID, 64, 1, 1, 1, 0, 1, MID, False, False))
-        pred = logits_nchw(c, self._new(B, 2, h, w))
+        x6, m6 = self._drop(y6, ("layer6.2",), self.drop_rate2)
+        pred = self.l7.forward(x6, self._new(B, 2, h, w))
         tape.update(y6=y6, m6=m6, x6=x6)
         self.tape = tape
         return pred
@@ -180,14 +128,10 @@ class CANetHeadTrainEngine(Stage2TrainEngine):
     def backward(self, dpred):
         """``dpred`` [B,2,h,w]: the gradient at the low-resolution logits.  Fills the flat gradient buffer."""
         f, tp, ws = self.flat, self.tape, self.ws
-        if f.side_stream is not None:          # the dgrad mirror is in place; the side stream starts behind the zeroed gradients
-            torch.cuda.current_stream().wait_stream(f.side_stream)
-            f.side_stream.wait_stream(torch.cuda.current_stream())
+        self._begin_backward()
         B, _, h, w = dpred.shape
         # layer7, layer6
-        w7 = f.krsc(self.l7.weight)
-        dx6 = T.canet_cls_bwd(dpred, tp["x6"], w7, torch.empty_like(tp["x6"]), f.krsc_grad(self.l7.weight), self.l7.bias.grad,
-                              ws_cache=ws)
+        dx6 = self.l7.backward(dpred, tp["x6"], ws)
         g6 = torch.empty_like(dx6)
         T.relu_bias_bwd(self._drop_bwd(dx6, tp["m6"]), tp["y6"], g6, relu=True, want_dbias=False)     # _aspp_backward: layer6's bias
         d = self._aspp_backward(g6)
@@ -200,7 +144,8 @@ class CANetHeadTrainEngine(Stage2TrainEngine):
             T.relu_bias_bwd(conv2d(d, c2.dgrad_params()), rec["t"], g1, relu=True, ws_cache=ws, out=c1.conv.bias.grad)
             inp = rec["inp"]
             if inp.shape[-1] != MID:           # the history block: padded input, 258 live weight channels, no history gradient
-                _enqueue_wgrad(f, _SliceWgradK(f.krsc_grad(c1.conv.weight).view(MID, 9, c1.cin), HIST_WGRAD, c1), inp, g1, ws)
+                dw1 = f.krsc_grad(c1.conv.weight).view(MID, 9, c1.cin)
+                _enqueue_wgrad(f, _SliceWgrad(HIST_WGRAD, MID, [(dw1, slice(c1.cin))], 3, c1.pad, c1.dil), inp, g1, ws)
                 wd = f.dgrad_krsc(c1.conv.weight)[:MID]
                 dprm = ConvParams(wd, None, None, MID, MID, 3, 3, 1, c1.dil * 2 - c1.pad, c1.dil, wd.shape[1], False, False)
             else:
@@ -217,7 +162,7 @@ class CANetHeadTrainEngine(Stage2TrainEngine):
         T.relu_bias_bwd(self._drop_bwd(d, tp["m55"]), tp["y55"], g55, relu=True, ws_cache=ws, out=c55.conv.bias.grad)
         dw55 = f.krsc_grad(c55.conv.weight).view(MID, 9, 2 * MID)
         fq = tp["f5"][ns:]
-        _enqueue_wgrad(f, _SliceWgradK(dw55[:, :, :MID], MID, c55), fq, g55, ws)
+        _enqueue_wgrad(f, _SliceWgrad(MID, MID, [(dw55[:, :, :MID], slice(None))], 3, c55.pad, c55.dil), fq, g55, ws)
         df5 = torch.empty_like(tp["f5"])
         wd = f.dgrad_krsc(c55.conv.weight)[:MID]
         conv2d(g55, ConvParams(wd, None, None, MID, MID, 3, 3, 1, c55.dil * 2 - c55.pad, c55.dil, wd.shape[1], False, False),
@@ -238,21 +183,11 @@ class CANetTrainer(Stage1Trainer):
     ``query = 1``, any ``shot``."""
 
     def __init__(self, model, lr=1e-3, momentum=0.9, weight_decay=5e-4, device=None, loss="ce", sigma=5.0, use_graph=False):
-        from .core import losses
-        if use_graph:
-            raise ValueError("CANetTrainer runs eagerly: hipGraph capture of the CANet step is not built")
+        self._eager_only(use_graph, "CANet")
         if not model.freeze_backbone:
-            raise ValueError("CANet trunk training (freeze_backbone=False) is not built: the HIP path trains the head behind a "
-                             "frozen trunk, as the reference's configuration does")
-        self.device = device if device is not None else torch.device("cuda", torch.cuda.current_device())
-        self.model = model
-        model.train()
+            raise ValueError(_FROZEN_TRUNK)
+        self._setup(model, device, lr, momentum, weight_decay, 0.0, loss, sigma, False)
         self.eng = CANetHeadTrainEngine(model, self.device)
-        self.lr, self.momentum, self.wd, self.max_norm = lr, momentum, weight_decay, 0.0
-        self.protos, self.dist_scalar = 0, None
-        self.last_grad_norm, self.nesterov, self.optimizer = None, False, None
-        self.use_graph, self._graphs = False, {}
-        self.loss_obj = losses.get({"loss": loss, "sigma": sigma})
 
     def forward_backward(self, sup_img, sup_mask, qry_img, qry_msk, history_mask=None, table=None, read_slot=None):
         """Fills the flat gradient buffer -> (loss, low-resolution logits [B,2,h,w]).  The history: ``history_mask`` [B,1,2,h,w]
@@ -269,22 +204,18 @@ class CANetTrainer(Stage1Trainer):
         eng.flat.grad.zero_()
         pred = eng.forward(sup_img, sup_mask, qry_img, history=hist, slot=slot)
         tgt = qry_msk.reshape(-1, *qry_msk.shape[-2:]).contiguous()
-        wmap = self.loss_obj.weight_map(tgt)                      # None for plain CE
-        _, stats, _ = ops.eval_tail(pred, tgt, ws_cache=eng.ws, weight=wmap)
-        loss = stats[:, 0].sum() / stats[:, 1].sum()
-        eng.backward(T.upsample_ce_bwd(pred, tgt, stats, weight=wmap))
+        loss, _, dpred = self._ce_upsampled(pred, tgt, self.loss_obj.weight_map(tgt))      # (no weight map for plain CE)
+        eng.backward(dpred)
         return loss.float(), pred
 
     def train_step(self, sup_img, sup_mask, qry_img, qry_msk=None, history_mask=None, table=None, read_slot=None, write_slot=None):
         """-> (loss, softmax of the low-resolution logits [B,2,h,w]); with a ``table`` the softmax also goes to its rows
         ``write_slot[b]`` (< 0: nowhere), the later history of those episodes."""
-        ins = [t.to(self.device) for t in (sup_img, sup_mask, qry_img, qry_msk)]
         if history_mask is not None:
             history_mask = history_mask.to(self.device)
-        self.eng.buckets.enabled = self.collectives
-        loss, pred = self.forward_backward(*ins, history_mask=history_mask, table=table, read_slot=read_slot)
-        self.optimizer_step()
-        self.eng.buckets.enabled = False
+        loss, pred = self._step((sup_img, sup_mask, qry_img, qry_msk),
+                                lambda *ins: self.forward_backward(*ins, history_mask=history_mask, table=table, read_slot=read_slot))
         prob = ops.canet_history_update(pred, table=table if write_slot is not None else None, slot=write_slot,
                                         out=torch.empty_like(pred))
         return loss, prob
+

@@ -18,6 +18,7 @@ flipped/transposed weights) backward.  The prototype head (MPM / cosine / upsamp
 the flops) runs forward and backward on the HIP head kernels (head.hip, head_bwd.hip); the torch-autograd
 restatement of the head that cross-checks them lives with the tests (tests/util.py).
 """
+import gc
 import os
 
 import torch
@@ -25,6 +26,7 @@ import torch.distributed as dist
 import torch.nn as nn
 
 from . import ops, train_ops as T
+from .engine import logits_nchw
 from .ops import ConvParams
 
 
@@ -208,6 +210,7 @@ class SegmentedCapture:
 
     def begin(self):
         torch.cuda.synchronize()
+        gc.collect()                       # no dead engine's hipGraphs may be destroyed inside a capture (see _HeadMixin._replay)
         self.cs.wait_stream(torch.cuda.current_stream())
         self._ctx = torch.cuda.stream(self.cs)
         self._ctx.__enter__()
@@ -296,16 +299,20 @@ def _enqueue_wgrad(flat, job, x, g, ws):
 
 
 class _SliceWgrad:
-    """Weight gradient of a 1x1 conv whose weight is a column slice of a larger matrix (ASPPV2's layer6 sees the global branch
-    and the four concatenated branches as two such slices): computed into a dense temporary, copied into the slice."""
+    """Weight gradient of a k x k conv whose weight is a channel slice of a larger KRSC matrix (ASPP's layer6 sees the global
+    branch and the four concatenated branches as two such slices), or whose input carries zero padding channels: computed into
+    a dense [Cout, taps, cin] temporary; every (dst, src) of ``copies`` then takes its channels ``src`` (a slice or an index)
+    into ``dst``, a view of the parameter's gradient ([Cout, channels] for one tap)."""
 
-    def __init__(self, dst, cin, cout):
-        self.dst, self.prm = dst, ConvParams(None, None, None, cin, cout, 1, 1, 1, 0, 1, cin, False, False)
+    def __init__(self, cin, cout, copies, k=1, pad=0, dil=1):
+        self.copies, self.prm = copies, ConvParams(None, None, None, cin, cout, k, k, 1, pad, dil, k * k * cin, False, False)
 
     def _wgrad_now(self, x, g, ws):
-        tmp = torch.empty((self.prm.cout, self.prm.cin), dtype=torch.float32, device=x.device)
-        T.conv_wgrad(x, g, self.prm, tmp, ws_cache=ws)
-        self.dst.copy_(tmp)
+        p = self.prm
+        tmp = torch.empty((p.cout, p.kpad), dtype=torch.float32, device=x.device)
+        T.conv_wgrad(x, g, p, tmp, ws_cache=ws)
+        for dst, src in self.copies:
+            dst.copy_(tmp.view(p.cout, p.kh * p.kw, p.cin)[..., src].view(dst.shape))
 
 
 class _Conv:
@@ -376,8 +383,50 @@ class _BN:
             self.bn.bias.grad.copy_(dbeta)
 
 
-class Stage1TrainEngine:
-    """Forward + backward of the stage-1 ResNet-50 encoder in train mode on HIP kernels."""
+class _FrozenConv(_Conv):
+    """A conv of a frozen trunk: its forward parameters are packed once."""
+
+    def __init__(self, flat, conv, stem=False):
+        super().__init__(flat, conv, stem)
+        self._packed = {}
+
+    def fwd_params(self, relu=False, with_bias=True):
+        key = (relu, with_bias)
+        if key not in self._packed:
+            self._packed[key] = super().fwd_params(relu, with_bias)
+        return self._packed[key]
+
+
+def block_handles(flat, blk, conv=_Conv, first=None):
+    """Handles of one torchvision-style bottleneck ``blk``: ``conv`` wraps its convs, ``first`` (default: ``conv``) conv1 and the
+    downsample conv (stage 2: the convs that see the communication channels)."""
+    first = first or conv
+    return dict(c1=first(flat, blk.conv1), b1=_BN(blk.bn1), c2=conv(flat, blk.conv2), b2=_BN(blk.bn2),
+                c3=conv(flat, blk.conv3), b3=_BN(blk.bn3),
+                ds=(first(flat, blk.downsample[0]), _BN(blk.downsample[1])) if blk.downsample is not None else None)
+
+
+class _Cls2:
+    """A C -> 2 classifier: forward as a conv padded to 64 output channels (re-packed every step), backward on canet_cls_bwd."""
+
+    def __init__(self, flat, conv, device):
+        self.flat, self.conv, self.cin = flat, conv, conv.weight.shape[1]
+        self.w = torch.zeros((64, self.cin), dtype=torch.float32, device=device)
+        self.b = torch.zeros(64, dtype=torch.float32, device=device)
+
+    def forward(self, x, pred):
+        self.w[:2].copy_(self.flat.krsc(self.conv.weight))
+        self.b[:2].copy_(self.conv.bias.data)
+        return logits_nchw(conv2d(x, ConvParams(self.w, None, self.b, self.cin, 64, 1, 1, 1, 0, 1, self.cin, False, False)), pred)
+
+    def backward(self, dpred, x, ws):
+        return T.canet_cls_bwd(dpred, x, self.flat.krsc(self.conv.weight), torch.empty_like(x), self.flat.krsc_grad(self.conv.weight),
+                               self.conv.bias.grad, ws_cache=ws)
+
+
+class TrainEngine:
+    """What every training engine is built on: the flat parameters, buffers and frozen parameters on the device, the workspace
+    cache, the Philox stream, the train-mode conv -> BatchNorm forward, Dropout2d and the handshake that opens a backward."""
 
     def __init__(self, model, device):
         self.model, self.device = model, device
@@ -387,10 +436,112 @@ class Stage1TrainEngine:
         for p in model.parameters():
             if not p.requires_grad:
                 p.data = p.data.to(device)
-        self.ws = {}
-        self.drop_rate, self.block_size = 0.0, 4
-        self.draws = None                                            # see _dropblock
+        self.ws, self.draws, self.tape = {}, None, None              # draws: see _dropblock / _drop
         self.rng = T.RandomStream(torch.initial_seed(), device)      # Philox stream of the DropBlock / Dropout2d kernels
+
+    def _new(self, *shape):
+        return torch.empty(shape, dtype=torch.float32, device=self.device)
+
+    def _pack(self, images_list, priors=None):
+        n = sum(t.shape[0] for t in images_list)
+        H, W = images_list[0].shape[-2:]
+        x4 = self._new(n, H, W, 4)
+        o = 0
+        for i, t in enumerate(images_list):
+            ops.pack_input(t.contiguous(), None if priors is None else priors[i].contiguous(), out=x4[o:o + t.shape[0]])
+            o += t.shape[0]
+        return x4
+
+    def _drop(self, y, layers, p):
+        """nn.Dropout2d(p) in train(): one Bernoulli(1 - p) / (1 - p) multiplier per (image, channel) -> (result, mask | None).
+        ``layers``: the reference names of the Dropout2d modules this call stands for, channel ranges in order; ``self.draws``
+        ({layer: uniforms [n, channels]}) replaces the Philox stream by given draws (parity tests)."""
+        if p <= 0.0:
+            return y, None
+        n, c = y.shape[0], y.shape[-1]
+        u = None
+        if self.draws is not None:
+            u = self.draws[layers[0]] if len(layers) == 1 else torch.cat([self.draws[k] for k in layers], dim=1)
+            if tuple(u.shape) != (n, c) or u.dtype != torch.float32 or u.device != y.device or not u.is_contiguous():
+                raise ValueError(f"dropout2d draws of {layers}: want contiguous float32 {(n, c)} on {y.device}")
+        m = T.dropout2d_mask(n, c, p, self.rng, self.device, uniforms=u)
+        return T.channel_scale(y, m), m
+
+    @staticmethod
+    def _drop_bwd(dy, m):
+        return dy if m is None else T.channel_scale(dy, m)
+
+    def _begin_backward(self):
+        """Opens ``backward`` -> whether a SegmentedCapture is recording (it orders the two streams itself).  Otherwise the main
+        stream waits for the dgrad weight mirror, and the side stream must not start before this step's gradients were zeroed."""
+        recording = self.flat.capture is not None
+        if self.flat.side_stream is not None and not recording:
+            torch.cuda.current_stream().wait_stream(self.flat.side_stream)
+            self.flat.side_stream.wait_stream(torch.cuda.current_stream())
+        return recording
+
+    def _cbn_fwd(self, x, conv, bn, relu, residual=None, img_bias=None):
+        """conv -> (+ per-image bias [N,Cout]) -> batch-stat BN (+residual)(+ReLU); returns (y, tape record)."""
+        prm = conv.fwd_params(relu=False, with_bias=False)
+        part = None
+        if FUSE_BN_STATS and img_bias is None and ops.stats_supported(x, prm):
+            z, part = ops.conv2d_stats(x, prm)         # batch statistics started in the conv epilogue
+        else:
+            z = conv2d(x, prm) if img_bias is None else conv2d(x, prm, shift_override=img_bias, per_image_shift=True)
+        mask = None
+        if FUSE_BN_BWD and relu and T.mask_supported(z.shape[-1]):       # sign bits of y: what the backward needs of it
+            mask = torch.empty((z.numel() // z.shape[-1], z.shape[-1] // 32), dtype=torch.int32, device=z.device)
+        if part is not None:                           # ... finished and applied by one call
+            y, mean, invstd = T.bn_fwd_partials(z, part, bn.bn.weight.data, bn.bn.bias.data, torch.empty_like(z), bn.bn.eps, BN_MOM,
+                                                bn.bn.running_mean, bn.bn.running_var, residual=residual, relu=relu, mask=mask)
+            return y, dict(x=x, z=z, y=y, mean=mean, invstd=invstd, relu=relu, mask=mask)
+        mean, invstd = bn.stats(z, self.ws)
+        y = T.bn_apply(z, mean, invstd, bn.bn.weight.data, bn.bn.bias.data, torch.empty_like(z), residual=residual, relu=relu,
+                       mask=mask)
+        return y, dict(x=x, z=z, y=y, mean=mean, invstd=invstd, relu=relu, mask=mask)
+
+    def _block_fwd(self, x, b, bias_c1=None, bias_ds=None):
+        rec = {"x": x}
+        y1, rec["r1"] = self._cbn_fwd(x, b["c1"], b["b1"], True, img_bias=bias_c1)
+        y2, rec["r2"] = self._cbn_fwd(y1, b["c2"], b["b2"], True)
+        if b["ds"] is not None:
+            res, rec["rd"] = self._cbn_fwd(x, b["ds"][0], b["ds"][1], False, img_bias=bias_ds)
+        else:
+            res = x
+        out, rec["r3"] = self._cbn_fwd(y2, b["c3"], b["b3"], True, residual=res)
+        return out, rec
+
+class HeadTrainEngine(TrainEngine):
+    """A head trained behind a frozen trunk (``requires_grad`` cleared before construction).  The trunk modules ``trunk`` run
+    forward only, in train mode -- batch-statistics BatchNorm, weights packed once, nothing kept for a backward; the head's
+    gradients are one all-reduce bucket.  ``_init_handles(model)`` builds the subclass's layer handles."""
+
+    def __init__(self, model, device, trunk):
+        super().__init__(model, device)
+        self.bn_counters = [m.num_batches_tracked for t in trunk for m in t.modules() if isinstance(m, nn.BatchNorm2d)]
+        self._init_handles(model)
+        self.flat.build_dgrad_mirror()
+        self.buckets = GradBuckets(self.flat.grad, [], side_stream=self.flat.side_stream)
+
+    def _frozen(self, blocks):
+        return [block_handles(self.flat, blk, _FrozenConv) for blk in blocks]
+
+    def _frozen_blocks(self, x, blocks, tap=None):
+        """``x`` through the frozen ``blocks`` -> (output, output of block ``tap``)."""
+        tapped = None
+        for bi, b in enumerate(blocks):
+            x, _ = self._block_fwd(x, b)
+            if bi == tap:
+                tapped = x
+        return x, tapped
+
+
+class Stage1TrainEngine(TrainEngine):
+    """Forward + backward of the stage-1 ResNet-50 encoder in train mode on HIP kernels."""
+
+    def __init__(self, model, device):
+        super().__init__(model, device)
+        self.drop_rate, self.block_size = 0.0, 4
         self._init_trunk(model.encoder.backbone)
         self._init_tail(model)
         self.flat.build_dgrad_mirror()
@@ -402,15 +553,8 @@ class Stage1TrainEngine:
         self.buckets = GradBuckets(self.flat.grad, self.block_off + [self.tail_off], side_stream=self.flat.side_stream)
 
     def _init_trunk(self, bb):
-        f = self.flat
-        self.stem = (_Conv(f, bb.conv1, stem=True), _BN(bb.bn1))
-        self.blocks = []
-        for name in ("layer1", "layer2", "layer3"):
-            for blk in getattr(bb, name):
-                self.blocks.append(dict(
-                    c1=_Conv(f, blk.conv1), b1=_BN(blk.bn1), c2=_Conv(f, blk.conv2), b2=_BN(blk.bn2),
-                    c3=_Conv(f, blk.conv3), b3=_BN(blk.bn3),
-                    ds=(_Conv(f, blk.downsample[0]), _BN(blk.downsample[1])) if blk.downsample is not None else None))
+        self.stem = (_Conv(self.flat, bb.conv1, stem=True), _BN(bb.bn1))
+        self.blocks = [block_handles(self.flat, blk) for name in ("layer1", "layer2", "layer3") for blk in getattr(bb, name)]
 
     def _init_tail(self, model):
         f, pur = self.flat, model.encoder.purifier
@@ -422,9 +566,6 @@ class Stage1TrainEngine:
         self.midc = self.aspp_conv[0].cout
 
     # -- helpers ------------------------------------------------------------------------------
-    def _new(self, *shape):
-        return torch.empty(shape, dtype=torch.float32, device=self.device)
-
     def _dropblock(self, x, n, h, w, layer):
         """DropBlock2D(drop_rate, block_size) in train(): -> (y, record for the backward) (identity at rate 0).  ``layer`` is
         the module's name in the reference model; ``self.draws`` ({layer: uniforms [n,h,w]}) replaces the Philox stream by
@@ -447,26 +588,6 @@ class Stage1TrainEngine:
     @staticmethod
     def _dropblock_bwd(dy, rec):
         return dy if rec is None else T.pixel_scale(dy, *rec)
-
-    def _cbn_fwd(self, x, conv, bn, relu, residual=None, img_bias=None):
-        """conv -> (+ per-image bias [N,Cout]) -> batch-stat BN (+residual)(+ReLU); returns (y, tape record)."""
-        prm = conv.fwd_params(relu=False, with_bias=False)
-        part = None
-        if FUSE_BN_STATS and img_bias is None and ops.stats_supported(x, prm):
-            z, part = ops.conv2d_stats(x, prm)         # batch statistics started in the conv epilogue
-        else:
-            z = conv2d(x, prm) if img_bias is None else conv2d(x, prm, shift_override=img_bias, per_image_shift=True)
-        mask = None
-        if FUSE_BN_BWD and relu and T.mask_supported(z.shape[-1]):       # sign bits of y: what the backward needs of it
-            mask = torch.empty((z.numel() // z.shape[-1], z.shape[-1] // 32), dtype=torch.int32, device=z.device)
-        if part is not None:                           # ... finished and applied by one call
-            y, mean, invstd = T.bn_fwd_partials(z, part, bn.bn.weight.data, bn.bn.bias.data, torch.empty_like(z), bn.bn.eps, BN_MOM,
-                                                bn.bn.running_mean, bn.bn.running_var, residual=residual, relu=relu, mask=mask)
-            return y, dict(x=x, z=z, y=y, mean=mean, invstd=invstd, relu=relu, mask=mask)
-        mean, invstd = bn.stats(z, self.ws)
-        y = T.bn_apply(z, mean, invstd, bn.bn.weight.data, bn.bn.bias.data, torch.empty_like(z), residual=residual, relu=relu,
-                       mask=mask)
-        return y, dict(x=x, z=z, y=y, mean=mean, invstd=invstd, relu=relu, mask=mask)
 
     def _cbn_bwd(self, dy, rec, conv, bn, want_gout=False, need_dx=True, add_to=None, up=None):
         """-> (dx [compact for stride-2], gout).  ``add_to`` is added to dx inside the dgrad epilogue; the
@@ -494,17 +615,6 @@ class Stage1TrainEngine:
         else:
             dx = conv2d(dz, prm, residual=add_to)
         return dx, gout
-
-    def _block_fwd(self, x, b, bias_c1=None, bias_ds=None):
-        rec = {"x": x}
-        y1, rec["r1"] = self._cbn_fwd(x, b["c1"], b["b1"], True, img_bias=bias_c1)
-        y2, rec["r2"] = self._cbn_fwd(y1, b["c2"], b["b2"], True)
-        if b["ds"] is not None:
-            res, rec["rd"] = self._cbn_fwd(x, b["ds"][0], b["ds"][1], False, img_bias=bias_ds)
-        else:
-            res = x
-        out, rec["r3"] = self._cbn_fwd(y2, b["c3"], b["b3"], True, residual=res)
-        return out, rec
 
     def _block_bwd(self, dx, b, rec, up=None):
         """``up``: tape record of the BatchNorm(+ReLU) that produced this block's input (the previous block's bn3)."""
@@ -534,10 +644,7 @@ class Stage1TrainEngine:
         return feat
 
     def backward(self, dfeat):
-        recording = self.flat.capture is not None
-        if self.flat.side_stream is not None and not recording:      # the side stream must not start before this step's gradients were zeroed
-            torch.cuda.current_stream().wait_stream(self.flat.side_stream)     # the dgrad weight mirror is in place
-            self.flat.side_stream.wait_stream(torch.cuda.current_stream())
+        recording = self._begin_backward()
         dx = self._tail_backward(dfeat, up=self.tape["blocks"][-1]["r3"] if self.tape.get("blocks") else None)
         self.flat.cut()                            # segment 0: forward + head + purifier / ASPP backward
         if self.tail_off:
@@ -546,16 +653,6 @@ class Stage1TrainEngine:
         if not recording:
             self.flat.join_side_stream()           # every weight gradient has landed before the optimizer / all-reduce
         self.tape = None
-
-    def _pack(self, images_list, priors=None):
-        n = sum(t.shape[0] for t in images_list)
-        H, W = images_list[0].shape[-2:]
-        x4 = self._new(n, H, W, 4)
-        o = 0
-        for i, t in enumerate(images_list):
-            ops.pack_input(t.contiguous(), None if priors is None else priors[i].contiguous(), out=x4[o:o + t.shape[0]])
-            o += t.shape[0]
-        return x4
 
     def _trunk_forward(self, images_list, tape):
         y, tape["stem"] = self._cbn_fwd(self._pack(images_list), *self.stem, relu=True)
@@ -628,12 +725,12 @@ class Stage1TrainEngine:
         w6 = tp["w6"]
         dw6 = self.flat.krsc_grad(l6w)                              # [512, 1280] view of the gradient
         # layer6: main 1x1 conv over the 4 concatenated branches + per-image bias from the global branch
-        _enqueue_wgrad(self.flat, _SliceWgrad(dw6[:, midc:], 4 * midc, l6w.shape[0]), tp["cat"], dfeat, self.ws)   # side stream
+        _enqueue_wgrad(self.flat, _SliceWgrad(4 * midc, l6w.shape[0], [(dw6[:, midc:], slice(None))]), tp["cat"], dfeat, self.ws)   # side stream
         dcat = conv2d(dfeat, ConvParams(T.dgrad_weight(w6[:, midc:].contiguous(), 1, 1), None, None, l6w.shape[0], 4 * midc,
                                             1, 1, 1, 0, 1, l6w.shape[0], False, False))
         s = ops.global_avgpool(dfeat) * float(hw)                   # per-image column sums [N, 512]
         self.l6.bias.grad.copy_(s.sum(dim=0))
-        _enqueue_wgrad(self.flat, _SliceWgrad(dw6[:, :midc], midc, l6w.shape[0]), tp["g0"], s.view(nimg, 1, 1, -1), self.ws)
+        _enqueue_wgrad(self.flat, _SliceWgrad(midc, l6w.shape[0], [(dw6[:, :midc], slice(None))]), tp["g0"], s.view(nimg, 1, 1, -1), self.ws)
         dg0 = conv2d(s.view(nimg, 1, 1, -1), ConvParams(T.dgrad_weight(w6[:, :midc].contiguous(), 1, 1), None, None, l6w.shape[0],
                                                             midc, 1, 1, 1, 0, 1, l6w.shape[0], False, False))
         # branches 1..4
@@ -774,9 +871,7 @@ class Stage1Trainer:
                  drop_rate=None, block_size=None, loss="ce", sigma=5.0, use_graph=False):
         from .networks.pemp_stage1 import net_ingredient
         cfg = net_ingredient.cfg
-        self.device = device if device is not None else torch.device("cuda", torch.cuda.current_device())
-        self.model = model
-        model.train()
+        self._setup(model, device, lr, momentum, weight_decay, max_norm, loss, sigma, use_graph, cfg["dist_scalar"])
         if getattr(model, "backbone_name", "resnet50") == "vgg16":     # stage 1 on VGG-16: conv+bias+ReLU chain, no purifier
             from .train_baseline import _VGGEngine
             self.eng = _VGGEngine(model, self.device)
@@ -784,16 +879,25 @@ class Stage1Trainer:
             self.eng = Stage1TrainEngine(model, self.device)
         self.eng.drop_rate = getattr(model, "drop_rate", cfg["drop_rate"]) if drop_rate is None else drop_rate
         self.eng.block_size = getattr(model, "block_size", cfg["block_size"]) if block_size is None else block_size
-        self.lr, self.momentum, self.wd, self.max_norm = lr, momentum, weight_decay, max_norm
-        self.protos = 0 if model.ctr is None else model.ctr.shape[1] // 2
-        self.dist_scalar = cfg["dist_scalar"]
-        self.last_grad_norm = None
-        self.nesterov = False
-        self.optimizer = None                     # optional torch optimizer acting as hyper-parameter / scheduler holder
-        self.use_graph = use_graph
-        self._graphs = {}
+
+    def _setup(self, model, device, lr, momentum, weight_decay, max_norm, loss, sigma, use_graph, dist_scalar=None):
+        """What every trainer's constructor does before it builds its engine: the model in ``train()``, hyper-parameters, the
+        loss object and the bookkeeping fields."""
         from .core import losses
+        self.device = device if device is not None else torch.device("cuda", torch.cuda.current_device())
+        self.model = model
+        model.train()
+        self.lr, self.momentum, self.wd, self.max_norm = lr, momentum, weight_decay, max_norm
+        self.protos = 0 if getattr(model, "ctr", None) is None else model.ctr.shape[1] // 2
+        self.dist_scalar = dist_scalar
+        self.last_grad_norm, self.nesterov = None, False
+        self.optimizer = None                     # optional torch optimizer acting as hyper-parameter / scheduler holder
+        self.use_graph, self._graphs = use_graph, {}
         self.loss_obj = losses.get({"loss": loss, "sigma": sigma})
+
+    def _eager_only(self, use_graph, what):
+        if use_graph:
+            raise ValueError(f"{what}Trainer runs eagerly: hipGraph capture of the {what} step is not built")
 
     map_full_res = False          # Baseline: masked average pooling over bilinearly up-sampled features
     #: False = a rank-LOCAL step: no gradient collective at all (bucket hooks off, no all-reduce in the optimizer step).
@@ -848,13 +952,27 @@ class Stage1Trainer:
         eng.backward(dfeat)
         return loss.float(), pred
 
-    def train_step(self, sup_img, sup_mask, qry_img, qry_msk=None):
-        ins = (sup_img.to(self.device), sup_mask.to(self.device), qry_img.to(self.device), qry_msk.to(self.device))
-        self.eng.buckets.enabled = self.collectives and not self.use_graph   # eager step: buckets are all-reduced during backward
-        loss = self._graphed_forward_backward(*ins) if self.use_graph else self.forward_backward(*ins)[0]
-        self.optimizer_step()                               # finishes / waits for the buckets
+    def _ce_upsampled(self, pred, tgt, weight=None):
+        """CE of the bilinearly up-sampled logits, fused (``ops.eval_tail``) -> (loss, its stats rows, the gradient at the
+        low-resolution logits)."""
+        _, stats, _ = ops.eval_tail(pred, tgt, ws_cache=self.eng.ws, weight=weight)
+        return stats[:, 0].sum() / stats[:, 1].sum(), stats, T.upsample_ce_bwd(pred, tgt, stats, weight=weight)
+
+    def _step(self, ins, run):
+        """One training step: ``run(*ins on the device)`` fills the flat gradient buffer -- an eager one with the buckets
+        all-reduced during its backward -- then the optimizer step finishes / waits for them -> what ``run`` returned."""
+        ins = [t.to(self.device) for t in ins]
+        self.eng.buckets.enabled = self.collectives and not self.use_graph
+        out = run(*ins)
+        self.optimizer_step()
         self.eng.buckets.enabled = False
-        return loss
+        return out
+
+    def _loss_step(self, *ins):
+        return self._graphed_forward_backward(*ins) if self.use_graph else self.forward_backward(*ins)[0]
+
+    def train_step(self, sup_img, sup_mask, qry_img, qry_msk=None):
+        return self._step((sup_img, sup_mask, qry_img, qry_msk), self._loss_step)
 
     def _graphed_forward_backward(self, *ins):
         """forward + backward (~450 short launches) replayed from a chain of hipGraphs per input signature

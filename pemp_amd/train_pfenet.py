@@ -8,7 +8,7 @@ BatchNorm's train mode, and nothing puts the trunk into ``eval()``.  The referen
 shot for that shot's B supports; every call normalises with its own batch's statistics and moves the running statistics
 (momentum 0.1), in the order query, shot 0, shot 1, ...; ``num_batches_tracked`` grows by S + 1 per step.  ``layer4`` sees
 ``layer3`` for the queries and ``layer3 * mask`` for a shot.  The trunk therefore runs S + 1 times on the train-mode conv ->
-batch-statistics BatchNorm chain of ``Stage1TrainEngine`` (forward only, weights packed once, no tape), and the per-epoch
+batch-statistics BatchNorm chain of ``train_engine.HeadTrainEngine`` (forward only, weights packed once, no tape), and the per-epoch
 evaluation sees the moved running statistics, as the reference's does.
 
 Head layout (forward as ``pfenet_engine.PFENetEngine.lowres``):
@@ -34,82 +34,35 @@ Dropout2d: Philox masks per (image, channel), or given uniforms (``eng.draws``, 
 b * S + s) for the parity tests.  ``eng.drop_scale`` = 0 switches every Dropout2d off.
 """
 import torch
-import torch.nn as nn
 
 from . import ops, train_ops as T
-from .engine import logits_nchw
 from .ops import ConvParams
 from .pfenet_engine import MERGE_CIN, PYRAMID_BINS, REDUCE
-from .train_canet import _FrozenConv
-from .train_engine import FlatParams, GradBuckets, Stage1TrainEngine, Stage1Trainer, _BN, _Conv, _enqueue_wgrad, conv2d
+from .train_engine import HeadTrainEngine, Stage1Trainer, _BN, _Cls2, _Conv, _FrozenConv, _SliceWgrad, _enqueue_wgrad, conv2d
 
 MERGE_WGRAD = 320                       # what the weight-gradient kernel of init_merge reads (Cin % 64); channels 257.. are zero
 TRUNK = ("layer0", "layer1", "layer2", "layer3", "layer4")
 
 
-class _MergeWgrad:
-    """Weight gradient of the query and prior columns of an ``init_merge`` conv: computed over the 320-channel input into a dense
-    temporary, its columns 0..255 and 256 copied to columns 0..255 and 512 of the [256, 513] gradient."""
+class PFENetHeadTrainEngine(HeadTrainEngine):
+    """S + 1 train-mode forward passes of the frozen deep-base trunk, forward + backward of PFENet's head."""
 
-    def __init__(self, dw):
-        self.dw = dw
-        self.prm = ConvParams(None, None, None, MERGE_WGRAD, REDUCE, 1, 1, 1, 0, 1, MERGE_WGRAD, False, False)
-
-    def _wgrad_now(self, x, g, ws):
-        tmp = torch.empty((REDUCE, MERGE_WGRAD), dtype=torch.float32, device=x.device)
-        T.conv_wgrad(x, g, self.prm, tmp, ws_cache=ws)
-        self.dw[:, :REDUCE].copy_(tmp[:, :REDUCE])
-        self.dw[:, 2 * REDUCE].copy_(tmp[:, REDUCE])
-
-
-class _Cls2:
-    """A 256 -> 2 classifier: forward as a conv padded to 64 output channels (re-packed every step), backward on canet_cls_bwd."""
-
-    def __init__(self, flat, conv, device):
-        self.flat, self.conv = flat, conv
-        self.w = torch.zeros((64, REDUCE), dtype=torch.float32, device=device)
-        self.b = torch.zeros(64, dtype=torch.float32, device=device)
-
-    def forward(self, x, pred):
-        self.w[:2].copy_(self.flat.krsc(self.conv.weight))
-        self.b[:2].copy_(self.conv.bias.data)
-        return logits_nchw(conv2d(x, ConvParams(self.w, None, self.b, REDUCE, 64, 1, 1, 1, 0, 1, REDUCE, False, False)), pred)
-
-    def backward(self, dpred, x, ws):
-        return T.canet_cls_bwd(dpred, x, self.flat.krsc(self.conv.weight), torch.empty_like(x), self.flat.krsc_grad(self.conv.weight),
-                               self.conv.bias.grad, ws_cache=ws)
-
-
-class PFENetHeadTrainEngine(Stage1TrainEngine):
-    """S + 1 train-mode forward passes of the frozen deep-base trunk (batch-statistics BatchNorm, no tape), forward + backward of
-    PFENet's head.  Shares the conv -> BatchNorm forward with the stage-1 engine; its constructor (a trainable trunk, a purifier)
-    is replaced."""
-
-    def __init__(self, model, device):                                   # noqa: super().__init__ builds a trainable trunk
+    def __init__(self, model, device):
         for name in TRUNK:
             for p in getattr(model, name).parameters():
                 p.requires_grad = False                                   # the reference's optimizer skips them: their .grad is None
-        self.model, self.device = model, device
-        self.flat = FlatParams(model, device)
-        for b in model.buffers():
-            b.data = b.data.to(device)
-        for p in model.parameters():
-            if not p.requires_grad:
-                p.data = p.data.to(device)
-        self.ws, self.draws, self.tape = {}, None, None
+        super().__init__(model, device, [getattr(model, name) for name in TRUNK])
         self.drop_scale, self.skip_aux = 1.0, False
-        self.rng = T.RandomStream(torch.initial_seed(), device)
-        f, l0 = self.flat, model.layer0
+        self.w_merge = [torch.zeros((REDUCE, MERGE_CIN), dtype=torch.float32, device=device) for _ in self.merge]
+        self.merge_in = {}
+
+    def _init_handles(self, model):
+        f, l0, device = self.flat, model.layer0, self.device
         self.stem = [(_FrozenConv(f, l0[0], stem=True), _BN(l0[1])), (_FrozenConv(f, l0[3]), _BN(l0[4])),
                      (_FrozenConv(f, l0[6]), _BN(l0[7]))]
-        blk = lambda b: dict(c1=_FrozenConv(f, b.conv1), b1=_BN(b.bn1), c2=_FrozenConv(f, b.conv2), b2=_BN(b.bn2),
-                             c3=_FrozenConv(f, b.conv3), b3=_BN(b.bn3),
-                             ds=(_FrozenConv(f, b.downsample[0]), _BN(b.downsample[1])) if b.downsample is not None else None)
-        self.blocks = [blk(b) for name in ("layer1", "layer2", "layer3") for b in getattr(model, name)]
-        self.blocks4 = [blk(b) for b in model.layer4]
+        self.blocks = self._frozen([*model.layer1, *model.layer2, *model.layer3])
+        self.blocks4 = self._frozen(model.layer4)
         self.f2_block = len(model.layer1) + len(model.layer2) - 1         # layer2's last block: channels 1024.. of cat(layer3, layer2)
-        self.bn_counters = [m.num_batches_tracked for name in TRUNK for m in getattr(model, name).modules()
-                            if isinstance(m, nn.BatchNorm2d)]
         self.down_q, self.down_s = _Conv(f, model.down_query[0]), _Conv(f, model.down_supp[0])
         self.p_down, self.p_cls = float(model.down_query[2].p), float(model.cls[2].p)
         self.merge = [m[0] for m in model.init_merge]
@@ -120,29 +73,6 @@ class PFENetHeadTrainEngine(Stage1TrainEngine):
         self.res1 = _Conv(f, model.res1[0])
         self.res2 = (_Conv(f, model.res2[0]), _Conv(f, model.res2[2]))
         self.cls0, self.cls3 = _Conv(f, model.cls[0]), _Cls2(f, model.cls[3], device)
-        self.flat.build_dgrad_mirror()
-        self.w_merge = [torch.zeros((REDUCE, MERGE_CIN), dtype=torch.float32, device=device) for _ in self.merge]
-        self.merge_in = {}
-        self.buckets = GradBuckets(self.flat.grad, [], side_stream=self.flat.side_stream)     # one bucket: the head is 40 MB
-
-    # -- helpers --------------------------------------------------------------------------------
-    def _drop(self, y, name, p):
-        """nn.Dropout2d(p) in train(): one Bernoulli(1 - p) / (1 - p) multiplier per (image, channel) -> (result, mask | None)."""
-        p = p * self.drop_scale
-        if p <= 0.0:
-            return y, None
-        n, c = y.shape[0], y.shape[3]
-        u = None
-        if self.draws is not None:
-            u = self.draws[name]
-            if tuple(u.shape) != (n, c) or u.dtype != torch.float32 or u.device != y.device or not u.is_contiguous():
-                raise ValueError(f"dropout2d draws of {name}: want contiguous float32 {(n, c)} on {y.device}")
-        m = T.dropout2d_mask(n, c, p, self.rng, self.device, uniforms=u)
-        return T.channel_scale(y, m), m
-
-    @staticmethod
-    def _drop_bwd(dy, m):
-        return dy if m is None else T.channel_scale(dy, m)
 
     # -- forward --------------------------------------------------------------------------------
     def _trunk_pass(self, images, mask=None):
@@ -153,15 +83,8 @@ class PFENetHeadTrainEngine(Stage1TrainEngine):
         for conv, bn in self.stem:
             x, _ = self._cbn_fwd(x, conv, bn, relu=True)
         x, _ = T.maxpool_idx(x, 3, 2, 1, ceil_mode=False)
-        for bi, b in enumerate(self.blocks):
-            x, _ = self._block_fwd(x, b)
-            if bi == self.f2_block:
-                f2 = x
-        f3 = x
-        x = f3 if mask is None else ops.scale_add(f3, mask=mask)
-        for b in self.blocks4:
-            x, _ = self._block_fwd(x, b)
-        return f2, f3, x
+        f3, f2 = self._frozen_blocks(x, self.blocks, tap=self.f2_block)
+        return f2, f3, self._frozen_blocks(f3 if mask is None else ops.scale_add(f3, mask=mask), self.blocks4)[0]
 
     def trunk_forward(self, sup_img, sup_mask, qry_img):
         """The S + 1 trunk passes in the reference's order (query, shot 0, shot 1, ...) -> cat(layer3, layer2) of the queries
@@ -192,9 +115,9 @@ class PFENetHeadTrainEngine(Stage1TrainEngine):
         f.refresh_dgrad_mirror()
         self.rng.begin_step()
         yq = conv2d(cat_q, self.down_q.fwd_params(relu=True))
-        dq, mq = self._drop(yq, "down_query.2", self.p_down)
+        dq, mq = self._drop(yq, ("down_query.2",), self.p_down * self.drop_scale)
         ys = conv2d(cat_s, self.down_s.fwd_params(relu=True))
-        ds, ms = self._drop(ys, "down_supp.2", self.p_down)
+        ds, ms = self._drop(ys, ("down_supp.2",), self.p_down * self.drop_scale)
         svec = ops.weighted_gap(ds, mfeat, S)
         self.last_supp_vec = svec
         tape = dict(cat_q=cat_q, cat_s=cat_s, mfeat=mfeat, S=S, yq=yq, mq=mq, ys=ys, ms=ms, svec=svec, bins=[])
@@ -232,7 +155,7 @@ class PFENetHeadTrainEngine(Stage1TrainEngine):
             r.update(m2=m2, t1=t1, t2=t2, m3=m3)
             if not self.skip_aux:
                 i0 = conv2d(m3, self.inner0[idx].fwd_params(relu=True))
-                i0d, mi = self._drop(i0, f"inner_cls.{idx}.2", self.p_cls)
+                i0d, mi = self._drop(i0, (f"inner_cls.{idx}.2",), self.p_cls * self.drop_scale)
                 inner.append(self.inner3[idx].forward(i0d, self._new(B, 2, bn, bn)))
                 r.update(i0=i0, mi=mi, i0d=i0d)
             ops.resize_bilinear_ac(m3, (h, w), out=res1_in[..., idx * REDUCE:(idx + 1) * REDUCE])
@@ -242,7 +165,7 @@ class PFENetHeadTrainEngine(Stage1TrainEngine):
         r1 = conv2d(r0, self.res2[1].fwd_params(relu=True))
         q2 = ops.scale_add(r1, residual=q1)
         c0 = conv2d(q2, self.cls0.fwd_params(relu=True))
-        c0d, mc = self._drop(c0, "cls.2", self.p_cls)
+        c0d, mc = self._drop(c0, ("cls.2",), self.p_cls * self.drop_scale)
         pred = self.cls3.forward(c0d, self._new(B, 2, h, w))
         tape.update(res1_in=res1_in, q1=q1, r0=r0, r1=r1, q2=q2, c0=c0, mc=mc, c0d=c0d)
         self.tape = tape
@@ -258,9 +181,7 @@ class PFENetHeadTrainEngine(Stage1TrainEngine):
         """``dpred`` [B,2,h,w] and ``dinner`` (four [B,2,bin,bin], or None with ``skip_aux``): the gradients at the low-resolution
         logits of ``cls`` and of the ``inner_cls`` heads.  Fills the flat gradient buffer."""
         f, tp, ws = self.flat, self.tape, self.ws
-        if f.side_stream is not None:          # the dgrad mirror is in place; the side stream starts behind the zeroed gradients
-            torch.cuda.current_stream().wait_stream(f.side_stream)
-            f.side_stream.wait_stream(torch.cuda.current_stream())
+        self._begin_backward()
         B, _, h, w = dpred.shape
         new = lambda t: torch.empty(t.shape, dtype=torch.float32, device=self.device)
 
@@ -299,7 +220,9 @@ class PFENetHeadTrainEngine(Stage1TrainEngine):
                 g0 = relu_bwd(dm2, r["m0"])
             g0s[idx] = g0
             wconv = self.merge[idx].weight
-            _enqueue_wgrad(f, _MergeWgrad(f.krsc_grad(wconv)), r["inp"], g0, ws)
+            dw = f.krsc_grad(wconv)                                       # [256, 513]: query | support | prior
+            copies = [(dw[:, :REDUCE], slice(REDUCE)), (dw[:, 2 * REDUCE], REDUCE)]      # from columns 0..255 and 256 of the dense gradient
+            _enqueue_wgrad(f, _SliceWgrad(MERGE_WGRAD, REDUCE, copies), r["inp"], g0, ws)
             wd = f.dgrad_krsc(wconv)[:REDUCE]                             # rows 0..255 of the mirrored weight: the query channels
             gqs[idx] = conv2d(g0, ConvParams(wd, None, None, REDUCE, REDUCE, 1, 1, 1, 0, 1, wd.shape[1], False, False))
         # support vector and down_supp (weight gradient only: the trunk is frozen)
@@ -321,34 +244,22 @@ class PFENetTrainer(Stage1Trainer):
 
     def __init__(self, model, lr=1e-3, momentum=0.9, weight_decay=5e-4, device=None, loss="ce", sigma=5.0, loss_coef=1.0,
                  use_graph=False):
-        from .core import losses
-        if use_graph:
-            raise ValueError("PFENetTrainer runs eagerly: hipGraph capture of the PFENet step is not built")
-        self.device = device if device is not None else torch.device("cuda", torch.cuda.current_device())
-        self.model = model
-        model.train()
+        self._eager_only(use_graph, "PFENet")
+        self._setup(model, device, lr, momentum, weight_decay, 0.0, loss, sigma, False)
         self.eng = PFENetHeadTrainEngine(model, self.device)
-        self.lr, self.momentum, self.wd, self.max_norm = lr, momentum, weight_decay, 0.0
         self.loss_coef = float(loss_coef)
-        self.protos, self.dist_scalar = 0, None
-        self.last_grad_norm, self.nesterov, self.optimizer = None, False, None
-        self.use_graph, self._graphs = False, {}
-        self.loss_obj = losses.get({"loss": loss, "sigma": sigma})
 
     def losses_backward(self, pred, inner, tgt):
         """Main and auxiliary loss of given logits and their backward through the head -> (loss, aux_loss)."""
         eng = self.eng
-        wmap = self.loss_obj.weight_map(tgt)                      # None for plain CE
-        _, stats, _ = ops.eval_tail(pred, tgt, ws_cache=eng.ws, weight=wmap)
-        loss = stats[:, 0].sum() / stats[:, 1].sum()
-        dpred = T.upsample_ce_bwd(pred, tgt, stats, weight=wmap)
+        loss, _, dpred = self._ce_upsampled(pred, tgt, self.loss_obj.weight_map(tgt))      # (no weight map for plain CE)
         aux, dinner = torch.zeros((), dtype=torch.float64, device=pred.device), None
         if inner:
             dinner = []
             for lg in inner:                                      # always nn.CrossEntropyLoss(ignore_index=255), mean over the heads
-                _, st, _ = ops.eval_tail(lg, tgt, ws_cache=eng.ws)
-                aux = aux + st[:, 0].sum() / st[:, 1].sum()
-                dinner.append(T.upsample_ce_bwd(lg, tgt, st).mul_(self.loss_coef / len(inner)))
+                ce, _, d = self._ce_upsampled(lg, tgt)
+                aux = aux + ce
+                dinner.append(d.mul_(self.loss_coef / len(inner)))
             aux = aux / len(inner)
         eng.backward(dpred, dinner)
         return loss.float(), aux.float()
@@ -368,9 +279,4 @@ class PFENetTrainer(Stage1Trainer):
         return loss, aux, pred
 
     def train_step(self, sup_img, sup_mask, qry_img, qry_msk=None):
-        ins = [t.to(self.device) for t in (sup_img, sup_mask, qry_img, qry_msk)]
-        self.eng.buckets.enabled = self.collectives
-        loss, aux, _ = self.forward_backward(*ins)
-        self.optimizer_step()
-        self.eng.buckets.enabled = False
-        return loss, aux
+        return self._step((sup_img, sup_mask, qry_img, qry_msk), self.forward_backward)[:2]

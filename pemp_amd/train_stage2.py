@@ -22,7 +22,7 @@ import torch
 
 from . import ops, train_ops as T
 from .ops import ConvParams
-from .train_engine import Stage1TrainEngine, Stage1Trainer, _BN, _Conv, _SliceWgrad, _enqueue_wgrad, conv2d
+from .train_engine import Stage1TrainEngine, Stage1Trainer, _BN, _Conv, _SliceWgrad, _enqueue_wgrad, block_handles, conv2d
 
 _CM_STRIDES = (2, 1, 2)          # backbones.py:230,235,240
 
@@ -64,7 +64,71 @@ class _ConvCM(_Conv):
                       accumulate)
 
 
-class Stage2TrainEngine(Stage1TrainEngine):
+class _ASPPNoBN:
+    """ASPP without BatchNorm, forward and backward, for an engine that has ``aspp_conv``, ``l6``, ``midc``, ``drop_rate2`` and
+    ``aspp_drop_names``: global branch + four conv branches, each conv -> ReLU -> Dropout2d, and ``layer6`` over their
+    concatenation as two weight slices (the global branch enters as a per-image bias)."""
+
+    #: reference names of the five branches' Dropout2d modules (the keys of ``self.draws``)
+    aspp_drop_names = tuple(f"encoder.purifier.6.aspp_{i}.2" for i in range(5))
+
+    def _aspp_forward(self, xb, tape, out_relu=False):
+        """-> layer6's output (``out_relu``: with a ReLU, CANet's)."""
+        nimg, h, w, _ = xb.shape
+        midc, names = self.midc, self.aspp_drop_names
+        gap = ops.global_avgpool(xb)
+        g0 = conv2d(gap.view(nimg, 1, 1, -1), self.aspp_conv[0].fwd_params(relu=True))
+        g0d, m0 = self._drop(g0, (names[0],), self.drop_rate2)
+        l6w = self.l6.weight
+        w6 = self.flat.krsc(l6w)                                              # [512, 1280]
+        w6g = ConvParams(w6[:, :midc].contiguous(), None, self.l6.bias.data, midc, l6w.shape[0], 1, 1, 1, 0, 1, midc, False, False)
+        bias6 = conv2d(g0d, w6g)
+        cat = self._new(nimg, h, w, 4 * midc)                                 # post-ReLU branch outputs u_i
+        for i in range(1, 5):
+            conv2d(xb, self.aspp_conv[i].fwd_params(relu=True), out=cat[..., (i - 1) * midc:i * midc])
+        # the four branch Dropout2d layers at once
+        catd, ms = self._drop(cat, names[1:], self.drop_rate2)
+        w6m = ConvParams(w6[:, midc:].contiguous(), None, None, 4 * midc, l6w.shape[0], 1, 1, 1, 0, 1, 4 * midc, False, out_relu)
+        feat = conv2d(catd, w6m, shift_override=bias6.view(nimg, -1), per_image_shift=True)
+        tape.update(xb=xb, gap=gap, g0=g0, m0=m0, g0d=g0d, cat=cat, catd=catd,
+                    ms=ms, w6=w6, hw=(nimg, h, w))
+        return feat
+
+    def _aspp_backward(self, dfeat):
+        """``dfeat``: the gradient at layer6's pre-activation -> the gradient at the ASPP's input."""
+        tp, midc = self.tape, self.midc
+        nimg, h, w = tp["hw"]
+        l6w = self.l6.weight
+        cout = l6w.shape[0]
+        w6 = tp["w6"]
+        dw6 = self.flat.krsc_grad(l6w)
+        _enqueue_wgrad(self.flat, _SliceWgrad(4 * midc, cout, [(dw6[:, midc:], slice(None))]), tp["catd"], dfeat, self.ws)      # side stream
+        dcat = conv2d(dfeat, ConvParams(T.dgrad_weight(w6[:, midc:].contiguous(), 1, 1), None, None, cout, 4 * midc,
+                                            1, 1, 1, 0, 1, cout, False, False))
+        s = ops.global_avgpool(dfeat) * float(h * w)                          # per-image column sums [N, 512]
+        self.l6.bias.grad.copy_(s.sum(dim=0))
+        _enqueue_wgrad(self.flat, _SliceWgrad(midc, cout, [(dw6[:, :midc], slice(None))]), tp["g0d"], s.view(nimg, 1, 1, -1), self.ws)
+        dg0 = conv2d(s.view(nimg, 1, 1, -1), ConvParams(T.dgrad_weight(w6[:, :midc].contiguous(), 1, 1), None, None, cout,
+                                                            midc, 1, 1, 1, 0, 1, cout, False, False))
+        dcat = self._drop_bwd(dcat, tp["ms"])
+        dxb = None
+        for i in range(1, 5):
+            conv = self.aspp_conv[i]
+            g = self._new(nimg, h, w, midc)
+            sl = slice((i - 1) * midc, i * midc)
+            T.relu_bias_bwd(dcat[..., sl], tp["cat"][..., sl], g, relu=True, ws_cache=self.ws, out=conv.conv.bias.grad)
+            conv.wgrad(tp["xb"], g, self.ws)
+            dxb = conv2d(g, conv.dgrad_params(), residual=dxb)            # branch gradients accumulate in the epilogue
+        conv0 = self.aspp_conv[0]
+        dg0 = self._drop_bwd(dg0, tp["m0"])
+        g = self._new(nimg, 1, 1, midc)
+        T.relu_bias_bwd(dg0, tp["g0"], g, relu=True, ws_cache=self.ws, out=conv0.conv.bias.grad)
+        conv0.wgrad(tp["gap"].view(nimg, 1, 1, -1), g, self.ws)
+        T.gap_bwd_add(conv2d(g, conv0.dgrad_params()).view(nimg, -1), dxb)
+        return dxb
+
+
+class Stage2TrainEngine(_ASPPNoBN, Stage1TrainEngine):
     def _init_trunk(self, bb):
         f = self.flat
         self.stem = (_Conv(f, bb.conv1, stem=True), _BN(bb.bn1))
@@ -72,12 +136,7 @@ class Stage2TrainEngine(Stage1TrainEngine):
         for name, lin in (("layer1", bb.linear1), ("layer2", bb.linear2), ("layer3", bb.linear3)):
             self.stage_first.append(len(self.blocks))
             self.lin.append(lin)
-            for i, blk in enumerate(getattr(bb, name)):
-                mk = _ConvCM if i == 0 else _Conv
-                self.blocks.append(dict(
-                    c1=mk(f, blk.conv1), b1=_BN(blk.bn1), c2=_Conv(f, blk.conv2), b2=_BN(blk.bn2),
-                    c3=_Conv(f, blk.conv3), b3=_BN(blk.bn3),
-                    ds=(mk(f, blk.downsample[0]), _BN(blk.downsample[1])) if blk.downsample is not None else None))
+            self.blocks += [block_handles(f, blk, first=_ConvCM if i == 0 else None) for i, blk in enumerate(getattr(bb, name))]
         self.drop_rate2 = 0.0
 
     def _init_tail(self, model):
@@ -141,90 +200,11 @@ class Stage2TrainEngine(Stage1TrainEngine):
         self._cbn_bwd(dy, tp["stem"], *self.stem, need_dx=False)
 
     # -- purifier: conv+ReLU+Dropout2d twice, ASPP (no BN), layer6 ------------------------------
-    def _drop(self, y, n, c, layers):
-        """nn.Dropout2d(drop_rate2) in train(): one Bernoulli(1-p)/(1-p) multiplier per (image, channel).  ``layers``: the
-        reference names of the Dropout2d modules this call stands for, channel ranges in order; ``self.draws``
-        ({layer: uniforms [n, channels]}) replaces the Philox stream by given draws (parity tests)."""
-        if self.drop_rate2 <= 0.0:
-            return y, None
-        u = None
-        if self.draws is not None:
-            u = torch.cat([self.draws[k] for k in layers], dim=1).contiguous()
-            if tuple(u.shape) != (n, c) or u.dtype != torch.float32 or u.device != y.device:
-                raise ValueError(f"dropout2d draws of {layers}: want float32 {(n, c)} on {y.device}")
-        m = T.dropout2d_mask(n, c, self.drop_rate2, self.rng, self.device, uniforms=u)
-        return T.channel_scale(y, m), m
-
-    @staticmethod
-    def _drop_bwd(dy, m):
-        return dy if m is None else T.channel_scale(dy, m)
-
-    #: reference names of the five branches' Dropout2d modules (the keys of ``self.draws``)
-    aspp_drop_names = tuple(f"encoder.purifier.6.aspp_{i}.2" for i in range(5))
-
-    def _aspp_forward(self, xb, tape, out_relu=False):
-        """ASPP without BatchNorm: global branch + four conv branches, each conv -> ReLU -> Dropout2d, and ``layer6`` over their
-        concatenation as two weight slices (the global branch enters as a per-image bias) -> layer6's output (``out_relu``: with a
-        ReLU, CANet's).  Needs ``self.aspp_conv``, ``self.l6``, ``self.midc``."""
-        nimg, h, w, _ = xb.shape
-        midc, names = self.midc, self.aspp_drop_names
-        gap = ops.global_avgpool(xb)
-        g0 = conv2d(gap.view(nimg, 1, 1, -1), self.aspp_conv[0].fwd_params(relu=True))
-        g0d, m0 = self._drop(g0, nimg, midc, (names[0],))
-        l6w = self.l6.weight
-        w6 = self.flat.krsc(l6w)                                              # [512, 1280]
-        w6g = ConvParams(w6[:, :midc].contiguous(), None, self.l6.bias.data, midc, l6w.shape[0], 1, 1, 1, 0, 1, midc, False, False)
-        bias6 = conv2d(g0d, w6g)
-        cat = self._new(nimg, h, w, 4 * midc)                                 # post-ReLU branch outputs u_i
-        for i in range(1, 5):
-            conv2d(xb, self.aspp_conv[i].fwd_params(relu=True), out=cat[..., (i - 1) * midc:i * midc])
-        # the four branch Dropout2d layers at once
-        catd, ms = self._drop(cat, nimg, 4 * midc, names[1:])
-        w6m = ConvParams(w6[:, midc:].contiguous(), None, None, 4 * midc, l6w.shape[0], 1, 1, 1, 0, 1, 4 * midc, False, out_relu)
-        feat = conv2d(catd, w6m, shift_override=bias6.view(nimg, -1), per_image_shift=True)
-        tape.update(xb=xb, gap=gap, g0=g0, m0=m0, g0d=g0d, cat=cat, catd=catd,
-                    ms=ms, w6=w6, hw=(nimg, h, w))
-        return feat
-
-    def _aspp_backward(self, dfeat):
-        """``dfeat``: the gradient at layer6's pre-activation -> the gradient at the ASPP's input."""
-        tp, midc = self.tape, self.midc
-        nimg, h, w = tp["hw"]
-        l6w = self.l6.weight
-        cout = l6w.shape[0]
-        w6 = tp["w6"]
-        dw6 = self.flat.krsc_grad(l6w)
-        _enqueue_wgrad(self.flat, _SliceWgrad(dw6[:, midc:], 4 * midc, cout), tp["catd"], dfeat, self.ws)      # side stream
-        dcat = conv2d(dfeat, ConvParams(T.dgrad_weight(w6[:, midc:].contiguous(), 1, 1), None, None, cout, 4 * midc,
-                                            1, 1, 1, 0, 1, cout, False, False))
-        s = ops.global_avgpool(dfeat) * float(h * w)                          # per-image column sums [N, 512]
-        self.l6.bias.grad.copy_(s.sum(dim=0))
-        _enqueue_wgrad(self.flat, _SliceWgrad(dw6[:, :midc], midc, cout), tp["g0d"], s.view(nimg, 1, 1, -1), self.ws)
-        dg0 = conv2d(s.view(nimg, 1, 1, -1), ConvParams(T.dgrad_weight(w6[:, :midc].contiguous(), 1, 1), None, None, cout,
-                                                            midc, 1, 1, 1, 0, 1, cout, False, False))
-        dcat = self._drop_bwd(dcat, tp["ms"])
-        dxb = None
-        for i in range(1, 5):
-            conv = self.aspp_conv[i]
-            g = self._new(nimg, h, w, midc)
-            sl = slice((i - 1) * midc, i * midc)
-            T.relu_bias_bwd(dcat[..., sl], tp["cat"][..., sl], g, relu=True, ws_cache=self.ws, out=conv.conv.bias.grad)
-            conv.wgrad(tp["xb"], g, self.ws)
-            dxb = conv2d(g, conv.dgrad_params(), residual=dxb)            # branch gradients accumulate in the epilogue
-        conv0 = self.aspp_conv[0]
-        dg0 = self._drop_bwd(dg0, tp["m0"])
-        g = self._new(nimg, 1, 1, midc)
-        T.relu_bias_bwd(dg0, tp["g0"], g, relu=True, ws_cache=self.ws, out=conv0.conv.bias.grad)
-        conv0.wgrad(tp["gap"].view(nimg, 1, 1, -1), g, self.ws)
-        T.gap_bwd_add(conv2d(g, conv0.dgrad_params()).view(nimg, -1), dxb)
-        return dxb
-
     def _tail_forward(self, x, tape):
-        nimg, h, w, _ = x.shape
         ya = conv2d(x, self.p0.fwd_params(relu=True))
-        xa, ma = self._drop(ya, nimg, ya.shape[-1], ("encoder.purifier.2",))
+        xa, ma = self._drop(ya, ("encoder.purifier.2",), self.drop_rate2)
         yb = conv2d(xa, self.p3.fwd_params(relu=True))
-        xb, mb = self._drop(yb, nimg, yb.shape[-1], ("encoder.purifier.5",))
+        xb, mb = self._drop(yb, ("encoder.purifier.5",), self.drop_rate2)
         feat = self._aspp_forward(xb, tape)
         tape.update(p0_in=x, ya=ya, ma=ma, xa=xa, yb=yb, mb=mb)
         return feat
@@ -250,22 +230,14 @@ class Stage2Trainer(Stage1Trainer):
 
     def __init__(self, stage1, model, lr=1e-3, momentum=0.9, weight_decay=5e-4, device=None, drop_rate2=None,
                  loss="ce", sigma=5.0, use_graph=False):
-        from .core import losses
         from .networks.pemp_stage2 import net_ingredient
         cfg = net_ingredient.cfg
-        self.device = device if device is not None else torch.device("cuda", torch.cuda.current_device())
-        self.stage1, self.model = stage1, model
+        self._setup(model, device, lr, momentum, weight_decay, 0.0, loss, sigma, use_graph, cfg["dist_scalar"])
+        self.stage1 = stage1
         if stage1 is not None:
             stage1.eval()
-        model.train()
         self.eng = Stage2TrainEngine(model, self.device)
         self.eng.drop_rate2 = getattr(model, "drop_rate2", cfg["drop_rate2"]) if drop_rate2 is None else drop_rate2
-        self.lr, self.momentum, self.wd, self.max_norm = lr, momentum, weight_decay, 0.0
-        self.protos = 0 if model.ctr is None else model.ctr.shape[1] // 2
-        self.dist_scalar = cfg["dist_scalar"]
-        self.last_grad_norm, self.nesterov, self.optimizer = None, False, None
-        self.use_graph, self._graphs = use_graph, {}
-        self.loss_obj = losses.get({"loss": loss, "sigma": sigma})
         self._groups = {}
 
     def prior(self, sup_img, sup_mask, qry_img):
@@ -302,10 +274,6 @@ class Stage2Trainer(Stage1Trainer):
         return self._head_hip(feat, sup_mask, qry_msk, B, S, Q)
 
     def train_step(self, sup_img, sup_mask, qry_img, qry_msk=None, qry_prior=None):
-        ins = [t.to(self.device) for t in (sup_img, sup_mask, qry_img, qry_msk)]
-        ins.append(self.prior(*ins[:3]) if qry_prior is None else qry_prior.to(self.device))
-        self.eng.buckets.enabled = self.collectives and not self.use_graph   # purifier / ASPP bucket goes out under the trunk's backward
-        loss = self._graphed_forward_backward(*ins) if self.use_graph else self.forward_backward(*ins)[0]
-        self.optimizer_step()
-        self.eng.buckets.enabled = False
-        return loss
+        def run(*ins):        # (the purifier / ASPP bucket goes out under the trunk's backward)
+            return self._loss_step(*ins, self.prior(*ins[:3]) if qry_prior is None else qry_prior.to(self.device))
+        return self._step((sup_img, sup_mask, qry_img, qry_msk), run)

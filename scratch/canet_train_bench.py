@@ -47,7 +47,8 @@ def main():
     from pemp_amd import ops, synth, train_ops as T
     from pemp_amd.networks import canet as m
     from pemp_amd.ops import ConvParams
-    from pemp_amd.train_canet import MID, CANetTrainer, _SliceWgradK
+    from pemp_amd.train_canet import MID, CANetTrainer
+    from pemp_amd.train_engine import _SliceWgrad
     dev = torch.device("cuda:0")
     net = m.CaNet(None)
     net.load_state_dict(synth.wgen_state_dict_for(net, m.WGEN_SEED))
@@ -119,11 +120,12 @@ def main():
     _, stats, _ = ops.eval_tail(pred, gt, ws_cache=eng.ws)
     dpred = T.upsample_ce_bwd(pred, gt, stats)
     x6, dx6 = torch.randn((B, h, w, MID), device=dev), torch.empty((B, h, w, MID), device=dev)
-    w7 = f.krsc(eng.l7.weight)
+    l7 = eng.l7.conv
+    w7 = f.krsc(l7.weight)
     kern = {
         "a_zterm_bwd": lambda: T.canet_zterm_bwd(g55, w55[:, :, MID:], z, dw55[:, :, MID:], c55.dil, ws_cache=eng.ws),
         "b_support_vector_bwd": lambda: T.canet_support_vector_bwd(z, smask, S, df),
-        "c_cls_bwd": lambda: T.canet_cls_bwd(dpred, x6, w7, dx6, f.krsc_grad(eng.l7.weight), eng.l7.bias.grad, ws_cache=eng.ws),
+        "c_cls_bwd": lambda: T.canet_cls_bwd(dpred, x6, w7, dx6, f.krsc_grad(l7.weight), l7.bias.grad, ws_cache=eng.ws),
         "d_upsample_ce_bwd": lambda: T.upsample_ce_bwd(pred, gt, stats),
     }
     ms = {k: round(timed(fn, args.steps), 4) for k, fn in kern.items()}
@@ -136,7 +138,7 @@ def main():
     wd = f.dgrad_krsc(c55.conv.weight)                                         # [512, 9 * 256]
     dq = torch.empty((B, h, w, MID), device=dev)
     pdq = ConvParams(wd[:MID], None, None, MID, MID, 3, 3, 1, c55.dil * 2 - c55.pad, c55.dil, wd.shape[1], False, False)
-    wg_q = _SliceWgradK(dw55[:, :, :MID], MID, c55)
+    wg_q = _SliceWgrad(MID, MID, [(dw55[:, :, :MID], slice(None))], 3, c55.pad, c55.dil)
 
     def split_form():
         wg_q._wgrad_now(fq, g55, eng.ws)

@@ -333,6 +333,26 @@ def test_trainer_plumbing(hip_lib, dev):
     assert not torch.equal(got, stale.to(dev).eval()(dsup, dmsk, dqry, False, history_mask=dh))
 
 
+def test_two_trainers_from_one_seed_take_the_same_steps(hip_lib, dev, monkeypatch):
+    """Dropout2d on (p = 0.5) with no pinned draws: the masks come from the Philox stream, seeded from torch's seed at
+    construction; the kernel variants are fixed (AUTOTUNE off) and no reduction is atomic.  So two trainers, each built after
+    the same ``torch.manual_seed``, end two ``train_step``s on one batch with equal flat parameters and equal losses, bit for
+    bit -- and the two steps of a trainer draw different masks."""
+    from pemp_amd import ops
+    monkeypatch.setattr(ops, "AUTOTUNE", False)
+    g, sup, msk, qry, gt, hist, _ = canet_ref.fixture_inputs("canet_trainstep")
+    runs = []
+    for _ in range(2):
+        torch.manual_seed(77)
+        tr, _ = _trainer(dev, True, 0.5)
+        assert tr.eng.draws is None and tr.eng.drop_rate2 == 0.5
+        losses = [tr.train_step(sup, msk, qry, qry_msk=gt, history_mask=hist[:, None])[0] for _ in range(2)]
+        torch.cuda.synchronize()
+        runs.append((torch.stack(losses), tr.eng.flat.data.clone()))
+    assert torch.equal(runs[0][0], runs[1][0]) and float(runs[0][0][0]) != float(runs[0][0][1]), runs
+    assert torch.equal(runs[0][1], runs[1][1])
+
+
 def test_history_drop_follows_the_reference_sampler():
     """``HistorySlots``: a key's first episode reads -1; on a second pass over the same keys the read slot is -1 exactly where a
     replayed RandomState(9876) draws <= 0.3 (one draw per episode that has a stored history, in batch order)."""

@@ -374,6 +374,24 @@ def test_bench_train_stub_roofline_pass_with_collectives_left_on_would_mismatch(
     assert not dist.is_initialized()
 
 
+def test_bench_stub_trainer_steps_without_the_trainer_constructor():
+    """bench.py's stub subclasses ``Stage1Trainer`` and assigns only ``eng, use_graph, optimizer, calls, device``:
+    ``train_step`` / ``optimizer_step`` / ``reduce_gradients`` / ``exposed_comm_ms`` must work on such an object, i.e. whatever
+    else they read has a class-level default.  One step: gradient 1 everywhere, no process group (scale 1), weights -0.1."""
+    import bench
+    tr = bench.stub_trainer(0)
+    assert set(vars(tr)) == {"eng", "use_graph", "optimizer", "calls", "device"}
+    loss = tr.train_step(*[torch.zeros(1)] * 4)
+    assert float(loss) == 1.0 and tr.calls == 1
+    assert torch.equal(tr.eng.flat.data, torch.full((1 << 16,), -0.1))
+    assert tr.eng.buckets.enabled is False and tr.eng.buckets.next == 0
+    assert tr.collectives is True and tr.comm_log is None and tr.exposed_comm_ms() is None
+    tr.comm_log = []
+    assert float(tr.train_step(*[torch.zeros(1)] * 4)) == 2.0
+    assert len(tr.comm_log) == 1 and tr.exposed_comm_ms() >= 0.0
+    assert set(vars(tr)) == {"eng", "use_graph", "optimizer", "calls", "device", "comm_log"}     # a step assigns nothing else
+
+
 def test_bench_dump_outputs_hold_the_last_timed_step(tmp_path):
     """`--dump-outputs DIR` writes what the LAST timed step computed, before the roofline pass takes more steps: the stub's
     loss counts its calls and every step moves each weight by -0.1, so --warmup 2 --steps 3 leave loss 5 and weights -0.5."""
