@@ -700,6 +700,32 @@ int pemp_rpmms_prob_map_f32(const float* qry, int ldq, const float* mu, float* o
 int pemp_rpmms_proto_sum_f32(const float* wz, const float* mu, const float* base, int ldb, const float* bias, float* T,
                              float* out, int ldo, long long gstride, int B, int h, int w, int C, int dil, void* stream);
 
+/* ---- RPMMs head training (csrc/rpmms_bwd.hip): layer55 over the ten prototype columns with one Dropout2d draw per column, its
+ * adjoint, and the adjoint of the softmax that makes the next pass's history.  No atomics; the one cross-block sum goes through
+ * `work` in a fixed order: bit-stable run to run.  C == 256.
+ * pemp_rpmms_proto_sum_f32 with a multiplier mult [B][10][C] (0 or 1 / (1 - p)) on each column's ReLU output before the sum
+ * over a mixture's columns: out_g = sum_{i in g, ascending} mult_i * relu(base + bias + R_i).  The same tap order and the same
+ * sum: with every multiplier 1.0 the output is pemp_rpmms_proto_sum_f32's, bit for bit.  T is written as there.            */
+int pemp_rpmms_proto_sum_train_f32(const float* wz, const float* mu, const float* base, int ldb, const float* bias,
+                                   const float* mult, float* T, float* out, int ldo, long long gstride, int B, int h, int w, int C,
+                                   int dil, void* stream);
+/* Its adjoint.  dout: the gradients at the three mixture outputs, dout[g * gstride + (b * h * w + p) * ldd + c]; base, bias, T,
+ * mult as in the forward (every column's pre-activation is recomputed; no per-column gradient is materialised).
+ *   dbase[b][p][c] (lddb) = sum_g sum_{i in g} mult_i 1[pre_i > 0] dout_g          (columns ascending)
+ *   G[b][i][tap][c]       = sum of column i's gated gradient over the pixels whose tap source lies inside the image
+ *   dW[(co * 9 + tap) * ldw + ci] = sum_b sum_i G[b][i][tap][co] mu[b][0][i][ci]    (optional; written, not accumulated: the
+ *                           prototype half of layer55's KRSC weight gradient, the pointer already at its first column)
+ *   dbias[c]              = sum_b sum_i G[b][i][4][c]                               (optional; = the sum of dbase over b, p)
+ * work: pemp_rpmms_proto_sum_bwd_work_floats(B, h, w, C) floats of the caller.                                              */
+size_t pemp_rpmms_proto_sum_bwd_work_floats(int B, int h, int w, int C);
+int pemp_rpmms_proto_sum_bwd_f32(const float* dout, int ldd, long long gstride, const float* base, int ldb, const float* bias,
+                                 const float* T, const float* mult, const float* mu, float* dbase, int lddb, float* G, float* dW,
+                                 int ldw, float* dbias, float* work, size_t work_floats, int B, int h, int w, int C, int dil,
+                                 void* stream);
+/* Adjoint of the softmax over two classes (rpmms.py:250-251,285: the history of pass p + 1 is the softmax of pass p's logits):
+ * dpred[b][k][p] += prob[b][k][p] * (dh_k - sum_j prob[b][j][p] dh_j), dh_k = dh[(b * HW + p) * ldh + k].  dpred, prob [B][2][HW]. */
+int pemp_rpmms_history_bwd_f32(const float* dh, int ldh, const float* prob, float* dpred, int B, int HW, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,15 +3,13 @@
 // and the sum over a mixture's prototypes of layer55(cat(query, prototype)) (:237-244) without the ten materialised convs.
 // All fp32, fixed summation orders, no atomics and no grid-wide wait: results are bit-stable run to run and do not depend on
 // the batch size (a block's work is a function of its image, its side and the feature size only).
-#include "common.h"
+#include "rpmms_common.h"
 
 namespace pemp {
 namespace {
 
 typedef __attribute__((ext_vector_type(4))) float rv4f;
 
-constexpr int RP_C = 256;                    // channels: one per thread of a block
-constexpr int RP_J = 10;                     // columns of the three mixtures side by side: K = 1 | 3 | 6
 constexpr int RP_GMAX = 16;                  // pixel slices (blocks) per image and side
 constexpr int RP_PART = RP_J * RP_C + 16;    // one block's partial: sums [10][256] | column sums [10] | padding
 constexpr int RP_MLD = RP_C + 4;             // mu table row stride: the 16-B reads of 11 rows fall on different banks
@@ -20,17 +18,6 @@ constexpr float RP_EPS = 1e-6f;
 constexpr float RP_KAPPA = 20.f;
 
 __device__ __forceinline__ rv4f ldv(const float* p) { return *(const rv4f*)p; }
-__device__ __forceinline__ float4 ld4(const float* p) { return *(const float4*)p; }
-
-__device__ __forceinline__ float4 add4(float4 a, float4 b) {
-    return make_float4(__fadd_rn(a.x, b.x), __fadd_rn(a.y, b.y), __fadd_rn(a.z, b.z), __fadd_rn(a.w, b.w));
-}
-__device__ __forceinline__ float4 relu4(float4 a) { return make_float4(fmaxf(a.x, 0.f), fmaxf(a.y, 0.f), fmaxf(a.z, 0.f), fmaxf(a.w, 0.f)); }
-
-// first column and width of mixture g
-__device__ __forceinline__ int group_first(int g) { return g == 0 ? 0 : g == 1 ? 1 : 4; }
-__device__ __forceinline__ int group_size(int g) { return g == 0 ? 1 : g == 1 ? 3 : 6; }
-
 // The current mu of one (image, side) from the G partials of the iteration before, every block for itself and every block in
 // the same order: mu'_j = (sum_g part_g[j]) / (1e-6 + sum_g colsum_g[j]), mu_j = mu'_j / (1e-6 + |mu'_j|).  Thread = channel;
 // returns the thread's ten values.  `red` is [RP_J][4], `cs` [RP_J].  The G <= 16 partials of a column are fetched as sixteen
@@ -287,35 +274,6 @@ __global__ __launch_bounds__(256) void prob_map_kernel(const float* __restrict__
     }
 }
 
-// T[b][i][tap][co] = sum_ci wz[tap][co][ci] mu[b][0][i][ci] for the ten foreground prototypes: one wave per (tap, co) row reads
-// the row once, float4 per lane along ci, and meets the ten prototypes with it; the lane partials are summed by the fixed
-// butterfly of wave_sum.  grid (rows / 4, B).
-__global__ __launch_bounds__(256) void tap_gemv_kernel(const float* __restrict__ wz, const float* __restrict__ mu,
-                                                       float* __restrict__ T, int rows) {
-    const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6), b = blockIdx.y;
-    if (row >= rows) return;                                  // whole waves leave together: no shuffle below is split
-    const float4 a = ld4(wz + (size_t)row * RP_C + 4 * lane);
-    const float* zb = mu + (size_t)b * 2 * RP_J * RP_C + 4 * lane;
-#pragma unroll
-    for (int i = 0; i < RP_J; ++i) {
-        const float4 v = ld4(zb + i * RP_C);
-        const float s = wave_sum(__fmaf_rn(a.w, v.w, __fmaf_rn(a.z, v.z, __fmaf_rn(a.y, v.y, __fmaf_rn(a.x, v.x, 0.f)))));
-        if (lane == 0) T[((size_t)b * RP_J + i) * rows + row] = s;
-    }
-}
-
-// The in-image taps of one prototype at a border pixel, in tap order (kept out of line: the ring is a small share of the pixels
-// and its 90 loads must not cost the interior path its registers).
-__device__ __noinline__ float4 border_taps(const float* __restrict__ Ti, int y, int x, int h, int w, int dil) {
-    float4 R = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int tap = 0; tap < 9; ++tap) {
-        const int sy = y + (tap / 3 - 1) * dil, sx = x + (tap % 3 - 1) * dil;
-        if (sy < 0 || sy >= h || sx < 0 || sx >= w) continue;
-        R = add4(R, ld4(Ti + (size_t)tap * RP_C));
-    }
-    return R;
-}
-
 // out_g[b][p][c] = sum_{i in mixture g, ascending} relu(base[b][p][c] + bias[c] + R_i[p][c]), R_i = the sum, in tap order 0..8,
 // of T[b][i][tap][c] over the taps of the 3x3 / dilation dil conv whose source pixel lies inside the image.  A thread owns four
 // channels and walks the pixels of its chunk; the all-taps sums of its channels (every interior pixel's R_i) stay in registers,
@@ -359,8 +317,6 @@ __global__ __launch_bounds__(256) void proto_sum_kernel(const float* __restrict_
         *(float4*)(op + 2 * gstride) = g2;
     }
 }
-
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 int em_blocks(int HW) { return std::min(RP_GMAX, cdiv(HW, 64)); }
 

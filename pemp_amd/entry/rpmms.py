@@ -7,14 +7,18 @@ the model's ``pmm_mu0`` buffer, outside the captured graph) unless the init is p
 
 The round loop is the shared one: it aggregates the cross-entropy of the final output (what the reference calls ``loss_p1``)
 with mIoU and bIoU, and the command's result line says ``Loss_p1``.  The sum of the three passes' losses is returned per step by
-``test_step``; aggregating it over a round would need a wider ``DeviceRoundTable``.  Training is not
-ported: ``train`` raises."""
+``test_step``; aggregating it over a round would need a wider ``DeviceRoundTable``.
+
+``train_head`` trains the head behind a FROZEN trunk (``pemp_amd.train_rpmms``): a deliberate departure from the reference, whose
+``maybe_fix_params()`` freezes nothing for RPMMs so that its ``train`` also updates the trunk's convs.  ``train`` (the
+reference's command name) still raises: trunk training is not built."""
 import numpy as np
 import torch
 
 from .. import ops
 from ..config import Experiment
 from ..networks.rpmms import WGEN_SEED, ModelClass, net_ingredient  # noqa: F401
+from ..train_rpmms import RPMMsTrainer
 from .pemp_stage1 import INGREDIENTS, SyntheticEpisodes, eval_episodes, get_val_labels, num_classes  # noqa: F401
 from .pemp_stage1 import Evaluator as _Evaluator
 
@@ -84,6 +88,57 @@ def test(_config, split, shot, query, exp_id, ckpt, seed):
     loss, miou, biou = ev.start_eval_loop(data, num_classes(d["dataset"]), split, _config["te"]["epochs"], logger,
                                           batch=d["test_bs"], dataset_name=d["dataset"])
     return f"Loss_p1: {loss:.4f}, mIoU: {np.mean(miou) * 100:.2f}, bIoU: {np.mean(biou) * 100:.2f}"
+
+
+def head_train_batches(trainer, dcfg, shot, split, rank, steps_per_epoch, device):
+    """-> ``batches(epoch)`` for ``TrainingLoop``: synthetic episodes with the query label at the input size (the reference resizes
+    a training label with its image).  When an epoch's batches are used up, the reference's per-epoch line (entry/rpmms.py:133,
+    141-144: the means of loss / loss_p1 / loss_p2 over the epoch's steps) is logged from what the trainer collected."""
+    from .train_stage1 import synthetic_batches
+
+    def batches(epoch):
+        trainer.epoch_losses = []
+        yield from synthetic_batches(dcfg["bs"], shot, steps_per_epoch, dcfg["seed"] + 7919 * epoch, rank, dcfg["height"], dcfg["width"])
+        if trainer.epoch_losses and trainer.logger is not None:
+            loss, p1, p2 = torch.stack([torch.stack(row) for row in trainer.epoch_losses]).mean(dim=0).tolist()
+            lr = trainer.optimizer.param_groups[0]["lr"] if trainer.optimizer is not None else trainer.lr
+            trainer.logger.info(f"[TRAIN] loss: {loss:.5f} - loss_p1: {p1:.5f} - loss_p2: {p2:.5f} - lr: {lr:g}")
+    return batches
+
+
+class HeadTrainer(RPMMsTrainer):
+    """``RPMMsTrainer`` that keeps every step's (loss, loss_p1, loss_p2) for the epoch's log line (``head_train_batches``)."""
+
+    def __init__(self, model, logger=None, **kw):
+        super().__init__(model, **kw)
+        self.logger, self.epoch_losses = logger, []
+
+    def train_step(self, sup_img, sup_mask, qry_img, qry_msk=None):
+        out = super().train_step(sup_img, sup_mask, qry_img, qry_msk=qry_msk)
+        self.epoch_losses.append(out)
+        return out
+
+
+@ex.command
+def train_head(_config, split, shot, query, seed, loss, sigma, exp_id, ckpt):
+    """``python -m pemp_amd.entry.rpmms train_head with split=0 ckpt=<checkpoint | wgen>``: RPMMs' training procedure
+    (entry/rpmms.py:107-149) for a FROZEN trunk -- the head trains on the HIP path (the reference also updates the trunk's convs:
+    not built), per-epoch evaluation, ``ckpt.pth`` / ``bestckpt.pth`` (reference-loadable state_dicts) under
+    ``<g.model_dir>/<tag>/<id>``."""
+    from .pemp_stage1 import run_training
+    if shot != 1 or query != 1:
+        raise ValueError("RPMMs is 1-shot with one query per episode (shot=1 query=1), as the reference is (rpmms.py:129, 266-267)")
+    if _config["data"].get("base_dir"):
+        raise ValueError("train_head reads synthetic episodes only: leave data.base_dir empty")
+
+    def make_trainer(logger, dev):
+        from ..core.snapshots import load_for_eval
+        model = ModelClass(logger)
+        load_for_eval(model, _config, exp_id, ckpt, logger, wgen_seed=WGEN_SEED)     # the frozen trunk comes from a checkpoint
+        return HeadTrainer(model.freeze_trunk(), logger=logger, lr=_config["tr"]["lr"], device=dev, loss=loss, sigma=sigma)
+
+    return run_training(_config, NAME, make_trainer, lambda tr, dev: Evaluator(tr.model, device=dev), split, shot, seed, exp_id,
+                        batches=head_train_batches)
 
 
 @ex.command

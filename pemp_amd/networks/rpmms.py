@@ -4,7 +4,8 @@ constructor :146-211; forward :213-287; loss / prediction :289-319; load_weights
 The module tree holds the reference's parameters under the reference's ``state_dict`` keys (tests/golden/
 state_keys_rpmms.json, with the reference's spelling ``residule``); the forward runs on ``pemp_amd.rpmms_engine`` (HIP kernels
 only).  Unlike the reference the constructor reads no ImageNet checkpoint: a trained model comes from ``load_weights`` /
-``ckpt``.  Inference only: a ``train()``-mode forward raises.  1-shot, one query: the reference's own ``bmm`` (:129) and ``cat``
+``ckpt``.  A ``train()``-mode forward raises: the head trains through ``pemp_amd.train_rpmms`` (explicit forward / backward behind
+a frozen trunk, ``freeze_trunk``), not through autograd.  1-shot, one query: the reference's own ``bmm`` (:129) and ``cat``
 (:266-267) fail for anything else.
 
 The initial mu of the EM: the reference draws a fresh normal(0, sqrt(2 / K)) [1,256,K] tensor per forward and per K and
@@ -126,6 +127,13 @@ class RPMMs(_HeadMixin, backbones.BaseModel):
         """What an evaluation step does first: a fresh draw (the reference draws per forward) unless the init is pinned."""
         if not self.pmm_init_pinned:
             self.resample_pmm_init(generator)
+
+    def freeze_trunk(self):
+        """Every ``model_res`` parameter stops receiving gradients: what ``pemp_amd.train_rpmms`` trains behind (the reference's
+        ``maybe_fix_params()`` freezes nothing for RPMMs; the HIP path trains the head only).  ``layer5`` stays trainable."""
+        for prm in self.model_res.parameters():
+            prm.requires_grad = False
+        return self
 
     # -- engine ------------------------------------------------------------------------------------------------------------------
     def _build_engine(self, eng, arena):

@@ -725,3 +725,99 @@ def pfenet_merge_support_bwd(gs, w_s, svec, dw_s, ws_cache=None):
                                                      arr(*[t.data_ptr() for t in dw_s]), ldw, _p(svec), _p(dsvec), _p(ws), ws.numel(),
                                                      b, cin, cout, _stream()), "pfenet_merge_support_bwd")
     return dsvec
+
+
+# -- RPMMs head training (csrc/rpmms_bwd.hip) ---------------------------------------------------------------------------------
+def _rpmms_operands(who, base, bias, taps, mult, mu=None):
+    from .ops import RPMMS_COLS, _nhwc
+    ldb = _nhwc(base, "base")
+    b, h, w, c = base.shape
+    for t, shape, name in ((bias, (c,), "bias"), (taps, (b, RPMMS_COLS, 9, c), "taps"), (mult, (b, RPMMS_COLS, c), "mult"),
+                           (mu, (b, 2, RPMMS_COLS, c), "mu")):
+        if t is not None and (tuple(t.shape) != shape or not t.is_contiguous() or t.dtype != torch.float32):
+            raise ValueError(f"{who}: {name} must be contiguous fp32 {list(shape)}, got {tuple(t.shape)}")
+    return ldb, b, h, w, c
+
+
+def rpmms_proto_sum_train(wz, mu, base, bias, mult, out, dil=2, taps=None):
+    """``ops.rpmms_proto_sum`` in train() mode (rpmms.py:237-244 with layer55's Dropout2d drawn once per prototype): ``mult``
+    contiguous fp32 [B,10,256], column i's multiplier (0 or 1 / (1 - p)) on its ReLU output before the sum over the mixture's
+    columns; the other operands as there.  With every multiplier 1.0 the result is ``ops.rpmms_proto_sum``'s, bit for bit.
+    -> (out, taps): ``taps`` [B,10,9,256] is an operand of the backward."""
+    from .ops import RPMMS_COLS, _rpmms_groups_out
+    lib = _lib.load()
+    _chk_dev(wz, mu, base, bias, mult, out, taps)
+    b, h, w, c = base.shape
+    if taps is None:
+        taps = torch.empty((b, RPMMS_COLS, 9, c), dtype=torch.float32, device=base.device)
+    ldb = _rpmms_operands("rpmms_proto_sum_train", base, bias, taps, mult, mu)[0]
+    if tuple(wz.shape) != (9, c, c) or not wz.is_contiguous() or wz.dtype != torch.float32:
+        raise ValueError(f"rpmms_proto_sum_train: wz must be contiguous fp32 [9,{c},{c}]")
+    ldo, gstride = _rpmms_groups_out("rpmms_proto_sum_train", out, b, h, w, c, c)
+    _lib.check(lib.pemp_rpmms_proto_sum_train_f32(_p(wz), _p(mu), _p(base), ldb, _p(bias), _p(mult), _p(taps), _p(out), ldo, gstride,
+                                                  b, h, w, c, int(dil), _stream()), "rpmms_proto_sum_train")
+    return out, taps
+
+
+def rpmms_proto_bwd_work_floats(B, h, w, C=256):
+    """Size of ``rpmms_proto_sum_bwd``'s workspace (include/pemp_hip.h: B x 10 columns x G pixel blocks x 9 taps x C partial
+    sums, G = min(16, ceil(h w / 4)))."""
+    from .ops import RPMMS_COLS
+    return B * RPMMS_COLS * min(16, -(-(h * w) // 4)) * 9 * C
+
+
+def rpmms_proto_sum_bwd(dout, base, bias, taps, mult, dil=2, mu=None, dw_z=None, dbias=None, dbase=None, work=None, ws_cache=None):
+    """Adjoint of ``rpmms_proto_sum_train``: dout fp32 [3,B,h,w,ld >= 256] (the gradients at the three mixture outputs), base, bias,
+    taps, mult as in the forward -> (dbase NHWC [B,h,w,256], G [B,10,9,256]: per column and tap the sum of the column's gated
+    gradient over the pixels whose tap source lies inside the image).  With ``mu`` [B,2,10,256] and ``dw_z``, the prototype half
+    of layer55's KRSC weight gradient as a [Cout,9,Cin] view of unit channel stride (a column slice of [Cout,9,Cin_total]), dW_z
+    = sum_b sum_i G[b,i] (x) mu[b,0,i] is written there; ``dbias`` [256] takes the sum of dbase over images and pixels.  ``work``: a
+    fp32 buffer of ``rpmms_proto_bwd_work_floats`` elements (default: taken from ``ws_cache`` or allocated)."""
+    from .ops import RPMMS_COLS, _nhwc, _rpmms_groups_out
+    lib = _lib.load()
+    _chk_dev(dout, base, bias, taps, mult, mu, dw_z, dbias, dbase, work)
+    ldb, b, h, w, c = _rpmms_operands("rpmms_proto_sum_bwd", base, bias, taps, mult, mu)
+    ldd, gstride = _rpmms_groups_out("rpmms_proto_sum_bwd", dout, b, h, w, c, c)
+    if dbase is None:
+        dbase = torch.empty((b, h, w, c), dtype=torch.float32, device=base.device)
+    if tuple(dbase.shape) != (b, h, w, c):
+        raise ValueError(f"rpmms_proto_sum_bwd: dbase {tuple(dbase.shape)} != {(b, h, w, c)}")
+    lddb = _nhwc(dbase, "dbase")
+    ldw = 0
+    if dw_z is not None:
+        if mu is None:
+            raise ValueError("rpmms_proto_sum_bwd: dw_z needs mu")
+        if dw_z.dim() != 3 or dw_z.dtype != torch.float32 or tuple(dw_z.shape) != (c, 9, c) or dw_z.stride(2) != 1 \
+                or dw_z.stride(0) != 9 * dw_z.stride(1):
+            raise ValueError("rpmms_proto_sum_bwd: dw_z must be a fp32 [256,9,256] view with unit channel stride and dense rows")
+        ldw = dw_z.stride(1)
+    if dbias is not None and (tuple(dbias.shape) != (c,) or not dbias.is_contiguous() or dbias.dtype != torch.float32):
+        raise ValueError(f"rpmms_proto_sum_bwd: dbias must be contiguous fp32 [{c}]")
+    need = rpmms_proto_bwd_work_floats(b, h, w, c)
+    if work is None:
+        work = _ws(4 * need, base.device, ws_cache, ("rpmms_proto_bwd", b, h, w)).view(torch.float32)
+    if work.numel() < need or not work.is_contiguous() or work.dtype != torch.float32:
+        raise ValueError(f"rpmms_proto_sum_bwd: work must be a contiguous fp32 buffer of at least {need} elements")
+    G = torch.empty((b, RPMMS_COLS, 9, c), dtype=torch.float32, device=base.device)
+    _lib.check(lib.pemp_rpmms_proto_sum_bwd_f32(_p(dout), ldd, gstride, _p(base), ldb, _p(bias), _p(taps), _p(mult), _p(mu), _p(dbase),
+                                                lddb, _p(G), _p(dw_z), ldw, _p(dbias), _p(work), work.numel(), b, h, w, c, int(dil),
+                                                _stream()), "rpmms_proto_sum_bwd")
+    return dbase, G
+
+
+def rpmms_history_bwd(dh, prob, dpred):
+    """Adjoint of the two-class softmax that turns a pass's logits into the next pass's history (rpmms.py:250-251,285): dh NHWC
+    [B,h,w,2] (a channel slice is fine: the gradient at the two history channels), prob contiguous fp32 [B,2,h,w] (the softmax
+    that was fed forward) -> dpred [B,2,h,w] += prob_k (dh_k - sum_j prob_j dh_j), in place."""
+    from .ops import _nhwc
+    lib = _lib.load()
+    _chk_dev(dh, prob, dpred)
+    ldh = _nhwc(dh, "dh")
+    b, h, w, c = dh.shape
+    for t, name in ((prob, "prob"), (dpred, "dpred")):
+        if tuple(t.shape) != (b, 2, h, w) or not t.is_contiguous() or t.dtype != torch.float32:
+            raise ValueError(f"rpmms_history_bwd: {name} must be contiguous fp32 [{b},2,{h},{w}], got {tuple(t.shape)}")
+    if c != 2:
+        raise ValueError("rpmms_history_bwd: dh must hold the two history channels")
+    _lib.check(lib.pemp_rpmms_history_bwd_f32(_p(dh), ldh, _p(prob), _p(dpred), b, h * w, _stream()), "rpmms_history_bwd")
+    return dpred
