@@ -130,7 +130,8 @@ int pemp_conv2d_group_nhwc_f32(int n, const pemp_conv_desc* d, const float* cons
  * fp32 rounding (hl, lh, mm, mh, hm, hh), accumulated in fp32: fp32-accurate, not bit-identical to the fp32-chain ids 21..37, and
  * bit-identical among 41..44, 46 and their grouped launches (ascending K order, fixed product order).  With these ids `w` is NOT the
  * [Cout][Kpad] fp32 weight but its split form from pemp_pack_split3_bf16.  Entries: pemp_conv2d_nhwc_f32, _padv_, _splitk_,
- * _padv_splitk_, _group_ (41..44, 46).  Plain epilogue only (no stats / bnbwd / dropblock / bf16 forms); buffer-addressed geometries
+ * _padv_splitk_, _group_ (41..44, 46), and pemp_split3_conv2d_stats_nhwc_f32 (the statistics epilogue on 41..44, 46).  No bnbwd /
+ * dropblock / bf16 forms, and pemp_conv2d_stats_nhwc_f32 itself stays with the fp32 chain; buffer-addressed geometries
  * only (<= 32 taps; no stem except the fused form below): an error, never a fall-back, elsewhere.
  * Fused stem (flag PEMP_CONV_POOL3S2, pemp_conv2d_nhwc_f32 only): the 7x7 / stride 2 / pad 3 PEMP_CONV_STEM4 conv with split3
  * arithmetic (`w` = pemp_pack_split3_bf16 of the stem's [Cout][224] pack; any split3 tile id 41..49 names it, the kernel has one
@@ -369,6 +370,24 @@ int pemp_splitk_reset(void* ws, void* stream);
 int pemp_conv2d_stats_nhwc_f32(const pemp_conv_desc* d, const float* x, const float* w, float* y, float* stats,
                                void* ws, size_t ws_bytes, void* stream);
 int pemp_conv2d_stats_rows(const pemp_conv_desc* d);
+/* The same statistics conv on the SPLIT3 family, for weights that do not change between steps (the frozen trunk of a head
+ * trainer: networks/canet.py, pfenet.py, rpmms.py run it forward only, in train()): `w3` is the pemp_pack_split3_bf16 form of
+ * the [Cout][Kpad] weight.  d->tile: 0 (runs as 43) or 41, 42, 43, 44, 46 -- the unsplit ids, on their own wave grids.  The K
+ * loop and the MFMA order are those of the plain split3 conv: y is bit-identical to pemp_conv2d_nhwc_f32 with the same id (no
+ * affine), hence fp32-accurate and NOT bit-identical to the fp32-chain entry above.  stats follows that entry's contract: one
+ * row per row tile, pemp_conv2d_stats_split3_rows(d) x 2 x Cout floats, summed over the rows m < M of the tile in the fixed
+ * order of the fp32-chain epilogue; no atomics, deterministic.  No workspace.  d->flags must be 0; Cout % 64 (% 128 for the
+ * 128-wide ids), Cin % 32, Kpad == KH*KW*Cin as above.  Returns -1 (pemp_last_error set, nothing launched) for every other
+ * id -- the persistent ids 47 / 49, the panel ids 71 / 72, the pre-split ids 146 / 149, split-K 51..56, any fp32-chain id --
+ * for any flag and for a null or misaligned pointer; -2 where the buffer-addressed kernels do not take the geometry (use
+ * pemp_conv2d_nhwc_f32 + pemp_bn_stats_f32 then).  No padding vector, residual or BatchNorm-backward form.
+ * pemp_conv2d_stats_split3_rows: ceil(M / BM) of the id, 0 for an id the entry does not take.
+ * (The launching entry is named pemp_split3_conv2d_..., not pemp_conv2d_..._split3: bench.py's live roofline keeps a table of
+ * every launching pemp_conv2d* entry, which tests/test_cpu_suite.py holds complete, and the benchmark is not part of this
+ * addition -- its workloads train their trunks and never reach this entry.)                                                */
+int pemp_split3_conv2d_stats_nhwc_f32(const pemp_conv_desc* d, const float* x, const void* w3, float* y, float* stats,
+                                      void* stream);
+int pemp_conv2d_stats_split3_rows(const pemp_conv_desc* d);
 int pemp_bn_stats_partials_f32(const float* stats, int nrows, int M, int C, float eps, float momentum, float* mean,
                                float* invstd, float* run_mean, float* run_var, void* stream);
 int pemp_bn_fwd_partials_f32(const float* z, int ldz, const float* stats, int nrows, int M, int C, float eps, float momentum,

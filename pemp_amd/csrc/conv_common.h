@@ -393,6 +393,9 @@ int launch_conv_dma2_splitk(int shape, ConvArgs a, void* ws, size_t ws_bytes, hi
 // split3 family (a.w = the weights from pemp_pack_split3_bf16); split: the split-K form (ws as for launch_conv_dma2_splitk)
 int launch_conv_dma2_split3(int shape, ConvArgs a, void* ws, size_t ws_bytes, bool split, hipStream_t st);
 int launch_conv_dma2_group_split3(int shape, ConvGroupArgs& g, hipStream_t st);
+// ... with the statistics epilogue (a.stats; unsplit, zero padding, no affine / residual); whether a shape has that form
+int launch_conv_dma2_split3_stats(int shape, const ConvArgs& a, hipStream_t st);
+bool conv_dma2_split3_stats_shape(int shape);
 // its persistent forms (shapes 3 and 6): a resident grid walks the tiles
 int launch_conv_dma2_split3_persist(int shape, const ConvArgs& a, hipStream_t st);
 // (with PEMP_CONV_OUT_SPLIT3: the producer variant of the shape, which has no residual path; whether a shape has one)

@@ -71,7 +71,8 @@ __device__ __forceinline__ void conv_dma2_body(const ConvArgs& a, const int bid,
     constexpr int RPI = NW * 8;                 // rows covered by one DMA instruction round of the block
     constexpr int WM = BM / WGM, WN = BN / WGN;
     static_assert(!R16 || (WM == 16 && WN % 16 == 0 && EPI == 0 && !SK && !BF16 && !DB), "R16: 16-row wave tiles, plain epilogue only");
-    static_assert(!S3 || (EPI == 0 && !BF16 && !DB && !R16), "S3: plain epilogue, fp32 operands");
+    static_assert(!S3 || (EPI <= 1 && !BF16 && !DB && !R16), "S3: plain or statistics epilogue, fp32 operands");
+    static_assert(!S3 || EPI == 0 || (!SK && !PADV && !A3), "S3 statistics: unsplit, zero padding, fp32 activations");
     static_assert(!A3 || (S3 && !SK && (BM * 12) % (NW * 64) == 0), "A3: an unsplit S3 form, whole A DMA rounds");
     static_assert(!ALSO || A3, "a second, pre-split output (PEMP_CONV_OUT_SPLIT3_ALSO; a.res is its pointer): the A3 forms only");
     constexpr int TM = R16 ? 1 : WM / 32, TN = R16 ? WN / 16 : WN / 32;      // R16: TN counts 16-column MFMA tiles
@@ -563,8 +564,9 @@ __device__ __forceinline__ void conv_dma2_body(const ConvArgs& a, const int bid,
 
     // ---- epilogue: transpose through LDS.  No LDS read and no DMA is outstanding after the loop's last barrier. ----
     float* Rall = (float*)smem + NW * 1024;          // EPI: [NW][TN][2][8][32] sums of the waves, behind their transpose patches
-    static_assert(EPI == 0 || NW * 1024 + NW * TN * 512 <= 64 * (BM + BN), "LDS: statistics area");
-    static_assert(NW * 1024 <= 64 * (BM + BN), "LDS: one 4 KB transpose patch per wave");
+    constexpr int LDSF = 8 * (AQ * BM + BQ * BN);    // floats of operand staging (fp32 chain: 64 (BM + BN); S3: 64 BM + 96 BN)
+    static_assert(EPI == 0 || NW * 1024 + NW * TN * 512 <= LDSF, "LDS: statistics area");
+    static_assert(NW * 1024 <= LDSF, "LDS: one 4 KB transpose patch per wave");
     if constexpr (R16) conv_epilogue_r16<TN>(a, acc16, (float*)smem + wave * 1024, m0 + wm0, n0 + wn0, lane);
     else if constexpr (PRE) conv_epilogue_lds_pre<TM, TN, TM * TN * 4, EPI, DB, S3 ? 1 : 0>(a, acc, (float*)smem + wave * 1024, m0 + wm0, n0 + wn0, lane, rpre, Rall + wave * TN * 512);
     else if constexpr (EPI != 0) {
@@ -1174,6 +1176,23 @@ int launch_conv_dma2_split3(int shape, ConvArgs a, void* ws, size_t ws_bytes, bo
                             : (a.padv ? dma2_kernel<T, true, 0, false, false, false, false, true> : dma2_kernel<T, false, 0, false, false, false, false, true>);
         return launch_with_lds(kern, sk_grid ? sk_grid : tile_grid<T>(a), T::NW * 64, tile_lds_s3<T>(), st, a,
                                sk_grid ? "conv_dma2/split3/splitk" : "conv_dma2/split3");
+    });
+}
+
+// ... with the statistics epilogue (EPI 1; pemp_split3_conv2d_stats_nhwc_f32): the K loop and the MFMA order of the plain form, so
+// z is bit-identical to launch_conv_dma2_split3 of the same shape; the partial rows are conv_stats_store's.  Unsplit, zero
+// padding, no affine / residual -- the frozen trunks of the head trainers.  FamSplit3Stats (conv_tiles.h) lists the shapes.
+bool conv_dma2_split3_stats_shape(int shape) { return in_family<FamSplit3Stats>(shape); }
+
+int launch_conv_dma2_split3_stats(int shape, const ConvArgs& a, hipStream_t st) {
+    if (!a.stats || a.bz || a.padv || a.res || a.rowmask || a.scale || a.shift || a.flags) {
+        set_error("conv split3 statistics: plain conv with a partials buffer only");
+        return -1;
+    }
+    return with_tile<FamSplit3Stats>(shape, [&](auto t) {
+        using T = decltype(t);
+        return launch_with_lds(dma2_kernel<T, false, 1, false, false, false, false, true>, tile_grid<T>(a), T::NW * 64, tile_lds_s3<T>(), st, a,
+                               "conv_dma2/split3/stats");
     });
 }
 

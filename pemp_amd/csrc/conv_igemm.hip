@@ -605,6 +605,44 @@ extern "C" int pemp_conv2d_stats_nhwc_f32(const pemp_conv_desc* d, const float* 
     return conv_stats_common("conv2d_stats", d, a, ws, ws_bytes, (hipStream_t)stream);
 }
 
+// ---- the statistics epilogue on the split3 family (conv_dma2.hip: launch_conv_dma2_split3_stats).  Entry points of their own:
+// pemp_conv2d_stats_nhwc_f32 / pemp_conv2d_stats_rows keep answering for the fp32 chain only.
+// the id of such a launch (0 runs as 43) -> its shape; 0 for an id the form does not take (persistent, panel, pre-split, split-K
+// ids; another family's; a shape whose statistics form is not offered)
+static int stats_split3_shape(const pemp_conv_desc* d) {
+    const int id = d->tile == 0 ? 43 : d->tile;
+    const TileId t = decode_tile(id);
+    if (id < 41 || id > 46 || t.family != TILE_SPLIT3 || !t.exists || t.persistent || t.splitk || t.panel || t.presplit) return 0;
+    return conv_dma2_split3_stats_shape(t.shape) ? t.shape : 0;
+}
+
+extern "C" int pemp_conv2d_stats_split3_rows(const pemp_conv_desc* d) {
+    if (!d || d->N <= 0 || d->Ho <= 0 || d->Wo <= 0) return 0;
+    const int shape = stats_split3_shape(d);
+    return shape ? cdiv(d->N * d->Ho * d->Wo, kTileShapes[shape].bm) : 0;
+}
+
+extern "C" int pemp_split3_conv2d_stats_nhwc_f32(const pemp_conv_desc* d, const float* x, const void* w3, float* y, float* stats, void* stream) {
+    PEMP_REQUIRE(d && x && w3 && y && stats, "conv2d_stats_split3: null pointer");
+    PEMP_REQUIRE((((uintptr_t)x | (uintptr_t)w3 | (uintptr_t)y | (uintptr_t)stats) & 15) == 0, "conv2d_stats_split3: pointers must be 16-byte aligned");
+    const int shape = stats_split3_shape(d);
+    PEMP_REQUIRE(shape, "conv2d_stats_split3: tile %d has no split3 statistics form (0 or an unsplit id of 41..46 that pemp_conv2d_stats_split3_rows answers for)", d->tile);
+    PEMP_REQUIRE(d->flags == 0, "conv2d_stats_split3: plain conv only (no flags: stem / ReLU / per-image shift / pre-split operands)");
+    PEMP_REQUIRE(d->Cout > 0 && d->Cout >= kTileShapes[shape].bn, "conv2d_stats_split3: Cout=%d below the tile's %d columns", d->Cout, kTileShapes[shape].bn);
+    ConvArgs a;
+    a.x = x; a.w = (const float*)w3; a.y = y; a.res = nullptr; a.stats = stats;
+    a.bmask = nullptr; a.bz = nullptr; a.bmean = nullptr; a.binvstd = nullptr; a.ldbz = 0;
+    pemp_conv_desc f = *d;
+    f.tile = 20 + shape;                 // conv_stats_fill's rules are those of the fp32-chain id of the same shape
+    const int rc = conv_stats_fill("conv2d_stats_split3", &f, a);
+    if (rc) return rc;
+    if ((long long)a.Cout * a.Kpad * 6 >= (1ll << 31)) {     // (conv_dma2_supported counts 4 bytes per weight)
+        set_error("conv2d_stats_split3: split3 weights of 2 GiB or more");
+        return -2;
+    }
+    return launch_conv_dma2_split3_stats(shape, a, (hipStream_t)stream);
+}
+
 extern "C" int pemp_conv2d_bnbwd_nhwc_f32(const pemp_conv_desc* d, const float* x, const float* w, float* y, const float* residual,
                                           const uint32_t* mask, const float* z, int ldz, const float* mean, const float* invstd,
                                           float* stats, void* ws, size_t ws_bytes, void* stream) {

@@ -43,6 +43,7 @@ struct FamFp32 { static constexpr unsigned shapes = shape_bits({1, 2, 3, 4, 5, 6
 struct FamGroup { static constexpr unsigned shapes = shape_bits({1, 2, 3, 4, 5, 6, 7, 8}); static constexpr bool s3 = false; };
 struct FamSplitK { static constexpr unsigned shapes = shape_bits({1, 2, 4, 5, 6, 7}); static constexpr bool s3 = false; };
 struct FamSplit3 { static constexpr unsigned shapes = shape_bits({1, 2, 3, 4, 6}); static constexpr bool s3 = true; };
+struct FamSplit3Stats { static constexpr unsigned shapes = shape_bits({1, 2, 3, 4, 6}); static constexpr bool s3 = true; };   // statistics epilogue
 struct FamPersist { static constexpr unsigned shapes = shape_bits({3, 6}); static constexpr bool s3 = true; };
 struct FamPanel { static constexpr unsigned shapes = shape_bits({1, 2}); static constexpr bool s3 = true; };     // conv_panel.hip: 128 rows x all of Cout, BN columns at a time
 

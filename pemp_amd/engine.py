@@ -23,6 +23,13 @@ BN_EPS = 1e-5
 SPLIT3 = os.environ.get("PEMP_SPLIT3", "1") != "0"
 
 
+def split3_admits(cp):
+    """``with_split3``'s geometry rule for ConvParams.w3: an fp32 non-stem layer of <= 32 taps with Cin % 32 == 0, Cout % 64 == 0
+    and an unpadded K."""
+    return (cp.w.dtype == torch.float32 and not cp.stem and cp.kh * cp.kw <= 32 and cp.cin % 32 == 0 and cp.cout % 64 == 0
+            and cp.kpad == cp.kh * cp.kw * cp.cin)
+
+
 def with_split3(cp):
     """Attach the split form of the weights when SPLIT3 is on: as ConvParams.w3 to an fp32 layer whose geometry the split3 kernels
     take (<= 32 taps, Cin % 32, Cout % 64), and as ConvParams.w3pool to the 7x7 / stride 2 / pad 3 NHWC4 stem, which then runs
@@ -33,7 +40,7 @@ def with_split3(cp):
     if cp.stem:
         if (cp.kh, cp.kw, cp.stride, cp.pad, cp.dil) == (7, 7, 2, 3, 1) and cp.kpad == 224 and cp.cout % 64 == 0:
             cp.w3pool = ops.pack_split3(cp.w)
-    elif cp.kh * cp.kw <= 32 and cp.cin % 32 == 0 and cp.cout % 64 == 0 and cp.kpad == cp.kh * cp.kw * cp.cin:
+    elif split3_admits(cp):
         cp.w3 = ops.pack_split3(cp.w)
     return cp
 

@@ -47,6 +47,7 @@ def ex_config():
     exp_id = -1                 # experiment id to load checkpoint
     loss = "ce"                 # str, loss type [ce/cedt]
     sigma = 5.                  # float, sigma of the DT loss
+    trunk_precision = "f32_chain"   # str, frozen-trunk convs of train_head [f32_chain/split3]; test / train ignore it
 
 
 def close_groups(keys, batch):
@@ -322,8 +323,8 @@ def head_train_batches(trainer, dcfg, shot, split, rank, steps_per_epoch, device
 
 
 @ex.command
-def train_head(_config, split, shot, query, seed, loss, sigma, exp_id, ckpt):
-    """``python -m pemp_amd.entry.canet train_head with split=0 [shot=5]``: CANet's training procedure (entry/canet.py:106-175)
+def train_head(_config, split, shot, query, seed, loss, sigma, exp_id, ckpt, trunk_precision):
+    """``python -m pemp_amd.entry.canet train_head with split=0 [shot=5] [trunk_precision=split3]``: CANet's training procedure (entry/canet.py:106-175)
     for the reference's frozen trunk -- the head trains on the HIP path, per-epoch evaluation with the history loop,
     ``ckpt.pth`` / ``bestckpt.pth`` (reference-loadable state_dicts) under ``<g.model_dir>/<tag>/<id>``."""
     from .pemp_stage1 import run_training
@@ -337,7 +338,7 @@ def train_head(_config, split, shot, query, seed, loss, sigma, exp_id, ckpt):
         from ..core.snapshots import load_for_eval
         model = ModelClass(logger)
         load_for_eval(model, _config, exp_id, ckpt, logger, wgen_seed=WGEN_SEED)     # the frozen trunk comes from a checkpoint
-        return HeadTrainer(model, lr=_config["tr"]["lr"], device=dev, loss=loss, sigma=sigma)
+        return HeadTrainer(model, lr=_config["tr"]["lr"], device=dev, loss=loss, sigma=sigma, trunk_precision=trunk_precision)
 
     return run_training(_config, NAME, make_trainer, lambda tr, dev: Evaluator(tr.model, device=dev), split, shot, seed, exp_id,
                         val_episodes=eval_episodes, batches=head_train_batches)

@@ -38,6 +38,7 @@ def ex_config():
     loss = "ce"                 # str, loss type [ce/cedt]
     sigma = 5.                  # float, sigma of the DT loss
     loss_coef = 1.              # float, coefficient of the auxiliary loss
+    trunk_precision = "f32_chain"   # str, frozen-trunk convs of train_head [f32_chain/split3]; test / train ignore it
     p = {"cls": -1, "sup": "", "qry": ""}
 
 
@@ -120,8 +121,8 @@ class HeadTrainer(RPMMsTrainer):
 
 
 @ex.command
-def train_head(_config, split, shot, query, seed, loss, sigma, exp_id, ckpt):
-    """``python -m pemp_amd.entry.rpmms train_head with split=0 ckpt=<checkpoint | wgen>``: RPMMs' training procedure
+def train_head(_config, split, shot, query, seed, loss, sigma, exp_id, ckpt, trunk_precision):
+    """``python -m pemp_amd.entry.rpmms train_head with split=0 ckpt=<checkpoint | wgen> [trunk_precision=split3]``: RPMMs' training procedure
     (entry/rpmms.py:107-149) for a FROZEN trunk -- the head trains on the HIP path (the reference also updates the trunk's convs:
     not built), per-epoch evaluation, ``ckpt.pth`` / ``bestckpt.pth`` (reference-loadable state_dicts) under
     ``<g.model_dir>/<tag>/<id>``."""
@@ -135,7 +136,8 @@ def train_head(_config, split, shot, query, seed, loss, sigma, exp_id, ckpt):
         from ..core.snapshots import load_for_eval
         model = ModelClass(logger)
         load_for_eval(model, _config, exp_id, ckpt, logger, wgen_seed=WGEN_SEED)     # the frozen trunk comes from a checkpoint
-        return HeadTrainer(model.freeze_trunk(), logger=logger, lr=_config["tr"]["lr"], device=dev, loss=loss, sigma=sigma)
+        return HeadTrainer(model.freeze_trunk(), logger=logger, lr=_config["tr"]["lr"], device=dev, loss=loss, sigma=sigma,
+                           trunk_precision=trunk_precision)
 
     return run_training(_config, NAME, make_trainer, lambda tr, dev: Evaluator(tr.model, device=dev), split, shot, seed, exp_id,
                         batches=head_train_batches)

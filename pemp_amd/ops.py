@@ -7,6 +7,7 @@ as a view (its pixel stride ``ld`` is taken from ``stride(2)``).
 """
 import ctypes as C
 import collections
+import functools
 import json
 import os
 
@@ -57,7 +58,8 @@ class ConvParams:
     __slots__ = ("w", "scale", "shift", "cin", "cout", "kh", "kw", "stride", "pad", "dil", "kpad", "stem", "relu", "w3", "w3pool")
 
     def __init__(self, w, scale, shift, cin, cout, kh, kw, stride, pad, dil, kpad, stem, relu, w3=None, w3pool=None):
-        # w3: the split form of w (pack_split3) -- when present, conv2d / conv2d_group run the split3 family (tile ids 41..56)
+        # w3: the split form of w (pack_split3) -- when present, conv2d / conv2d_group run the split3 family (tile ids 41..56) and
+        # conv2d_stats its statistics form (SPLIT3_STATS_TILES)
         # w3pool: the split form of a 7x7 / 2 / 3 NHWC4 stem's w, for the fused stem + max-pool launch (stem_pool); conv2d never
         # reads it: a stem on its own stays on the fp32 chain, w3 stays None
         self.w, self.scale, self.shift, self.w3, self.w3pool = w, scale, shift, w3, w3pool
@@ -734,10 +736,53 @@ def _stats_launch(lib, fn, what, desc, x, *operands):
     return launch
 
 
+#: the split3 ids that have a statistics epilogue (pemp_split3_conv2d_stats_nhwc_f32): the unsplit ids on their own wave grids.
+#: No persistent, panel, pre-split or split-K form; the library's rows query is the authority (``split3_stats_tiles``).
+SPLIT3_STATS_TILES = (43, 42, 41, 44, 46)
+
+
+@functools.lru_cache(maxsize=None)
+def _split3_stats_offered():
+    lib = _lib.load()
+    d = lambda t: ConvDesc(1, 8, 8, 32, 32, 8, 8, 256, 256, 1, 1, 1, 0, 1, 0, 32, 0, t)
+    return tuple(t for t in SPLIT3_STATS_TILES if lib.pemp_conv2d_stats_split3_rows(C.byref(d(t))) > 0)
+
+
+def split3_stats_tiles(cout):
+    """The ids of SPLIT3_STATS_TILES the library offers (pemp_conv2d_stats_split3_rows answers for them) whose BN divides ``cout``."""
+    return _fits(_split3_stats_offered(), cout)
+
+
+def _conv2d_stats_split3(x, p, out, tile):
+    """conv2d_stats for a layer that carries split weights (ConvParams.w3): pemp_split3_conv2d_stats_nhwc_f32."""
+    lib = _lib.load()
+    _chk_dev(x, p.w3, out)
+    n, h, w, cin, ldx, ho, wo, out, ldy, _ = _conv_geom("conv2d_stats", x, p, out, None)
+    m = n * ho * wo
+    part = torch.empty(((m + 63) // 64, 2, p.cout), dtype=torch.float32, device=x.device)     # the smallest row tile has 64 rows
+    desc = lambda t: ConvDesc(n, h, w, cin, ldx, ho, wo, p.cout, ldy, p.kh, p.kw, p.stride, p.pad, p.dil, 0, p.kpad, 0, t)
+
+    def launch(t):
+        _lib.check(lib.pemp_split3_conv2d_stats_nhwc_f32(C.byref(desc(t)), _p(x), _p(p.w3), _p(out), _p(part), _stream()),
+                   "pemp_split3_conv2d_stats_nhwc_f32")
+
+    if tile == 0:
+        # a key of its own: 2 = the stats epilogue, the trailing 3 = on the split3 family -- never the key of an fp32 statistics
+        # pick (no trailing 3) nor of a plain split3 pick (0 / 4 / 6 / 7 where this one has 2)
+        key = (p.cin, p.cout, p.kh, p.kw, p.stride, p.pad, p.dil, 2, n, h, w, 0, 0, 3)
+        tile = _choose_tile(key, m, launch, lambda: split3_stats_tiles(p.cout), SPLIT3_DEFAULT_TILE)
+    launch(tile)
+    return out, part[:int(lib.pemp_conv2d_stats_split3_rows(C.byref(desc(tile))))]
+
+
 def conv2d_stats(x, p, out=None, tile=0):
     """z = conv(x, w) with the per-32-row partial sums of z and z^2 left by the epilogue (pemp_conv2d_stats_nhwc_f32):
     -> (z, partials [row tiles of the chosen variant, 2, Cout]).  Raises PempHipError where the buffer-addressed kernels do not apply
-    (callers then use conv2d + bn_stats); ``stats_supported`` says so beforehand."""
+    (callers then use conv2d + bn_stats); ``stats_supported`` says so beforehand.
+    A layer with split weights (``p.w3``) runs the split3 form (pemp_split3_conv2d_stats_nhwc_f32; ids of SPLIT3_STATS_TILES): z is
+    then bit-identical to ``conv2d(x, p, tile=id)`` of the same id, not to the fp32 chain."""
+    if p.w3 is not None and not p.stem and p.scale is None:
+        return _conv2d_stats_split3(x, p, out, tile)
     lib = _lib.load()
     _chk_dev(x, p.w, out)
     n, h, w, cin, ldx, ho, wo, out, ldy, _ = _conv_geom("conv2d_stats", x, p, out, None)
@@ -793,8 +838,11 @@ def dma2_supported(x, p):
 
 
 def stats_supported(x, p):
-    """Whether conv2d_stats applies to this (input, layer)."""
-    return p.scale is None and dma2_supported(x, p)
+    """Whether conv2d_stats applies to this (input, layer) -- for a layer with split weights (``p.w3``): whether its split3 form
+    does (the split weights below 2 GiB as well, and an id offered for the layer's Cout)."""
+    if p.scale is not None or not dma2_supported(x, p):
+        return False
+    return p.w3 is None or (p.w3.numel() * 2 < 2 ** 31 and bool(split3_stats_tiles(p.cout)))
 
 
 def fold_input_affine(p, s, t):

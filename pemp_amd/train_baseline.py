@@ -81,7 +81,8 @@ class BaselineTrainer(Stage1Trainer):
     map_full_res = True
 
     def __init__(self, model, lr=1e-3, momentum=0.9, weight_decay=5e-4, device=None, loss="ce", sigma=5.0,
-                 use_graph=False):
+                 use_graph=False, trunk_precision=None):
+        self._no_trunk_precision(trunk_precision)
         from .networks.baseline import net_ingredient
         self._setup(model, device, lr, momentum, weight_decay, 0.0, loss, sigma, use_graph, net_ingredient.cfg["dist_scalar"])
         eng_cls = _VGGEngine if model.backbone_name == "vgg16" else _ResNetProjectionEngine

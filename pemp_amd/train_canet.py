@@ -31,7 +31,7 @@ import torch
 
 from . import canet_engine, ops, train_ops as T
 from .ops import ConvParams
-from .train_engine import HeadTrainEngine, Stage1Trainer, _BN, _Cls2, _Conv, _FrozenConv, _SliceWgrad, _enqueue_wgrad, conv2d
+from .train_engine import HeadTrainEngine, Stage1Trainer, _BN, _Cls2, _Conv, _SliceWgrad, _enqueue_wgrad, check_trunk_precision, conv2d
 from .train_stage2 import _ASPPNoBN
 
 MID = canet_engine.MID
@@ -47,11 +47,12 @@ class CANetHeadTrainEngine(_ASPPNoBN, HeadTrainEngine):
     """Train-mode forward of the frozen trunk, forward + backward of CANet's head; the ASPP is stage 2's."""
     aspp_drop_names = tuple(f"aspp_{i}.2" for i in range(5))
 
-    def __init__(self, model, device):
+    def __init__(self, model, device, trunk_precision="f32_chain"):
         if not model.freeze_backbone:
             raise ValueError(_FROZEN_TRUNK)
+        check_trunk_precision(trunk_precision)
         model.maybe_fix_params()
-        super().__init__(model, device, [model.encoder])
+        super().__init__(model, device, [model.encoder], trunk_precision)
         self.drop_rate2 = float(model.layer5[2].p)
         self.use_history = bool(model.use_history)
         self.w_hist = torch.zeros((MID, 9, HIST_FWD), dtype=torch.float32, device=device) if self.use_history else None
@@ -59,7 +60,7 @@ class CANetHeadTrainEngine(_ASPPNoBN, HeadTrainEngine):
 
     def _init_handles(self, model):
         f, bb = self.flat, model.encoder
-        self.stem = (_FrozenConv(f, bb.conv1, stem=True), _BN(bb.bn1))
+        self.stem = (self._frozen_conv(bb.conv1, stem=True), _BN(bb.bn1))
         self.blocks = self._frozen([*bb.layer1, *bb.layer2, *bb.layer3])
         self.f2_block = len(bb.layer1) + len(bb.layer2) - 1               # layer2's last block: the first half of cat((f2, f3))
         self.l5, self.l55 = _Conv(f, model.layer5[0]), _Conv(f, model.layer55[0])
@@ -182,12 +183,14 @@ class CANetTrainer(Stage1Trainer):
     backward through the head, SGD step without gradient clipping -> (loss, softmax of the low-resolution logits).  Eager only;
     ``query = 1``, any ``shot``."""
 
-    def __init__(self, model, lr=1e-3, momentum=0.9, weight_decay=5e-4, device=None, loss="ce", sigma=5.0, use_graph=False):
+    def __init__(self, model, lr=1e-3, momentum=0.9, weight_decay=5e-4, device=None, loss="ce", sigma=5.0, use_graph=False,
+                 trunk_precision="f32_chain"):
         self._eager_only(use_graph, "CANet")
+        check_trunk_precision(trunk_precision)
         if not model.freeze_backbone:
             raise ValueError(_FROZEN_TRUNK)
         self._setup(model, device, lr, momentum, weight_decay, 0.0, loss, sigma, False)
-        self.eng = CANetHeadTrainEngine(model, self.device)
+        self.eng = CANetHeadTrainEngine(model, self.device, trunk_precision)
 
     def forward_backward(self, sup_img, sup_mask, qry_img, qry_msk, history_mask=None, table=None, read_slot=None):
         """Fills the flat gradient buffer -> (loss, low-resolution logits [B,2,h,w]).  The history: ``history_mask`` [B,1,2,h,w]

@@ -26,7 +26,8 @@ import torch.distributed as dist
 import torch.nn as nn
 
 from . import ops, train_ops as T
-from .engine import logits_nchw
+from . import engine as _engine
+from .engine import logits_nchw, split3_admits
 from .ops import ConvParams
 
 
@@ -384,16 +385,22 @@ class _BN:
 
 
 class _FrozenConv(_Conv):
-    """A conv of a frozen trunk: its forward parameters are packed once."""
+    """A conv of a frozen trunk: its forward parameters are packed once.  ``split3``: the split form of the weights is attached
+    as well (ConvParams.w3, once) where ``engine.split3_admits`` the layer -- the conv then runs on the split3 family, with the
+    statistics epilogue where ``ops.stats_supported``; the NHWC4 stem and every layer the rule excludes stay on the fp32 chain."""
 
-    def __init__(self, flat, conv, stem=False):
+    def __init__(self, flat, conv, stem=False, split3=False):
         super().__init__(flat, conv, stem)
-        self._packed = {}
+        self._packed, self.split3 = {}, split3
 
     def fwd_params(self, relu=False, with_bias=True):
         key = (relu, with_bias)
         if key not in self._packed:
-            self._packed[key] = super().fwd_params(relu, with_bias)
+            cp = super().fwd_params(relu, with_bias)
+            if self.split3 and split3_admits(cp):
+                w3 = next((q.w3 for q in self._packed.values() if q.w3 is not None), None)
+                cp.w3 = ops.pack_split3(cp.w) if w3 is None else w3
+            self._packed[key] = cp
         return self._packed[key]
 
 
@@ -511,20 +518,42 @@ class TrainEngine:
         out, rec["r3"] = self._cbn_fwd(y2, b["c3"], b["b3"], True, residual=res)
         return out, rec
 
+TRUNK_PRECISIONS = ("f32_chain", "split3")
+
+
+def check_trunk_precision(value):
+    """ValueError for a ``trunk_precision`` no head trainer takes, and for "split3" while the split3 family is switched off
+    (PEMP_SPLIT3=0)."""
+    if value not in TRUNK_PRECISIONS:
+        raise ValueError(f"trunk_precision must be one of {TRUNK_PRECISIONS}, got {value!r}")
+    if value == "split3" and not _engine.SPLIT3:
+        raise ValueError('trunk_precision="split3" needs the split3 family, which PEMP_SPLIT3=0 switches off')
+
+
 class HeadTrainEngine(TrainEngine):
     """A head trained behind a frozen trunk (``requires_grad`` cleared before construction).  The trunk modules ``trunk`` run
     forward only, in train mode -- batch-statistics BatchNorm, weights packed once, nothing kept for a backward; the head's
-    gradients are one all-reduce bucket.  ``_init_handles(model)`` builds the subclass's layer handles."""
+    gradients are one all-reduce bucket.  ``_init_handles(model)`` builds the subclass's layer handles.
+    ``trunk_precision``: "f32_chain" (the default) -- the trunk's convs on the fp32-chain kernels, like every training conv; or
+    "split3" -- the frozen convs that ``engine.split3_admits`` run on the split3 family with the statistics epilogue
+    (ops.conv2d_stats with ConvParams.w3; weights split once).  The head's own convs, every backward kernel and every weight
+    gradient stay on the fp32 chain either way."""
 
-    def __init__(self, model, device, trunk):
+    def __init__(self, model, device, trunk, trunk_precision="f32_chain"):
+        check_trunk_precision(trunk_precision)
+        self.trunk_precision = trunk_precision
         super().__init__(model, device)
         self.bn_counters = [m.num_batches_tracked for t in trunk for m in t.modules() if isinstance(m, nn.BatchNorm2d)]
         self._init_handles(model)
         self.flat.build_dgrad_mirror()
         self.buckets = GradBuckets(self.flat.grad, [], side_stream=self.flat.side_stream)
 
+    def _frozen_conv(self, conv, stem=False):
+        """The handle of one frozen trunk conv, on the engine's trunk precision."""
+        return _FrozenConv(self.flat, conv, stem, split3=self.trunk_precision == "split3")
+
     def _frozen(self, blocks):
-        return [block_handles(self.flat, blk, _FrozenConv) for blk in blocks]
+        return [block_handles(self.flat, blk, lambda flat, conv: self._frozen_conv(conv)) for blk in blocks]
 
     def _frozen_blocks(self, x, blocks, tap=None):
         """``x`` through the frozen ``blocks`` -> (output, output of block ``tap``)."""
@@ -868,7 +897,8 @@ class Stage1Trainer:
     clip_grad_norm_(1.1), SGD step; returns the loss tensor (entry/pemp_stage1.py:57-65)."""
 
     def __init__(self, model, lr=1e-3, momentum=0.9, weight_decay=5e-4, max_norm=1.1, device=None,
-                 drop_rate=None, block_size=None, loss="ce", sigma=5.0, use_graph=False):
+                 drop_rate=None, block_size=None, loss="ce", sigma=5.0, use_graph=False, trunk_precision=None):
+        self._no_trunk_precision(trunk_precision)
         from .networks.pemp_stage1 import net_ingredient
         cfg = net_ingredient.cfg
         self._setup(model, device, lr, momentum, weight_decay, max_norm, loss, sigma, use_graph, cfg["dist_scalar"])
@@ -894,6 +924,13 @@ class Stage1Trainer:
         self.optimizer = None                     # optional torch optimizer acting as hyper-parameter / scheduler holder
         self.use_graph, self._graphs = use_graph, {}
         self.loss_obj = losses.get({"loss": loss, "sigma": sigma})
+
+    def _no_trunk_precision(self, trunk_precision):
+        """``trunk_precision`` belongs to the head trainers (a frozen trunk, weights split once); a trainer whose trunk weights
+        change every step has no such switch."""
+        if trunk_precision is not None:
+            raise ValueError(f"{type(self).__name__} trains its trunk: trunk_precision is a switch of the head trainers "
+                             "(CANetTrainer, PFENetTrainer, RPMMsTrainer)")
 
     def _eager_only(self, use_graph, what):
         if use_graph:

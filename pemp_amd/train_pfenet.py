@@ -38,7 +38,7 @@ import torch
 from . import ops, train_ops as T
 from .ops import ConvParams
 from .pfenet_engine import MERGE_CIN, PYRAMID_BINS, REDUCE
-from .train_engine import HeadTrainEngine, Stage1Trainer, _BN, _Cls2, _Conv, _FrozenConv, _SliceWgrad, _enqueue_wgrad, conv2d
+from .train_engine import HeadTrainEngine, Stage1Trainer, _BN, _Cls2, _Conv, _SliceWgrad, _enqueue_wgrad, check_trunk_precision, conv2d
 
 MERGE_WGRAD = 320                       # what the weight-gradient kernel of init_merge reads (Cin % 64); channels 257.. are zero
 TRUNK = ("layer0", "layer1", "layer2", "layer3", "layer4")
@@ -47,19 +47,20 @@ TRUNK = ("layer0", "layer1", "layer2", "layer3", "layer4")
 class PFENetHeadTrainEngine(HeadTrainEngine):
     """S + 1 train-mode forward passes of the frozen deep-base trunk, forward + backward of PFENet's head."""
 
-    def __init__(self, model, device):
+    def __init__(self, model, device, trunk_precision="f32_chain"):
+        check_trunk_precision(trunk_precision)
         for name in TRUNK:
             for p in getattr(model, name).parameters():
                 p.requires_grad = False                                   # the reference's optimizer skips them: their .grad is None
-        super().__init__(model, device, [getattr(model, name) for name in TRUNK])
+        super().__init__(model, device, [getattr(model, name) for name in TRUNK], trunk_precision)
         self.drop_scale, self.skip_aux = 1.0, False
         self.w_merge = [torch.zeros((REDUCE, MERGE_CIN), dtype=torch.float32, device=device) for _ in self.merge]
         self.merge_in = {}
 
     def _init_handles(self, model):
         f, l0, device = self.flat, model.layer0, self.device
-        self.stem = [(_FrozenConv(f, l0[0], stem=True), _BN(l0[1])), (_FrozenConv(f, l0[3]), _BN(l0[4])),
-                     (_FrozenConv(f, l0[6]), _BN(l0[7]))]
+        self.stem = [(self._frozen_conv(l0[0], stem=True), _BN(l0[1])), (self._frozen_conv(l0[3]), _BN(l0[4])),
+                     (self._frozen_conv(l0[6]), _BN(l0[7]))]
         self.blocks = self._frozen([*model.layer1, *model.layer2, *model.layer3])
         self.blocks4 = self._frozen(model.layer4)
         self.f2_block = len(model.layer1) + len(model.layer2) - 1         # layer2's last block: channels 1024.. of cat(layer3, layer2)
@@ -243,10 +244,11 @@ class PFENetTrainer(Stage1Trainer):
     ``shot``.  ``loss = cedt`` weights the main loss only: the auxiliary loss is the model's own plain CE (pfenet.py:59,282)."""
 
     def __init__(self, model, lr=1e-3, momentum=0.9, weight_decay=5e-4, device=None, loss="ce", sigma=5.0, loss_coef=1.0,
-                 use_graph=False):
+                 use_graph=False, trunk_precision="f32_chain"):
         self._eager_only(use_graph, "PFENet")
+        check_trunk_precision(trunk_precision)
         self._setup(model, device, lr, momentum, weight_decay, 0.0, loss, sigma, False)
-        self.eng = PFENetHeadTrainEngine(model, self.device)
+        self.eng = PFENetHeadTrainEngine(model, self.device, trunk_precision)
         self.loss_coef = float(loss_coef)
 
     def losses_backward(self, pred, inner, tgt):

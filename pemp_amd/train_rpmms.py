@@ -32,7 +32,7 @@ from .canet_engine import MID
 from .ops import ConvParams
 from .rpmms_engine import PASSES
 from .train_canet import HIST_FWD, HIST_WGRAD
-from .train_engine import HeadTrainEngine, Stage1Trainer, _BN, _Cls2, _Conv, _FrozenConv, _SliceWgrad, _enqueue_wgrad, conv2d
+from .train_engine import HeadTrainEngine, Stage1Trainer, _BN, _Cls2, _Conv, _SliceWgrad, _enqueue_wgrad, check_trunk_precision, conv2d
 from .train_stage2 import _ASPPNoBN
 
 _FROZEN_TRUNK = ("RPMMs trunk training is not built: the HIP path trains the head behind a frozen trunk -- call "
@@ -48,9 +48,9 @@ class RPMMsHeadTrainEngine(_ASPPNoBN, HeadTrainEngine):
     """Train-mode forward of the frozen trunk (two batches), forward + backward of RPMMs' head; the ASPP is stage 2's."""
     aspp_drop_names = tuple(f"layer6.aspp_{i}.2" for i in range(5))
 
-    def __init__(self, model, device):
+    def __init__(self, model, device, trunk_precision="f32_chain"):
         _check_frozen(model)
-        super().__init__(model, device, [model.model_res])
+        super().__init__(model, device, [model.model_res], trunk_precision)
         self.drop_rate2 = float(model.layer55[2].p)
         z = lambda *s: torch.zeros(s, dtype=torch.float32, device=device)
         self.w_hist, self.w_56 = z(MID, 9, HIST_FWD), z(MID, 9, HIST_FWD)      # 258 live input channels of 288, re-packed per step
@@ -63,7 +63,7 @@ class RPMMsHeadTrainEngine(_ASPPNoBN, HeadTrainEngine):
 
     def _init_handles(self, model):
         f, bb = self.flat, model.model_res
-        self.stem = (_FrozenConv(f, bb.conv1, stem=True), _BN(bb.bn1))
+        self.stem = (self._frozen_conv(bb.conv1, stem=True), _BN(bb.bn1))
         self.blocks = self._frozen([*bb.layer1, *bb.layer2, *bb.layer3])
         self.f2_block = len(bb.layer1) + len(bb.layer2) - 1               # layer2's last block: the first half of cat((f2, f3))
         self.l5, self.bn5 = _Conv(f, model.layer5[0]), _BN(model.layer5[1])
@@ -281,11 +281,13 @@ class RPMMsTrainer(Stage1Trainer):
     the sum of the three passes' cross-entropies on the bilinearly up-sampled logits, backward through the head, SGD step
     without gradient clipping -> (loss, CE of out2, CE of out1).  Eager only; 1-shot, one query (``model.check_inputs``)."""
 
-    def __init__(self, model, lr=1e-3, momentum=0.9, weight_decay=5e-4, device=None, loss="ce", sigma=5.0, use_graph=False):
+    def __init__(self, model, lr=1e-3, momentum=0.9, weight_decay=5e-4, device=None, loss="ce", sigma=5.0, use_graph=False,
+                 trunk_precision="f32_chain"):
         self._eager_only(use_graph, "RPMMs")
         _check_frozen(model)
+        check_trunk_precision(trunk_precision)
         self._setup(model, device, lr, momentum, weight_decay, 0.0, loss, sigma, False)
-        self.eng = RPMMsHeadTrainEngine(model, self.device)
+        self.eng = RPMMsHeadTrainEngine(model, self.device, trunk_precision)
 
     def forward_backward(self, sup_img, sup_mask, qry_img, qry_msk):
         """Fills the flat gradient buffer -> (loss, (out0, out1, out2)), the three passes' low-resolution logits [B,2,h,w];

@@ -229,7 +229,8 @@ class Stage2Trainer(Stage1Trainer):
     inference path) -> stage-2 forward, CE, backward, SGD (entry/pemp_stage2.py:72-83)."""
 
     def __init__(self, stage1, model, lr=1e-3, momentum=0.9, weight_decay=5e-4, device=None, drop_rate2=None,
-                 loss="ce", sigma=5.0, use_graph=False):
+                 loss="ce", sigma=5.0, use_graph=False, trunk_precision=None):
+        self._no_trunk_precision(trunk_precision)
         from .networks.pemp_stage2 import net_ingredient
         cfg = net_ingredient.cfg
         self._setup(model, device, lr, momentum, weight_decay, 0.0, loss, sigma, use_graph, cfg["dist_scalar"])

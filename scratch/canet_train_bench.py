@@ -2,6 +2,10 @@
 stage-1 headline).
 
 usage: python scratch/canet_train_bench.py [--bs 4] [--shot 1] [--size 401] [--steps 20] [--warmup 5] [--rounds 5]
+       [--trunk-precision f32_chain|split3|both] [--only-step]
+
+``--trunk-precision both``: the two trunk precisions alternated in one process (scratch/trunk_precision_ab.py), nothing else;
+``--only-step``: the ``train_step`` lines only (for a profiler run).
 
 JSON lines:
   * ``train_step``: ms per ``CANetTrainer.train_step`` and training episodes/s (host clock around steps that end in a
@@ -20,6 +24,8 @@ import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
+
+import trunk_precision_ab  # noqa: E402
 
 
 def timed(fn, reps, warm=3):
@@ -43,6 +49,8 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--only-step", action="store_true")
+    trunk_precision_ab.add_argument(ap)
     args = ap.parse_args()
     from pemp_amd import ops, synth, train_ops as T
     from pemp_amd.networks import canet as m
@@ -50,9 +58,13 @@ def main():
     from pemp_amd.train_canet import MID, CANetTrainer
     from pemp_amd.train_engine import _SliceWgrad
     dev = torch.device("cuda:0")
-    net = m.CaNet(None)
-    net.load_state_dict(synth.wgen_state_dict_for(net, m.WGEN_SEED))
-    tr = CANetTrainer(net, lr=1e-4, device=dev)
+    def trainer(precision):
+        net = m.CaNet(None)
+        net.load_state_dict(synth.wgen_state_dict_for(net, m.WGEN_SEED))
+        return CANetTrainer(net, lr=1e-4, device=dev, trunk_precision=precision), net
+
+    both = args.trunk_precision == "both"
+    tr, net = trainer("f32_chain" if both else args.trunk_precision)
     eng, H, B, S = tr.eng, args.size, args.bs, args.shot
     b = synth.make_batch(list(range(2000, 2000 + B)), shot=S, height=H, width=H, out_hw=(H, H))
     sup, msk, qry = (torch.from_numpy(b[k]).to(dev) for k in ("sup_img", "sup_mask", "qry_img"))
@@ -63,6 +75,12 @@ def main():
     def step():
         return tr.train_step(sup, msk, qry, qry_msk=gt, history_mask=hist)
 
+    if both:
+        tr3, _ = trainer("split3")
+        trunk_precision_ab.alternate("canet", {"f32_chain": lambda: step()[0],
+                                               "split3": lambda: tr3.train_step(sup, msk, qry, qry_msk=gt, history_mask=hist)[0]},
+                                     args.steps, args.warmup, args.rounds, B)
+        return
     for _ in range(args.warmup):                                   # picks every conv / wgrad variant, fills the workspaces
         loss, _ = step()
     for rep in range(2):
@@ -75,6 +93,8 @@ def main():
         print(json.dumps({"train_step": rep, "bs": B, "shot": S, "size": H, "feature_hw": h, "ms_per_step": round(1e3 * dt / args.steps, 3),
                           "episodes_per_s": round(B * args.steps / dt, 2), "loss": round(float(loss), 5)}), flush=True)
     step_ms = 1e3 * dt / args.steps
+    if args.only_step:
+        return
 
     # -- phases by device events ------------------------------------------------------------------------------------------
     ev = {k: [torch.cuda.Event(enable_timing=True) for _ in range(args.steps)] for k in ("t0", "trunk", "fwd", "loss", "bwd", "opt")}

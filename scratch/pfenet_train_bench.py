@@ -1,6 +1,10 @@
 """PFENet head-training throughput at 4 x 401 x 401, 1-shot or 5-shot (side benchmark, bench.py measures the stage-1 headline).
 
-usage: python scratch/pfenet_train_bench.py [--bs 4] [--shot 1] [--size 401] [--steps 20] [--warmup 5]
+usage: python scratch/pfenet_train_bench.py [--bs 4] [--shot 1] [--size 401] [--steps 20] [--warmup 5] [--rounds 5]
+       [--trunk-precision f32_chain|split3|both] [--only-step]
+
+``--trunk-precision both``: the two trunk precisions alternated in one process (scratch/trunk_precision_ab.py), nothing else;
+``--only-step``: the ``train_step`` lines only (for a profiler run).
 
 JSON lines:
   * ``train_step``: ms per ``PFENetTrainer.train_step`` and training episodes/s (host clock around steps that end in a
@@ -17,6 +21,8 @@ import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
+
+import trunk_precision_ab  # noqa: E402
 
 
 def timed(fn, reps, warm=3):
@@ -39,6 +45,9 @@ def main():
     ap.add_argument("--size", type=int, default=401)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--only-step", action="store_true")
+    trunk_precision_ab.add_argument(ap)
     args = ap.parse_args()
     from pemp_amd import synth, train_ops as T
     from pemp_amd.networks import pfenet as m
@@ -46,9 +55,13 @@ def main():
     from pemp_amd.train_pfenet import PFENetTrainer
     dev = torch.device("cuda:0")
     H, B, S = args.size, args.bs, args.shot
-    net = m.ModelClass(S, None)
-    net.load_state_dict(synth.wgen_state_dict_for(net, m.WGEN_SEED))
-    tr = PFENetTrainer(net, lr=1e-4, device=dev)
+    def trainer(precision):
+        net = m.ModelClass(S, None)
+        net.load_state_dict(synth.wgen_state_dict_for(net, m.WGEN_SEED))
+        return PFENetTrainer(net, lr=1e-4, device=dev, trunk_precision=precision)
+
+    both = args.trunk_precision == "both"
+    tr = trainer("f32_chain" if both else args.trunk_precision)
     eng = tr.eng
     b = synth.make_batch(list(range(2000, 2000 + B)), shot=S, height=H, width=H, out_hw=(H, H))
     sup, msk, qry = (torch.from_numpy(b[k]).to(dev) for k in ("sup_img", "sup_mask", "qry_img"))
@@ -57,6 +70,12 @@ def main():
     def step():
         return tr.train_step(sup, msk, qry, qry_msk=gt)
 
+    if both:
+        tr3 = trainer("split3")
+        trunk_precision_ab.alternate(f"pfenet_{S}shot", {"f32_chain": lambda: step()[0],
+                                                         "split3": lambda: tr3.train_step(sup, msk, qry, qry_msk=gt)[0]},
+                                     args.steps, args.warmup, args.rounds, B)
+        return
     for _ in range(args.warmup):                                   # picks every conv / wgrad variant, fills the workspaces
         loss, aux = step()
     for rep in range(2):
@@ -70,6 +89,8 @@ def main():
                           "episodes_per_s": round(B * args.steps / dt, 2), "loss": round(float(loss), 5), "aux": round(float(aux), 5)}),
               flush=True)
     step_ms = 1e3 * dt / args.steps
+    if args.only_step:
+        return
 
     # -- phases by device events ------------------------------------------------------------------------------------------
     order = ("t0", "trunk", "fwd", "loss", "bwd", "opt")

@@ -2,6 +2,10 @@
 measures the stage-1 headline).
 
 usage: python scratch/rpmms_train_bench.py [--bs 4] [--size 401] [--steps 20] [--warmup 5] [--only-rpmms]
+       [--rounds 5] [--trunk-precision f32_chain|split3|both]
+
+``--trunk-precision`` is the RPMMs trainer's (the CANet comparison stays on its default); ``both``: the two trunk precisions of the
+RPMMs trainer alternated in one process (scratch/trunk_precision_ab.py), nothing else.
 
 JSON lines:
   * ``train_step``: ms per ``RPMMsTrainer.train_step`` / ``CANetTrainer.train_step`` and training episodes/s (host clock around
@@ -22,6 +26,8 @@ import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
+
+import trunk_precision_ab  # noqa: E402
 
 
 def timed(fn, reps, warm=3):
@@ -44,6 +50,8 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--only-rpmms", action="store_true")
+    ap.add_argument("--rounds", type=int, default=5)
+    trunk_precision_ab.add_argument(ap)
     args = ap.parse_args()
     from pemp_amd import synth, train_ops as T
     from pemp_amd.networks import canet, rpmms
@@ -55,10 +63,20 @@ def main():
     sup, msk, qry = (torch.from_numpy(b[k]).to(dev) for k in ("sup_img", "sup_mask", "qry_img"))
     gt = torch.from_numpy(b["qry_mask"]).reshape(-1, H, H).to(dev)
 
-    rnet = rpmms.RPMMs(None)
-    rnet.load_state_dict(synth.wgen_state_dict_for(rnet, rpmms.WGEN_SEED))
-    rtr = RPMMsTrainer(rnet.freeze_trunk(), lr=1e-4, device=dev)
+    def trainer(precision):
+        net = rpmms.RPMMs(None)
+        net.load_state_dict(synth.wgen_state_dict_for(net, rpmms.WGEN_SEED))
+        return RPMMsTrainer(net.freeze_trunk(), lr=1e-4, device=dev, trunk_precision=precision), net
+
+    both = args.trunk_precision == "both"
+    rtr, rnet = trainer("f32_chain" if both else args.trunk_precision)
     h, w = rnet.feature_hw(H, H)
+    if both:
+        rtr3, _ = trainer("split3")
+        trunk_precision_ab.alternate("rpmms", {"f32_chain": lambda: rtr.train_step(sup, msk, qry, qry_msk=gt)[0],
+                                               "split3": lambda: rtr3.train_step(sup, msk, qry, qry_msk=gt)[0]},
+                                     args.steps, args.warmup, args.rounds, B)
+        return
     steps = {"rpmms": lambda: rtr.train_step(sup, msk, qry, qry_msk=gt)[0]}
     if not args.only_rpmms:
         cnet = canet.CaNet(None)
