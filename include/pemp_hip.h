@@ -73,6 +73,12 @@ int pemp_abi_version(void);
  *         47, 49        persistent forms of 43 and 46: a resident grid walks the tiles
  *     5x  51, 52, 54, 56  split3 with the last round split along K
  *    14x  146, 149        split3 with pre-split ACTIVATIONS (PEMP_CONV_IN_SPLIT3): 46 and 49 without the split in the K loop
+ *    24x  246, 249        the tile and results of 146 / 149 (249: the persistent form) with ONE activation stage per (channel chunk,
+ *                       kh): the three kw taps read it displaced by -d, 0, +d rows, image-row boundaries carry d zero rows
+ *                       (conv_row3.hip: conv_row3_kernel, conv_row3p_kernel).  3x3, stride 1,
+ *                       pad == dil == d, 256 + 2 d + d ceil((255 + 2 d) / W) <= 288; the plain fp32 output (affine, ReLU) only: no
+ *                       PEMP_CONV_OUT_SPLIT3 / _ALSO, residual, padding value, per-image shift, split-K or workspace -- anything
+ *                       else is an error ("unsupported").  Bit-identical to 146 / 149
  *     7x  71, 72          split3, activation-stationary (1x1 convs without padding, Kpad <= 256, pemp_conv2d_nhwc_f32 only): a
  *                       block of 4 waves keeps 128 output rows x K of split activations in registers and walks ALL of Cout, 128
  *                       (71) or 64 (72) columns at a time, with only the packed weights streaming through LDS; no padding value,
@@ -152,7 +158,7 @@ int pemp_conv2d_group_nhwc_f32(int n, const pemp_conv_desc* d, const float* cons
  *   chosen at compile time, with no residual path at all (that is what leaves them registers for the split): 47 and 49 run
  *   conv_dma2_s3po_kernel<64, 64, ...> / <256, 128, ...>, 149 runs conv_dma2_a3po_kernel<256, 128, ...>; a persistent shape without
  *   such a variant would run as the id it walks (none today).  Same tiles, K order and split: the bf16 tensor ids 43 / 46 write.
- *   PEMP_CONV_IN_SPLIT3 (consumer; ids 146 = the form of 46, 149 = the form of 49, and no other id): `x` is such a tensor
+ *   PEMP_CONV_IN_SPLIT3 (consumer; ids 146 = the form of 46, 149 = the form of 49, 246 / 249 = 146 / 149 on row stages, and no other id): `x` is such a tensor
  *   (ldx == Cin, Cin % 32 == 0), a padding value is the [Cin / 32][3][32] bf16 split of the fp32 vector, behind x like the fp32
  *   one.  Multi-tap convs only; no per-image shift, split-K or workspace; Cout % 128 == 0.  Same MFMA order and epilogue as
  *   41..49 on the same pieces: bit-identical to them on the fp32 tensor.  (No 128 x 128 form: its A tile of 96 KiB would leave one

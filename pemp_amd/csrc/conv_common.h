@@ -406,6 +406,10 @@ int launch_conv_dma2_split3_pre(int shape, bool persistent, const ConvArgs& a, h
 // conv_panel.hip: the activation-stationary split3 form of short-K 1x1 convs (shapes 1 and 2 = 128 / 64 columns at a time)
 bool conv_panel_supported(const ConvArgs& a);
 int launch_conv_panel(int shape, const ConvArgs& a, hipStream_t st);
+// conv_row3.hip: 3x3 / stride 1 / pad == dil convs on pre-split activations, one A stage per (chunk, kh) group (tile ids 246 /
+// 249: one tile per block / persistent)
+bool conv_row3_supported(const ConvArgs& a);
+int launch_conv_row3(bool persistent, const ConvArgs& a, hipStream_t st);
 int conv_dma2_simds();                                                     // SIMDs of the current device (4 per CU)
 int pack_split3(const float* w, void* out, int cout, int kpad, hipStream_t st);
 // conv_stem_pool.hip: the 7x7 / 2 / 3 NHWC4 stem (split3 weights) + its 3 / 2 / 1 ceil-mode max-pool in one launch (PEMP_CONV_POOL3S2)

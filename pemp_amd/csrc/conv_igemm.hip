@@ -375,6 +375,12 @@ static int conv2d_impl(const pemp_conv_desc* d, const float* x, const float* w, 
         PEMP_REQUIRE(conv_dma2_supported(a) && (long long)a.Cout * a.Kpad * 6 < (1ll << 31),
                      "conv2d: tile %d needs <= 32 taps and operands < 2 GiB (a padding value behind the activations)", tile);
         PEMP_REQUIRE_COUT("conv2d", t.shape, a.Cout);
+        if (t.row3) {                    // conv_row3.hip: same results as 146 / 149 where it applies, an error elsewhere
+            PEMP_REQUIRE(conv_row3_supported(a),
+                         "conv2d: tile %d unsupported: needs a 3x3 / stride 1 / pad == dil conv, the plain fp32 output without residual / padding value, "
+                         "and a stage of at most 288 rows (256 + 2 d + d ceil((255 + 2 d) / W))", tile);
+            return launch_conv_row3(t.persistent, a, st);
+        }
         return launch_conv_dma2_split3_pre(t.shape, t.persistent, a, st);      // (+ the variants of both ids that store pre-split)
     }
     if (t.family == TILE_SPLIT3) {       // conv_dma2.hip, S3: w from pemp_pack_split3_bf16

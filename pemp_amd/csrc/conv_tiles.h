@@ -72,14 +72,15 @@ struct TileId {
     bool persistent;   // 47, 49
     bool exists;       // some entry point takes the id
     bool panel;        // 71, 72: the activation-stationary 1x1 form (conv_panel.hip)
-    bool presplit;     // 146, 149: the activations come pre-split (PEMP_CONV_IN_SPLIT3); the forms of 46 / 49
+    bool presplit;     // 146, 149, 246, 249: the activations come pre-split (PEMP_CONV_IN_SPLIT3); the forms of 46 / 49
+    bool row3;         // 246, 249: the tile of 146 / 149 with one A stage for the three taps of a kernel row (conv_row3.hip)
 };
 
 inline TileId decode_tile(int id) {
-    TileId t = {TILE_NONE, 0, false, false, false, false, false};
+    TileId t = {TILE_NONE, 0, false, false, false, false, false, false};
     const int decade = id / 10, s = id % 10;
-    if (id == 146 || id == 149) {
-        t.family = TILE_SPLIT3, t.shape = 6, t.exists = t.presplit = true, t.persistent = id == 149;
+    if (id == 146 || id == 149 || id == 246 || id == 249) {
+        t.family = TILE_SPLIT3, t.shape = 6, t.exists = t.presplit = true, t.persistent = id % 10 == 9, t.row3 = id > 200;
         return t;
     }
     if (decade == 7 && in_family<FamPanel>(s)) {

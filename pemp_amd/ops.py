@@ -89,6 +89,9 @@ TILES.update({70 + s: Tile(_SHAPES[s], "split3", False, None) for s in (1, 2)})
 #: split3 with pre-split ACTIVATIONS (csrc/conv_dma2.hip, A3): the forms of 46 / 49 whose input was written split by its producer's
 #: epilogue (conv2d(out_split3=True)), so that their K loop has no splitting left to do
 TILES.update({146: Tile(_SHAPES[6], "split3", False, None), 149: Tile(_SHAPES[6], "split3", False, 146)})
+#: ... and the tiles of 146 / 149 with ONE activation stage for the three taps of a kernel row (csrc/conv_row3.hip): 3x3 / stride 1 /
+#: pad == dil convs whose stage fits 288 rows (``_row3_ok``); 249: the persistent form of 246
+TILES.update({246: Tile(_SHAPES[6], "split3", False, None), 249: Tile(_SHAPES[6], "split3", False, 246)})
 _NO_TILE = Tile(None, None, False, None)        # an id outside the registry: the library refuses it
 
 
@@ -117,6 +120,11 @@ SPLIT3_PANEL = os.environ.get("PEMP_SPLIT3_PANEL", "1") != "0"
 #: hand a tensor over pre-split (the A/B switch)
 SPLIT3_PRESPLIT_TILES = (146, 149)
 SPLIT3_PRESPLIT = os.environ.get("PEMP_SPLIT3_PRESPLIT", "1") != "0"
+#: ... and the row-stage forms of 146 / 149 (bit-identical to them): a registry of its own, offered to timing-based picks only, where
+#: ``_row3_ok`` holds (PEMP_SPLIT3_ROW3=0: never, the A/B switch)
+SPLIT3_ROW3_TILES = (246, 249)
+SPLIT3_ROW3 = os.environ.get("PEMP_SPLIT3_ROW3", "1") != "0"
+ROW3_STAGE_ROWS = 288
 AUTOTUNE = True
 #: test hook: ``PICK_HOOK(kind, cands, key) -> one of cands`` decides every kernel-variant pick INSTEAD of timing (kind "conv":
 #: tile ids, "wgrad": block counts / (tile kind, block count) pairs), at any problem size.  Timing-based picks differ from box
@@ -272,6 +280,19 @@ def _panel_ok(p, n, ho, wo, ldx, ldy, ldr, h, w, pad_value, splitk, per_image_sh
             and n * ho * wo * max(ldy, ldr) * 4 < lim)
 
 
+def row3_stage_rows(w, dil):
+    """Stage rows a 256-row tile of csrc/conv_row3.hip can need on maps of width ``w``: 256 + 2 d pixels and d zero rows per image-row
+    boundary inside them (row3_stage_rows there)."""
+    return 256 + 2 * dil + dil * ((255 + 2 * dil + w - 1) // w)
+
+
+def _row3_ok(p, w, residual, pad_value, out_split3, also_split3, per_image_shift):
+    """Whether the ids of SPLIT3_ROW3_TILES take this call with a pre-split input (conv_row3.hip: conv_row3_supported)."""
+    return (SPLIT3_ROW3 and (p.kh, p.kw, p.stride) == (3, 3, 1) and p.pad == p.dil and residual is None
+            and pad_value is None and not out_split3 and also_split3 is None and not per_image_shift
+            and row3_stage_rows(w, p.dil) <= ROW3_STAGE_ROWS)
+
+
 def pack_split3(w):
     """KRSC [Cout, Kpad] fp32 (Kpad % 32 == 0) -> its split3 form (pemp_pack_split3_bf16): bf16 [Cout, Kpad / 32, 3, 32], per row
     and 32-channel K step the planes h, m, l with w == h + m + l exactly."""
@@ -382,8 +403,8 @@ def conv2d(x, p, out=None, residual=None, shift_override=None, per_image_shift=F
             raise ValueError("conv2d: a pre-split input needs a multi-tap conv with Cin % 32 == 0 and Cout % 128 == 0, no per-image shift")
     if also_split3 is not None and (not x_split3 or out_split3 or residual is not None):
         raise ValueError("conv2d: a second, pre-split output needs a pre-split input (x_split3), no out_split3, no residual")
-    if (tile in SPLIT3_PRESPLIT_TILES) != bool(x_split3) and (tile or not x_split3):
-        raise ValueError(f"conv2d: the tile ids {SPLIT3_PRESPLIT_TILES} and x_split3 come together (tile {tile})")
+    if (tile in SPLIT3_PRESPLIT_TILES + SPLIT3_ROW3_TILES) != bool(x_split3) and (tile or not x_split3):
+        raise ValueError(f"conv2d: the tile ids {SPLIT3_PRESPLIT_TILES + SPLIT3_ROW3_TILES} and x_split3 come together (tile {tile})")
     if x.dtype == torch.bfloat16 and not x_split3:
         return _conv2d_bf16(x, p, out, residual, shift_override, per_image_shift, relu, tile, pad_value)
     n, h, w, cin, ldx, ho, wo, out, ldy, ldr = _conv_geom("conv2d", x, p, out, residual, x_split3=x_split3, out_split3=out_split3)
@@ -466,7 +487,13 @@ def conv2d(x, p, out=None, residual=None, shift_override=None, per_image_shift=F
             # (a pre-split output: 17 where it was 16 -- the persistent ids 47 / 49 / 149 run producer kernels of their own now and are
             # offered; a pick remembered under 16 was made without them and is not replayed.  64: with the second output)
             key += (146,) * int(x_split3) + (17,) * int(out_split3) + (64,) * int(also_split3 is not None)
-            cands = lambda: _fits(list(SPLIT3_PRESPLIT_TILES if x_split3 else SPLIT3_TILES), p.cout)
+            # ... and a call that the row-stage id takes under a key of its own (246): an older pick, made without that candidate, is
+            # never replayed on it.  The id is offered to timing-based picks only (the test hook decides among the other ids)
+            row3 = bool(x_split3) and _row3_ok(p, w, residual, pad_value, out_split3, also_split3, per_image_shift)
+            if row3:
+                key += (246,)
+            cands = lambda: _fits(list(SPLIT3_PRESPLIT_TILES if x_split3 else SPLIT3_TILES) +
+                                  (list(SPLIT3_ROW3_TILES) if row3 and PICK_HOOK is None else []), p.cout)
         elif s3:
             # a pick among candidates that include the panel ids is remembered under a key of its own (71): a call of the same
             # geometry that they do not take (a per-image shift, operands of 2 GiB) must never replay it

@@ -1,7 +1,7 @@
 """The heavy layers of the 25-episode eval step (M = 130 050 rows: 50 maps of 51 x 51) alone on the chip, per split3 tile id: us,
 TFLOP/s, bit-identity of every unsplit id with id 43, and a hash of every output (ids 51..56 included) so that two builds can be
-compared.  The multi-tap layers also run the ids that read PRE-SPLIT activations (146 / 149, the input split on the device by the
-reference arithmetic) -- without a residual also with the second, pre-split output ("149+s" = id 149 with also_split3: the fp32 tensor
+compared.  The multi-tap layers also run the ids that read PRE-SPLIT activations (146 / 149, and 246 / 249 where they apply, the input
+split on the device by the reference arithmetic) -- without a residual also with the second, pre-split output ("149+s" = id 149 with also_split3: the fp32 tensor
 must be id 43's and the second one its split) -- and the 1x1 layers without a residual also run as producers of a pre-split output
 ("43s" = id 43 with out_split3, "49s" = the persistent id's producer kernel; the result must be the split of id 43's).  Every cell carries the fastest and the slowest of its --reps timings.  GPU.
 
@@ -22,6 +22,7 @@ UNSPLIT = (43, 42, 41, 44, 46, 47, 49)     # 47 / 49: persistent forms of 43 / 4
 SPLIT = (52, 51, 54, 56)
 PANEL = ops.SPLIT3_PANEL_TILES             # 71 / 72: activation-stationary forms (1x1, Kpad <= 256; conv_panel.hip)
 PRESPLIT = ops.SPLIT3_PRESPLIT_TILES       # 146 / 149: the forms of 46 / 49 on pre-split activations
+ROW3 = ops.SPLIT3_ROW3_TILES               # 246 / 249: 146 / 149 with one activation stage per (chunk, kh) (3x3, pad == dil, no residual / padding value; conv_row3.hip)
 # (cin, cout, k, dil, residual, padding value[, stride, maps of HW x HW]): the six geometries that carry ~81 % of the step's conv time, and the 3 x 3 layer
 # once more with a padding value (the PADV instantiation)
 LAYERS = ((256, 1024, 1, 1, True, False), (512, 1024, 1, 1, False, False), (1024, 256, 1, 1, False, False),
@@ -118,8 +119,10 @@ def main():
             sbuf = torch.zeros((M + 4) * cin * 3, dtype=torch.bfloat16, device=dev)
             sbuf[:(M + 1) * cin * 3] = presplit(buf[:M + 1]).reshape(-1)
             xs, pvs = sbuf[:M * cin * 3].view(N, HW, HW, cin // 32, 3, 32), sbuf[M * cin * 3:(M + 1) * cin * 3].view(cin // 32, 3, 32)
-            for tile in keep(PRESPLIT):
+            row3 = ROW3 if k == 3 and stride == 1 and not has_res and not padv and ops.row3_stage_rows(HW, dil) <= ops.ROW3_STAGE_ROWS else ()
+            for tile in keep(PRESPLIT + row3):
                 run = lambda: ops.conv2d(xs, prm, residual=res, pad_value=pvs if padv else None, out=out, tile=tile, x_split3=True)
+                out.zero_()
                 run()
                 same = torch.equal(out, ref)
                 us, worst = timed(run, args.reps)
@@ -150,7 +153,7 @@ def main():
             del want, outs
         print(f"{name:>16} k{k} d{dil} res{int(has_res)} | " + " | ".join(cells), flush=True)
         print(f"{'':>16} hash " + " ".join(hashes), flush=True)
-    print("(146 / 149: on the pre-split input; NNs: id NN writing a pre-split output, ! = not the split of id 43's;")
+    print("(146 / 149 / 246 / 249: on the pre-split input; NNs: id NN writing a pre-split output, ! = not the split of id 43's;")
     print(" NNN+s: id NNN writing fp32 and the pre-split copy, ! = either differs)")
     print("(! = an unsplit id differs from id 43; ~ = a split-K id differs from id 43, expected where it splits)")
 
