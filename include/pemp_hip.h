@@ -261,6 +261,16 @@ int pemp_cosine_proto_max_f32(const float* qry, int ldf, const float* protos, fl
                               uint8_t* resp, int B, int n, int c, int p, float dist_scalar,
                               void* stream);
 
+/* The same map against a prototype BANK: prototypes of K classes enrolled once, met by N queries in one launch.
+ *   bank  [K][2p][c]  (the protos layout above, class after class; 16-byte aligned)
+ *   index NULL:            every query against every class; pred [N][K][2][n], resp [N][K][n] (or NULL)
+ *   index [N] int32 (dev): query b against class index[b] (clamped into 0..K-1); pred [N][2][n], resp [N][n] (or NULL)
+ * For every (b, k) the outputs are bit for bit those of pemp_cosine_proto_max_f32 on query b with protos = bank[k].
+ * N, K <= 65535.                                                                                              */
+int pemp_cosine_bank_max_f32(const float* qry, int ldf, const float* bank, const int32_t* index,
+                             float* pred, uint8_t* resp, int N, int K, int n, int c, int p,
+                             float dist_scalar, void* stream);
+
 /* PANet's alignment branch (networks/panet.py:168-171): masks [B][2][n] from a low-resolution prediction
  * pred [B][2][n]:  masks[b][0] = [argmax == 1] (foreground), masks[b][1] = [argmax == 0]; channel 0 wins ties
  * (torch.argmax).  They feed pemp_masked_avg_pool_f32(full_res = 0) with the QUERY features as "support".    */

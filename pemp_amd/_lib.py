@@ -67,6 +67,7 @@ SYMBOLS = {
     "pemp_masked_avg_pool_f32": (c_int, [c_fp, c_int, c_fp, c_fp, c_fp, c_size] + [c_int] * 8 + [c_fp]),
     "pemp_cosine_proto_max_f32": (c_int, [c_fp, c_int, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_int,
                                           C.c_float, c_fp]),
+    "pemp_cosine_bank_max_f32": (c_int, [c_fp, c_int, c_fp, c_fp, c_fp, c_fp] + [c_int] * 5 + [C.c_float, c_fp]),
     "pemp_upsample_bilinear_ac_f32": (c_int, [c_fp, c_fp] + [c_int] * 6 + [c_fp]),
     "pemp_upsample_nearest_u8_i64": (c_int, [c_fp, c_fp] + [c_int] * 5 + [c_fp]),
     "pemp_eval_tail_workspace_bytes": (c_size, [c_int] * 3),

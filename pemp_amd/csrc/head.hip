@@ -50,6 +50,12 @@ extern "C" int pemp_cosine_proto_max_f32(const float* qry, int ldf, const float*
     return j16::pemp_cosine_proto_max_f32(qry, ldf, protos, pred, resp, B, n, c, p, dist_scalar, stream);
 }
 
+extern "C" int pemp_cosine_bank_max_f32(const float* qry, int ldf, const float* bank, const int32_t* index, float* pred,
+                                        uint8_t* resp, int N, int K, int n, int c, int p, float dist_scalar, void* stream) {
+    if (2 * p <= 8) return j8::pemp_cosine_bank_max_f32(qry, ldf, bank, index, pred, resp, N, K, n, c, p, dist_scalar, stream);
+    return j16::pemp_cosine_bank_max_f32(qry, ldf, bank, index, pred, resp, N, K, n, c, p, dist_scalar, stream);
+}
+
 extern "C" int pemp_argmax_masks_f32(const float* pred, float* masks, int B, int n, void* stream) {
     return j8::pemp_argmax_masks_f32(pred, masks, B, n, stream);
 }

@@ -331,10 +331,55 @@ struct RowTile {
                 if (qq + s < NQ) pass<NORM>(s, qq + s, stage, bp, lane, acc, ss);
         }
     }
+    // The same pass against T 16-column tables (prototype banks): the staged xv feeds one accumulator per tile.  Per tile
+    // the MFMAs and their k order are those of pass(), so a column's sum is the same bits whichever tile holds it.
+    template <bool NORM, int T>
+    __device__ __forceinline__ void pass_tiles(int s, int qq, float* stage, const float* const (&bp)[T], int lane,
+                                               hv4f (&acc)[T], float& ss) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) *(hv4f*)(stage + (4 * u + (lane >> 4)) * SLD + 4 * (lane & 15)) = buf[s][u];
+        if (qq + NB < NQ) load(s, qq + NB);
+        __builtin_amdgcn_wave_barrier();
+        const float* xr = stage + (lane & 15) * SLD + 4 * (lane >> 4);
+#pragma unroll
+        for (int t = 0; t < SQ / 16; ++t) {
+            const hv4f xv = *(const hv4f*)(xr + 16 * t);
+            if (NORM) ss += (xv.x * xv.x + xv.y * xv.y) + (xv.z * xv.z + xv.w * xv.w);
+#pragma unroll
+            for (int tt = 0; tt < T; ++tt) {
+                const hv4f pv = *(const hv4f*)(bp[tt] + qq * SQ + 16 * t);
+                acc[tt] = __builtin_amdgcn_mfma_f32_16x16x4f32(xv.x, pv.x, acc[tt], 0, 0, 0);
+                acc[tt] = __builtin_amdgcn_mfma_f32_16x16x4f32(xv.y, pv.y, acc[tt], 0, 0, 0);
+                acc[tt] = __builtin_amdgcn_mfma_f32_16x16x4f32(xv.z, pv.z, acc[tt], 0, 0, 0);
+                acc[tt] = __builtin_amdgcn_mfma_f32_16x16x4f32(xv.w, pv.w, acc[tt], 0, 0, 0);
+            }
+        }
+        __builtin_amdgcn_wave_barrier();
+    }
+    template <bool NORM, int T>
+    __device__ __forceinline__ void run_tiles(float* stage, const float* const (&bp)[T], int lane, hv4f (&acc)[T], float& ss) {
+#pragma unroll
+        for (int qq = 0; qq < NQ; qq += NB) {
+#pragma unroll
+            for (int s = 0; s < NB; ++s)
+                if (qq + s < NQ) pass_tiles<NORM, T>(s, qq + s, stage, bp, lane, acc, ss);
+        }
+    }
 };
 // D[i][j] of the 16x16 tile lives in lane 16*(i>>2) + j, register i&3: hand row (l & 15) to lane l.
 __device__ __forceinline__ void rows_to_lanes(const hv4f& acc, int lane, float (&v)[MAXJ]) {
     const int row = lane & 15, src = 16 * (row >> 2), e = row & 3;
+#pragma unroll
+    for (int j = 0; j < MAXJ; ++j) {
+        const float t0 = __shfl(acc[0], src + j, 64), t1 = __shfl(acc[1], src + j, 64);
+        const float t2 = __shfl(acc[2], src + j, 64), t3 = __shfl(acc[3], src + j, 64);
+        v[j] = e == 0 ? t0 : e == 1 ? t1 : e == 2 ? t2 : t3;
+    }
+}
+// the same for columns C0 .. C0 + MAXJ - 1 of the tile (C0 = 8: the second class of a bank tile)
+template <int C0>
+__device__ __forceinline__ void cols_to_lanes(const hv4f& acc, int lane, float (&v)[MAXJ]) {
+    const int row = lane & 15, src = 16 * (row >> 2) + C0, e = row & 3;
 #pragma unroll
     for (int j = 0; j < MAXJ; ++j) {
         const float t0 = __shfl(acc[0], src + j, 64), t1 = __shfl(acc[1], src + j, 64);
@@ -354,6 +399,22 @@ __device__ __forceinline__ float table_sqnorm(const float* tab, int ldt, int J, 
         for (int k = 0; k < MAXCL / 4; ++k) {                        // branch-free: rows >= J are the zero row
             const int ch = 4 * lane + 256 * k;
             const hv4f v = *(const hv4f*)(tab + min(j, J) * ldt + (ch < c ? ch : 0));
+            s[j] += ch < c ? (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w) : 0.f;
+        }
+    }
+    return wave_sum8(s);
+}
+
+// table_sqnorm for the J rows that start at row0 of a table with several classes (rows >= J: the zero row zrow)
+__device__ __forceinline__ float table_sqnorm_at(const float* tab, int ldt, int row0, int zrow, int J, int c, int lane) {
+    float s[MAXJ];
+#pragma unroll
+    for (int j = 0; j < MAXJ; ++j) {
+        s[j] = 0.f;
+#pragma unroll
+        for (int k = 0; k < MAXCL / 4; ++k) {
+            const int ch = 4 * lane + 256 * k;
+            const hv4f v = *(const hv4f*)(tab + (j < J ? row0 + j : zrow) * ldt + (ch < c ? ch : 0));
             s[j] += ch < c ? (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w) : 0.f;
         }
     }
@@ -418,6 +479,93 @@ __global__ __launch_bounds__(256, PEMP_HEAD_OCC) void cosine_mfma_kernel(const f
         pred[((size_t)b * 2 + 1) * n + i] = best[0];
         if (resp) resp[(size_t)b * n + i] = (uint8_t)(best[0] > best[1] ? bi[0] + 3 : bi[1]);
     }
+}
+
+// Prototype bank: the cosine map of cosine_mfma_kernel against SEVERAL classes' prototypes in one pass over the query
+// rows.  bank is [K][2p][c].  Two classes share a 16-column tile (class 2t in columns 0..7, class 2t+1 in columns 8..15,
+// columns past 2p and past the last class read the zero row) and a block keeps T tiles, i.e. up to 2T classes: the staged
+// 16 x 64 slab of a pass feeds T accumulators, |x|^2 is taken once.  A column of a 16x16x4 MFMA depends on its own table
+// column and on the k order alone, and the k order is that of cosine_mfma_kernel, so for every (query, class) the outputs
+// are bit for bit what that kernel writes for protos = bank[class].  Classes beyond 2T go to blockIdx.z (those blocks
+// read the rows again).  index != null: query b meets class index[b] only (clamped into the bank), one class per block.
+// LDS: [ncap * 2p + 1][c + 8] table (compact: a class's rows follow the previous class's; last row used = zeros) | stages.
+static inline int bank_ncap(bool indexed, int T, int K) { return indexed ? 1 : min(2 * T, K); }
+static inline size_t bank_lds_bytes(int ncap, int J, int c) { return ((size_t)(ncap * J + 1) * (c + 8) + 4 * 16 * SLD) * sizeof(float); }
+template <int NQ, int T>
+__global__ __launch_bounds__(256) void cosine_bank_mfma_kernel(const float* __restrict__ qry, int ldf,
+                                                               const float* __restrict__ bank,
+                                                               const int32_t* __restrict__ index, float* __restrict__ pred,
+                                                               uint8_t* __restrict__ resp, int n, int c, int p, int K,
+                                                               float scalar) {
+    extern __shared__ __attribute__((aligned(16))) float pnl[];
+    const int b = blockIdx.y;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int J = 2 * p, ldt = c + 8;
+    const int i0 = (blockIdx.x * 4 + wave) * 16;
+    const int r = lane & 15, q = lane >> 4;
+    const int ncap = index ? 1 : min(2 * T, K);                      // bank_ncap: the table the launch sized
+    const int kbase = index ? min(max((int)index[b], 0), K - 1) : (int)blockIdx.z * 2 * T;
+    const int ncls = index ? 1 : min(2 * T, K - kbase);              // classes of this block
+    const size_t slot0 = index ? (size_t)b : (size_t)b * K + kbase;  // output image of the block's first class
+    const int zrow = ncls * J;
+    float* stage = pnl + (ncap * J + 1) * ldt + wave * 16 * SLD;
+    RowTile<NQ> rt;
+    rt.init(qry + (size_t)b * n * ldf, ldf, i0, n, lane);
+    const float* pb = bank + (size_t)kbase * J * c;
+    const int c4 = c / 4;
+    for (int t = threadIdx.x; t < ncls * J * c4; t += 256) {
+        const int row = t / c4, ch = (t - row * c4) * 4;
+        *(hv4f*)(pnl + row * ldt + ch) = *(const hv4f*)(pb + (size_t)row * c + ch);
+    }
+    for (int ch = threadIdx.x; ch < c; ch += 256) pnl[zrow * ldt + ch] = 0.f;
+    __syncthreads();
+    const float* bp[T];
+    hv4f acc[T];
+#pragma unroll
+    for (int tt = 0; tt < T; ++tt) {
+        const int cl = 2 * tt + (r >> 3), j = r & 7;
+        bp[tt] = pnl + (size_t)((j < J && cl < ncls) ? cl * J + j : zrow) * ldt + 4 * q;
+        acc[tt] = (hv4f){0.f, 0.f, 0.f, 0.f};
+    }
+    float ss = 0.f;
+    rt.template run_tiles<true, T>(stage, bp, lane, acc, ss);
+    ss += __shfl_xor(ss, 16, 64);
+    ss += __shfl_xor(ss, 32, 64);                                    // lane l: |x|^2 of pixel (l & 15)
+    const float f = scalar / fmaxf(sqrtf(ss), 1e-8f);
+    const int i = i0 + r;
+#pragma unroll
+    for (int tt = 0; tt < T; ++tt)
+#pragma unroll
+        for (int half = 0; half < 2; ++half) {
+            const int cl = 2 * tt + half;
+            if (cl < ncls) {                                         // block-uniform: the shuffles below are wave-wide
+                const float pn2 = table_sqnorm_at(pnl, ldt, cl * J, zrow, J, c, lane);
+                float v[MAXJ];
+                if (half == 0) cols_to_lanes<0>(acc[tt], lane, v);
+                else cols_to_lanes<8>(acc[tt], lane, v);
+#pragma unroll
+                for (int j = 0; j < MAXJ; ++j) v[j] = v[j] / fmaxf(sqrtf(__shfl(pn2, j, 64)), 1e-8f) * f;
+                if (q == 0 && i < n) {
+                    float best[2] = {0.f, 0.f};      // as cosine_mfma_kernel: first maximum wins
+                    int bi[2] = {0, 0};
+#pragma unroll
+                    for (int j = 0; j < MAXJ; ++j)
+                        if (j < J) {
+                            const bool fg = j < p;
+                            const int first = fg ? 0 : p;
+                            if (fg) {
+                                if (j == first || v[j] > best[0]) { best[0] = v[j]; bi[0] = j; }
+                            } else {
+                                if (j == first || v[j] > best[1]) { best[1] = v[j]; bi[1] = j - p; }
+                            }
+                        }
+                    const size_t slot = slot0 + cl;
+                    pred[(slot * 2 + 0) * n + i] = best[1];
+                    pred[(slot * 2 + 1) * n + i] = best[0];
+                    if (resp) resp[slot * n + i] = (uint8_t)(best[0] > best[1] ? bi[0] + 3 : bi[1]);
+                }
+            }
+        }
 }
 
 // MPM soft assignment on the same row stream (MODE 0 of assign_kernel): softmax_j(-|x - c_j|^2) within
@@ -575,15 +723,14 @@ static inline size_t proj_lds_bytes(int, int) { return 0; }
 // -----------------------------------------------------------------------------------------------
 // cosine map + group max, VALU variant (c not a multiple of 8, or PEMP_HEAD_VALU set): one wave per query pixel.
 // torch>=2 F.cosine_similarity: each vector is divided by max(||.||, 1e-8), then dotted.
-__global__ __launch_bounds__(256) void cosine_kernel(const float* __restrict__ qry, int ldf,
-                                                     const float* __restrict__ protos, float* __restrict__ pred,
-                                                     uint8_t* __restrict__ resp, int n, int c, int p, float scalar) {
+// qb: the query image's rows, pb: its [2p][c] prototypes, pred_b / resp_b: its output image (shared by the two kernels below)
+__device__ __forceinline__ void cosine_pixels(const float* __restrict__ qb, int ldf, const float* __restrict__ pb,
+                                              float* __restrict__ pred_b, uint8_t* __restrict__ resp_b, int n, int c, int p,
+                                              float scalar) {
     __shared__ float pn[MAXJ][64 * MAXCL];
     __shared__ float nrm[MAXJ];
-    const int b = blockIdx.y;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int J = 2 * p;
-    const float* pb = protos + (size_t)b * J * c;
     for (int j = wave; j < J; j += 4) {
         float s = 0.f;
         for (int ch = lane; ch < c; ch += 64) {
@@ -601,7 +748,7 @@ __global__ __launch_bounds__(256) void cosine_kernel(const float* __restrict__ q
     __syncthreads();
     const int ncl = (c + 255) / 256;
     for (int i = blockIdx.x * 4 + wave; i < n; i += gridDim.x * 4) {
-        const float* xp = qry + ((size_t)b * n + i) * ldf;
+        const float* xp = qb + (size_t)i * ldf;
         float xv[MAXCL];
         float ss = 0.f;
 #pragma unroll
@@ -646,11 +793,29 @@ __global__ __launch_bounds__(256) void cosine_kernel(const float* __restrict__ q
                         bi[g] = j;
                     }
             }
-            pred[((size_t)b * 2 + 0) * n + i] = best[1];  // channel 0 = bg
-            pred[((size_t)b * 2 + 1) * n + i] = best[0];  // channel 1 = fg
-            if (resp) resp[(size_t)b * n + i] = (uint8_t)(best[0] > best[1] ? bi[0] + 3 : bi[1]);
+            pred_b[i] = best[1];                          // channel 0 = bg
+            pred_b[(size_t)n + i] = best[0];              // channel 1 = fg
+            if (resp_b) resp_b[i] = (uint8_t)(best[0] > best[1] ? bi[0] + 3 : bi[1]);
         }
     }
+}
+__global__ __launch_bounds__(256) void cosine_kernel(const float* __restrict__ qry, int ldf,
+                                                     const float* __restrict__ protos, float* __restrict__ pred,
+                                                     uint8_t* __restrict__ resp, int n, int c, int p, float scalar) {
+    const int b = blockIdx.y;
+    cosine_pixels(qry + (size_t)b * n * ldf, ldf, protos + (size_t)b * 2 * p * c, pred + (size_t)b * 2 * n,
+                  resp ? resp + (size_t)b * n : nullptr, n, c, p, scalar);
+}
+// prototype bank, wave-per-pixel: block (x, b, k) is cosine_kernel's block (x, b) with protos = bank[k] (index: bank[index[b]])
+__global__ __launch_bounds__(256) void cosine_bank_kernel(const float* __restrict__ qry, int ldf,
+                                                          const float* __restrict__ bank, const int32_t* __restrict__ index,
+                                                          float* __restrict__ pred, uint8_t* __restrict__ resp, int n, int c,
+                                                          int p, int K, float scalar) {
+    const int b = blockIdx.y;
+    const int k = index ? min(max((int)index[b], 0), K - 1) : (int)blockIdx.z;
+    const size_t slot = index ? (size_t)b : (size_t)b * K + k;
+    cosine_pixels(qry + (size_t)b * n * ldf, ldf, bank + (size_t)k * 2 * p * c, pred + slot * 2 * n,
+                  resp ? resp + slot * n : nullptr, n, c, p, scalar);
 }
 
 // masks[b][0][i] = [argmax_ch pred[b][.][i] == 1], masks[b][1][i] = [argmax == 0]  (channel 0 wins ties, as torch.argmax):
@@ -871,6 +1036,57 @@ static int pemp_cosine_proto_max_f32(const float* qry, int ldf, const float* pro
     hipLaunchKernelGGL(cosine_kernel, dim3(min(cdiv(n, 4), max(1, 4096 / B)), B), dim3(256), 0, (hipStream_t)stream, qry, ldf, protos,
                        pred, resp, n, c, p, dist_scalar);
     return launch_status("cosine");
+}
+
+static int pemp_cosine_bank_max_f32(const float* qry, int ldf, const float* bank, const int32_t* index, float* pred,
+                                    uint8_t* resp, int N, int K, int n, int c, int p, float dist_scalar, void* stream) {
+    PEMP_REQUIRE(qry && bank && pred, "cosine_bank: null pointer");
+    PEMP_REQUIRE(N > 0 && K > 0 && n > 0 && p >= 1 && 2 * p <= MAXJ, "cosine_bank: bad dims");
+    PEMP_REQUIRE(N <= 65535 && K <= 65535, "cosine_bank: N=%d, K=%d must be <= 65535", N, K);
+    PEMP_REQUIRE(c > 0 && c % 4 == 0 && c <= 64 * MAXCL && ldf >= c && ldf % 4 == 0, "cosine_bank: c=%d must be a multiple of 4 and <= %d", c, 64 * MAXCL);
+    PEMP_REQUIRE(((uintptr_t)qry & 15) == 0 && ((uintptr_t)bank & 15) == 0, "cosine_bank: qry and bank must be 16-byte aligned");
+    static const bool force_valu = getenv("PEMP_HEAD_VALU") != nullptr;     // A/B switch for measurements
+    const hipStream_t st = (hipStream_t)stream;
+#if PEMP_MAXJ == 8
+    if (mfma_rows_ok(c) && !force_valu) {
+        // tiles per block: all K classes in one pass over the query rows up to 8 classes (4 tiles, <= 153 KB of LDS);
+        // PEMP_BANK_TILES=1..4 caps it (A/B switch for measurements)
+        static const int cap_t = getenv("PEMP_BANK_TILES") ? atoi(getenv("PEMP_BANK_TILES")) : 4;
+        const int T = index ? 1 : min(cdiv(K, 2), max(1, min(cap_t, 4)));
+        const size_t lds = bank_lds_bytes(bank_ncap(index != nullptr, T, K), 2 * p, c);
+        const dim3 grid(cdiv(cdiv(n, 16), 4), N, index ? 1 : cdiv(K, 2 * T));
+#define PEMP_BANK(NQ, TT)                                                                                             \
+    do {                                                                                                              \
+        if (lds > 64 * 1024) {                                                                                        \
+            hipError_t e = hipFuncSetAttribute((const void*)cosine_bank_mfma_kernel<NQ, TT>,                          \
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                 \
+            if (e != hipSuccess) {                                                                                    \
+                set_error("cosine_bank: hipFuncSetAttribute(lds=%zu): %s", lds, hipGetErrorString(e));                \
+                return (int)e;                                                                                        \
+            }                                                                                                         \
+        }                                                                                                             \
+        hipLaunchKernelGGL((cosine_bank_mfma_kernel<NQ, TT>), grid, dim3(256), lds, st, qry, ldf, bank, index, pred, resp, n, \
+                           c, p, K, dist_scalar);                                                                     \
+    } while (0)
+#define PEMP_BANK_T(NQ)                                                                                               \
+    do {                                                                                                              \
+        if (T == 1) PEMP_BANK(NQ, 1);                                                                                 \
+        else if (T == 2) PEMP_BANK(NQ, 2);                                                                            \
+        else if (T == 3) PEMP_BANK(NQ, 3);                                                                            \
+        else PEMP_BANK(NQ, 4);                                                                                        \
+    } while (0)
+        if (c == 512) PEMP_BANK_T(8);
+        else if (c == 256) PEMP_BANK_T(4);
+        else if (c == 128) PEMP_BANK_T(2);
+        else PEMP_BANK_T(1);
+#undef PEMP_BANK_T
+#undef PEMP_BANK
+        return launch_status("cosine_bank_mfma");
+    }
+#endif
+    hipLaunchKernelGGL(cosine_bank_kernel, dim3(min(cdiv(n, 4), max(1, 4096 / N)), N, index ? 1 : K), dim3(256), 0, st, qry, ldf,
+                       bank, index, pred, resp, n, c, p, K, dist_scalar);
+    return launch_status("cosine_bank");
 }
 
 static int pemp_argmax_masks_f32(const float* pred, float* masks, int B, int n, void* stream) {

@@ -507,17 +507,24 @@ class PurifierEngine:
                        else a.get("pur0", (n, h, w, self.p0.cout)))
         # the ASPP input carries 8 spare pixel rows behind it: the folded-BatchNorm branches keep their per-channel
         # padding vectors there, inside the buffer-descriptor window of the tensor (conv_dma2.hip, PADV)
+        # The kernels reach a padding vector at a non-negative offset from the first tap, so it must sit at least dil * (w + 1)
+        # pixel rows behind the start of the map (ops._group_member_ok).  Behind the map itself that holds unless the map is
+        # small: ONE 13 x 13 image under dilation 18 -- a one-image pass is what a prototype bank's enroll / segment make.  `gap`
+        # unused rows then push the vectors out far enough, so that such a pass runs the split3 kernels too and equals, bit for
+        # bit, the same image inside a larger batch (without them it fell back to the fp32 chain).  0 for every larger map.
         c = self.p3.cout
-        flat = a.get("pur3+tail", (n * h * w + 8, c))
+        reach = max([q.dil for q in (self.aspp.branches() or []) if q.kh * q.kw > 1] or [0]) if isinstance(self.aspp, ASPPV2Engine) else 0
+        gap = max(0, reach * (w + 1) - n * h * w)
+        flat = a.get("pur3+tail", (n * h * w + gap + 8, c), zero=gap > 0)             # nobody writes the gap rows
         # p3's output has five readers.  Where the dilated ASPP branches qualify (presplit_readers) p3 writes it twice, fp32 and
         # pre-split -- that copy with its 8 spare rows too, for the split padding vectors -- and they read the split one
         br = self.aspp.branches() if isinstance(self.aspp, (ASPPV2Engine, ASPPEngine)) else None
         dual = pre and br is not None and presplit_readers(self.p3, br, x, n * h * w)
-        flat_s = a.get("pur3s+tail", (n * h * w + 8, c // 32, 3, 32), torch.bfloat16) if dual else None
+        flat_s = a.get("pur3s+tail", (n * h * w + gap + 8, c // 32, 3, 32), torch.bfloat16, zero=gap > 0) if dual else None
         ys = flat_s[:n * h * w].view(ops.split3_shape(n, h, w, c)) if dual else None
         y = ops.conv2d(y, self.p3, out=flat[:n * h * w].view(n, h, w, c), x_split3=pre, also_split3=ys)
         if isinstance(self.aspp, ASPPV2Engine):
-            return self.aspp.forward(y, tail=flat[n * h * w:], xs=ys, tail_s=flat_s[n * h * w:] if dual else None)
+            return self.aspp.forward(y, tail=flat[n * h * w + gap:], xs=ys, tail_s=flat_s[n * h * w + gap:] if dual else None)
         return self.aspp.forward(y, xs=ys) if dual else self.aspp.forward(y)
 
 

@@ -45,6 +45,13 @@ def test(_config, split, shot, exp_id, ckpt):
 
 
 @ex.command
+def test_bank(_config, split, shot, exp_id, ckpt):
+    """``test`` with the enroll-once protocol (entry.pemp_stage1.BankEvaluator): every class's supports enrolled once per round."""
+    from .pemp_stage1 import run_test_bank
+    return run_test_bank(_config, NAME, ModelClass, split, shot, exp_id, ckpt)
+
+
+@ex.command
 def train(_config, split, shot, seed, loss, sigma, exp_id):
     """Baseline training procedure (entry/baseline.py:54-62,65-110): no gradient clipping; VGG-16 or ResNet-50 per net.backbone."""
     from .pemp_stage1 import run_training

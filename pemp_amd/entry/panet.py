@@ -101,6 +101,14 @@ def test(_config, split, shot, exp_id, ckpt):
 
 
 @ex.command
+def test_bank(_config, split, shot, exp_id, ckpt):
+    """``test`` with the enroll-once protocol (entry.pemp_stage1.BankEvaluator): every class's supports enrolled once per round.
+    The alignment loss needs an episode's own supports beside its query, so this command reports the query loss only."""
+    from .pemp_stage1 import run_test_bank
+    return run_test_bank(_config, NAME, ModelClass, split, shot, exp_id, ckpt)
+
+
+@ex.command
 def train(_config, split, shot, seed, loss, sigma, exp_id, loss_coef):
     """PANet training procedure (entry/panet.py:103-146): loss + loss_coef * align_loss, no gradient clipping."""
     from .pemp_stage1 import run_training

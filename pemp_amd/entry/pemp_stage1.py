@@ -238,15 +238,18 @@ class Evaluator:
         dev_in = [torch.cat([ep[0][k].to(self.device, non_blocking=True) for ep in episodes]) for k in range(3)]
         labels = [ep[1].view(-1, *ep[1].shape[-2:]).to(self.device, non_blocking=True) for ep in episodes]
         with torch.no_grad():
-            pred = self._lowres(dev_in)
-            stats = torch.empty((len(episodes), 8), dtype=torch.float64, device=self.device)
-            by_size = {}
-            for i, lab in enumerate(labels):
-                by_size.setdefault(tuple(lab.shape[-2:]), []).append(i)
-            for idx in by_size.values():
-                sel = torch.tensor(idx, device=self.device)
-                _, st, _ = ops.eval_tail(pred.index_select(0, sel), torch.cat([labels[i] for i in idx]), ws_cache=self._ws)
-                stats.index_copy_(0, sel, st)
+            return self._tail_by_size(self._lowres(dev_in), labels)
+
+    def _tail_by_size(self, pred, labels):
+        """One fused tail launch per distinct label size -> stats f64 [len(labels), 8], rows in the given order."""
+        stats = torch.empty((len(labels), 8), dtype=torch.float64, device=self.device)
+        by_size = {}
+        for i, lab in enumerate(labels):
+            by_size.setdefault(tuple(lab.shape[-2:]), []).append(i)
+        for idx in by_size.values():
+            sel = torch.tensor(idx, device=self.device)
+            _, st, _ = ops.eval_tail(pred.index_select(0, sel), torch.cat([labels[i] for i in idx]), ws_cache=self._ws)
+            stats.index_copy_(0, sel, st)
         return stats
 
     def _lowres(self, dev_in):
@@ -359,6 +362,92 @@ class Evaluator:
         #: per-class IoU of every round, [te_epochs, len(val_labels)] / [te_epochs, 2] (the return value averages them)
         self.round_miou, self.round_biou = np.array(accum.values["miou"]), np.array(accum.values["biou"])
         return accum.mean(["loss", "miou", "biou"])
+
+
+class BankEvaluator(Evaluator):
+    """The enroll-once protocol over the same loop: per round, the supports of the round's FIRST task of every class that
+    occurs are enrolled into a prototype bank (``model.enroll``; ``shot`` = supports enrolled per class), and every query of
+    the round is segmented against its own class, ``batch`` queries per step (``model.segment_lowres(index=...)``, replayed
+    from a graph with ``use_graph``).  The fused tail, the device round table, the all-reduce and the return value are the
+    ordinary evaluator's.  Every rank walks the whole round and enrolls every class itself (the first task of a class may lie
+    in another rank's shard), so the result does not depend on the world size; it evaluates the queries of its own shard.
+    The bank has one slot per validation class of the split and keeps its storage over the rounds."""
+
+    def __init__(self, model, device=None, use_graph=True, splitk=None):
+        super().__init__(model, device, use_graph, lanes=1, splitk=splitk)
+        self.bank, self._labels = None, []
+
+    def start_eval_loop(self, dataset, num_classes, split, te_epochs=5, logger=None, batch=1, dataset_name="PASCAL"):
+        self._labels = [int(c) for c in get_val_labels(split, dataset_name)]
+        return super().start_eval_loop(dataset, num_classes, split, te_epochs, logger, batch, dataset_name)
+
+    def _enroll(self, slot, cls, sup_img, sup_mask):
+        from ..bank import PrototypeBank
+        one = self.model.enroll(sup_img.to(self.device, non_blocking=True), sup_mask.to(self.device, non_blocking=True), labels=[cls])
+        if self.bank is None or len(self.bank) != len(self._labels) or tuple(self.bank.protos.shape[1:]) != tuple(one.protos.shape[1:]):
+            zeros = torch.zeros((len(self._labels),) + tuple(one.protos.shape[1:]), dtype=torch.float32, device=self.device)
+            self.bank = PrototypeBank(zeros, one.family, one.backbone, one.precision, one.dist_scalar, labels=self._labels)
+        self.bank.update(slot, one)
+
+    def _episodes(self, dataset, indices):
+        """The round's episodes of this rank as ((qry_img, bank slot), qry_msk, cls); enrolls on the way."""
+        mine, enrolled = set(indices), set()
+        for i, (inputs, qry_msk, cls) in enumerate(super()._episodes(dataset, range(len(dataset)))):
+            c = int(cls[0])
+            if c not in self._labels:
+                raise ValueError(f"episode {i} has class {c}, which is not a validation class of the split {self._labels}")
+            slot = self._labels.index(c)
+            if c not in enrolled:
+                enrolled.add(c)
+                with ops.eval_splitk(ops.EVAL_SPLITK if self.splitk is None else self.splitk):
+                    self._enroll(slot, c, inputs[0], inputs[1])
+            if i in mine:
+                yield (inputs[2], slot), qry_msk, cls
+
+    def test_step_batch(self, episodes):
+        """``episodes``: list of ((qry_img [1,1,3,H,W], bank slot), qry_msk).  -> stats f64 [len(episodes), 8] on the GPU."""
+        qry = torch.cat([ep[0][0].to(self.device, non_blocking=True).flatten(0, 1) for ep in episodes])
+        index = [ep[0][1] for ep in episodes]
+        labels = [ep[1].view(-1, *ep[1].shape[-2:]).to(self.device, non_blocking=True) for ep in episodes]
+        seg = self.model.segment_graphed if self.use_graph else self.model.segment_lowres
+        with torch.no_grad(), ops.eval_splitk(ops.EVAL_SPLITK if self.splitk is None else self.splitk):
+            return self._tail_by_size(seg(self.bank, qry, index=index)[0], labels)
+
+    def test_step_device(self, inputs, qry_msk):
+        """One query per step -> (None, stats f64 [1,8]): the arg-max image is not kept on this path."""
+        return None, self.test_step_batch([(inputs, qry_msk)])
+
+    def test_steps_device(self, episodes):
+        return self.test_step_batch(episodes)
+
+
+def run_test_bank(_config, name, model_class, split, shot, exp_id, ckpt, seed=None):
+    """Body of the ``test_bank`` commands: ``test`` with the enroll-once protocol (``BankEvaluator``).  Same checkpoint
+    lookup, same episode source (``data.base_dir`` or synthetic), same result string; no configuration key of its own."""
+    import logging
+    logging.basicConfig(level=logging.INFO, format="%(message)s")
+    logger = logging.getLogger(name)
+    if split < 0:
+        raise ValueError("Argument `split` is required! For example: `python -m pemp_amd.entry.pemp_stage1 test_bank with split=0`")
+    if seed is not None:
+        torch.manual_seed(seed)
+    from ..core.snapshots import load_for_eval
+    model = model_class(logger)
+    load_for_eval(model, _config, exp_id, ckpt, logger)
+    model = model.cuda().eval()
+    dcfg = _config["data"]
+    data = eval_episodes(dcfg, shot, split)
+    ev = BankEvaluator(model)
+    loss, miou, biou = ev.start_eval_loop(data, num_classes(dcfg["dataset"]), split, _config["te"]["epochs"], logger,
+                                          batch=dcfg["test_bs"], dataset_name=dcfg["dataset"])
+    return f"Loss: {loss:.4f}, mIoU: {np.mean(miou) * 100:.2f}, bIoU: {np.mean(biou) * 100:.2f}"
+
+
+@ex.command
+def test_bank(_config, split, shot, seed, exp_id, ckpt):
+    """``python -m pemp_amd.entry.pemp_stage1 test_bank with split=0 exp_id=1``: the evaluation rounds of ``test`` with the
+    supports of every class enrolled once per round (its first task's) and all of the class's queries segmented against them."""
+    return run_test_bank(_config, NAME, ModelClass, split, shot, exp_id, ckpt, seed)
 
 
 @ex.command

@@ -39,6 +39,7 @@ class Baseline(_HeadMixin, backbones.BaseModel):
             raise ValueError(backbone_error.format(backbone))
         pretrained = pretrained_weights[backbone]
         self.backbone_name = backbone
+        self.feat_channels = 512 if backbone == "vgg16" else out_channels          # c of the encoder's output
         if backbone == "vgg16":
             trunk = backbones.VGG16Params(init_channels, last_relu=False)
             self.encoder = nn.Sequential(OrderedDict([("backbone", trunk)]))
@@ -60,6 +61,23 @@ class Baseline(_HeadMixin, backbones.BaseModel):
         else:
             eng["trunk"] = engine.ResNetEngine(self.encoder.backbone, arena)
             eng["proj"] = engine.conv_params(self.encoder.projection, None, relu=False)
+
+    # -- prototype banks (networks/pemp_stage1._HeadMixin.enroll / segment): the calls of lowres(), supports and queries apart
+    _bank_family = "baseline"
+
+    def _bank_setup(self):
+        return 1, net_ingredient.cfg["dist_scalar"]
+
+    def _bank_features(self, images):
+        eng = self._engine_for(images.device)
+        a = eng["arena"]
+        f = eng["trunk"].forward(engine.pack_episode(a, (images,)))
+        if eng["proj"] is not None:
+            f = ops.conv2d(f, eng["proj"], out=a.get("feat", tuple(f.shape[:3]) + (eng["proj"].cout,)))
+        return f
+
+    def _bank_pool(self, eng, feats, msk, K, S, out):
+        return ops.masked_avg_pool(feats, msk, K, S, full_res=True, ws_cache=eng["arena"].ws, out=out)
 
     def lowres(self, sup_img, sup_mask, qry_img, ret_ind=False, dist_scalar=None):
         dist_scalar = net_ingredient.cfg["dist_scalar"] if dist_scalar is None else dist_scalar

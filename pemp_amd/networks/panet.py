@@ -54,6 +54,11 @@ class PANet(_baseline.Baseline):
         if logger is not None:
             logger.info(f"           ==> Model {self.__class__.__name__} created")
 
+    _bank_family = "panet"          # prototype banks: the Baseline's calls with this module's own ``net`` ingredient
+
+    def _bank_setup(self):
+        return 1, net_ingredient.cfg["dist_scalar"]
+
     def forward(self, sup_img, sup_mask, qry_img, out_shape=None):
         """Same contract as the reference (panet.py:68-118): (logits [BQ,2,Ho,Wo], align_loss)."""
         if self.training:

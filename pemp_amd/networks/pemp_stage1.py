@@ -222,6 +222,104 @@ class _HeadMixin:
             return out
         return out, ops.upsample_nearest_u8_i64(resp, out_shape)
 
+    # -- prototype banks (pemp_amd.bank): enroll supports once, segment many queries -------------------------------
+    # A model family states: _bank_family (str, or None: its head conditions on the query, no bank), _bank_resp (it has a
+    # response map), _bank_setup() -> (p, dist_scalar), _bank_features(images) and _bank_pool(eng, feats, masks, K, S, out):
+    # the feature pass and the pooling call of its own ``lowres``.
+    _bank_family = None
+    _bank_resp = False
+
+    def _bank_desc(self):
+        if self._bank_family is None:
+            raise ValueError(f"{type(self).__name__}: prototype banks exist for the prototype-matching heads only (PEMP stage 1, "
+                             "Baseline, PANet); this model's head depends on the query")
+        p, dist_scalar = self._bank_setup()
+        return dict(family=self._bank_family, backbone=self.backbone_name, precision=self.__dict__.get("_precision", "f32"),
+                    p=int(p), c=int(self.feat_channels), dist_scalar=float(dist_scalar))
+
+    def _check_bank(self, bank, what):
+        from ..bank import PrototypeBank
+        if not isinstance(bank, PrototypeBank):
+            raise TypeError(f"{what}: expected a PrototypeBank, got {type(bank).__name__}")
+        for k, v in self._bank_desc().items():
+            if getattr(bank, k) != v:
+                raise ValueError(f"{what}: the bank was made with {k} = {getattr(bank, k)!r}, this model has {k} = {v!r}")
+
+    def enroll(self, sup_img, sup_mask, labels=None, out=None):
+        """Supports of K classes, ``sup_img`` [K,S,3,H,W] and ``sup_mask`` [K,S,2,H,W] -> ``PrototypeBank`` of their prototypes:
+        one supports-only pass through the trunk and the pooling call an episode makes.  ``out``: enroll into that bank (same
+        K) in place -- its ``protos`` keep their address, so captured graphs that read them see the new classes."""
+        from ..bank import PrototypeBank
+        desc = self._bank_desc()
+        if out is not None:
+            self._check_bank(out, "enroll(out=)")
+        self._require_eval_gpu(self, sup_img, sup_mask)
+        K, S, ch, H, W = sup_img.shape
+        if tuple(sup_mask.shape) != (K, S, 2, H, W):
+            raise ValueError(f"enroll: sup_mask must be [{K},{S},2,{H},{W}], got {tuple(sup_mask.shape)}")
+        if out is not None and (len(out) != K or not out.protos.is_cuda):
+            raise ValueError(f"enroll(out=): the bank holds {len(out)} classes on {out.protos.device}, {K} are enrolled")
+        eng = self._engine_for(sup_img.device)
+        with torch.no_grad():
+            feats = self._bank_features(sup_img.reshape(K * S, ch, H, W))
+            msk = sup_mask.reshape(K * S, 2, H, W).contiguous()
+            pro = self._bank_pool(eng, feats, msk, K, S, None if out is None else out.protos)
+        if out is None:
+            return PrototypeBank(pro, labels=labels, **{k: desc[k] for k in ("family", "backbone", "precision", "dist_scalar")})
+        if labels is not None:
+            out.labels = PrototypeBank._labels(labels, K)
+        return out
+
+    def _segment_dev(self, bank, qry_img, index_dev, ret_ind):
+        feats = self._bank_features(qry_img)
+        out = ops._cosine_bank(feats, bank.protos, bank.dist_scalar, index_dev, want_resp=ret_ind)
+        return out if ret_ind else (out, None)
+
+    def _segment_args(self, bank, qry_img, index, ret_ind, what):
+        self._check_bank(bank, what)
+        if ret_ind and not self._bank_resp:
+            raise ValueError(f"{what}: ret_ind is a stage-1 option (the response map of its meta-prototypes)")
+        if qry_img.dim() != 4:
+            raise ValueError(f"{what}: qry_img must be [N,3,H,W], got {tuple(qry_img.shape)}")
+        return None if index is None else ops.bank_index(index, qry_img.shape[0], len(bank))      # checked on the host
+
+    def segment_lowres(self, bank, qry_img, index=None, ret_ind=False):
+        """Queries ``qry_img`` [N,3,H,W] against an enrolled bank, at feature resolution: one query-only pass through the
+        trunk, one cosine launch.  ``index`` None: every query against every class -> pred [N,K,2,h,w]; ``index`` (N class
+        numbers, a Python sequence or a CPU tensor): query b against class index[b] -> pred [N,2,h,w].
+        -> (pred, resp uint8 or None)."""
+        idx = self._segment_args(bank, qry_img, index, ret_ind, "segment_lowres")
+        self._require_eval_gpu(self, qry_img, bank.protos)
+        with torch.no_grad():
+            return self._segment_dev(bank, qry_img, None if idx is None else idx.to(qry_img.device, non_blocking=True), ret_ind)
+
+    def segment(self, bank, qry_img, index=None, out_shape=None, ret_ind=False):
+        """``segment_lowres`` + the final upsampling of ``forward``: logits [N,2,Ho,Wo] with ``index``, [N,K,2,Ho,Wo] without
+        (+ the int64 response map [N,Ho,Wo] / [N,K,Ho,Wo] when ``ret_ind``)."""
+        pred, resp = self.segment_lowres(bank, qry_img, index, ret_ind)
+        out_shape = tuple(out_shape) if out_shape is not None else tuple(qry_img.shape[-2:])
+        lead = tuple(pred.shape[:-3])
+        out = self._finish(pred.reshape((-1,) + tuple(pred.shape[-3:])), None if resp is None else resp.reshape((-1,) + tuple(resp.shape[-2:])),
+                           out_shape)
+        if resp is None:
+            return out.view(lead + (2,) + out_shape)
+        return out[0].view(lead + (2,) + out_shape), out[1].view(lead + out_shape)
+
+    def segment_graphed(self, bank, qry_img, index=None, ret_ind=False):
+        """``segment_lowres`` replayed from a captured hipGraph (the protocol of ``lowres_graphed``).  The graph reads
+        ``bank.protos`` where it lies -- ``bank.update`` / ``enroll(out=bank)`` need no recapture -- and the index through a
+        static int32 buffer.  The returned tensors are the graph's static outputs."""
+        idx = self._segment_args(bank, qry_img, index, ret_ind, "segment_graphed")
+        self._require_eval_gpu(self, qry_img, bank.protos)
+        inputs = [qry_img] if idx is None else [qry_img, idx]
+        key = ("bank", bank.protos.data_ptr()) + tuple((tuple(t.shape), t.dtype) for t in inputs) + \
+              (len(bank), idx is not None, ret_ind, ops.EVAL_SPLITK)
+        eng = self._engine_for(qry_img.device)
+        # the graph holds the prototypes' address, the copy into the static index buffer reads host memory: keep both alive
+        eng.setdefault("bank_refs", {})[key] = (bank.protos, idx)
+        run = lambda s: self._segment_dev(bank, s[0], s[1] if idx is not None else None, ret_ind)
+        return self._replay(eng, key, inputs, run, run)
+
 
 class PEMPStage1(_HeadMixin, backbones.BaseModel):
     """Stage 1 of the Prior-Enhanced network with Meta-Prototypes (reference class of the same name)."""
@@ -249,6 +347,7 @@ class PEMPStage1(_HeadMixin, backbones.BaseModel):
         elif logger is not None:
             logger.info(f"           ==> pretrained file {pretrained} not found: backbone left at random init")
         check_protos(protos, "net.protos")
+        self.feat_channels = 512 if backbone == "vgg16" else out_channels         # c of the encoder's output
         self.ctr = nn.Parameter(torch.rand(out_channels, protos * 2), requires_grad=True) if protos > 0 else None
         if logger is not None:
             logger.info(f"           ==> Model {self.__class__.__name__} created")
@@ -270,6 +369,22 @@ class PEMPStage1(_HeadMixin, backbones.BaseModel):
         x4 = engine.pack_episode(eng["arena"], image_groups)
         f = eng["trunk"].forward(x4)
         return eng["purifier"].forward(f) if eng["purifier"] is not None else f
+
+    # -- prototype banks: the calls of lowres() / _head(), supports and queries apart ---------------
+    _bank_family = "pemp_stage1"
+    _bank_resp = True
+
+    def _bank_setup(self):
+        return (self.ctr.shape[1] // 2 if self.ctr is not None else 1), net_ingredient.cfg["dist_scalar"]
+
+    def _bank_features(self, images):
+        return self.encode(images)
+
+    def _bank_pool(self, eng, feats, msk, K, S, out):
+        ws = eng["arena"].ws
+        if self.ctr is not None:
+            return ops.mpm_protos(feats, msk, eng["ctr"], K, S, self.ctr.shape[1] // 2, ws_cache=ws, out=out)
+        return ops.masked_avg_pool(feats, msk, K, S, full_res=False, ws_cache=ws, out=out)
 
     # -- API -----------------------------------------------------------------------------------
     @net_ingredient.capture

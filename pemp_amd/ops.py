@@ -1022,6 +1022,79 @@ def cosine_proto_max(qry_feat, protos, dist_scalar, want_resp=False, pred=None, 
     return (pred, resp) if want_resp else pred
 
 
+def bank_index(index, n_queries, n_classes):
+    """The ``index`` argument of ``cosine_bank_max`` checked on the host: a Python sequence or a CPU integer tensor of
+    ``n_queries`` class numbers in ``0 .. n_classes - 1`` -> CPU int32 tensor.  A device tensor is refused: its values could
+    only be checked with a synchronisation."""
+    if isinstance(index, torch.Tensor):
+        if index.device.type != "cpu":
+            raise ValueError(f"cosine_bank_max: index must be a Python sequence or a CPU tensor (it is checked on the host), "
+                             f"got a tensor on {index.device}")
+        if index.dtype not in (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8):
+            raise ValueError(f"cosine_bank_max: index must hold integers, got {index.dtype}")
+        idx = index.reshape(-1).to(torch.int64)
+        if index.dim() != 1:
+            raise ValueError(f"cosine_bank_max: index must have shape [{n_queries}], got {tuple(index.shape)}")
+    else:
+        vals = list(index)
+        if any(int(v) != v for v in vals):
+            raise ValueError("cosine_bank_max: index must hold integers")
+        idx = torch.tensor([int(v) for v in vals], dtype=torch.int64)
+    if idx.numel() != n_queries:
+        raise ValueError(f"cosine_bank_max: index has {idx.numel()} entries for {n_queries} queries")
+    if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= n_classes):
+        raise ValueError(f"cosine_bank_max: index values must lie in 0..{n_classes - 1}, got {idx.tolist()}")
+    return idx.to(torch.int32)
+
+
+def cosine_bank_max(qry_feat, bank, dist_scalar, index=None, want_resp=False, pred=None, resp=None):
+    """qry_feat [N,h,w,c] (NHWC view); bank [K,2p,c] (prototypes of K enrolled classes, the layout of ``mpm_protos`` /
+    ``masked_avg_pool``).  ``index`` None: every query against every class -> pred [N,K,2,h,w] (+ resp uint8 [N,K,h,w]);
+    ``index`` (a Python sequence or a CPU integer tensor [N], checked here against 0 <= i < K, then uploaded as int32):
+    query b against class index[b] -> pred [N,2,h,w] (+ resp [N,h,w]).  One launch; [b,k] is bit for bit
+    ``cosine_proto_max(qry_feat[b:b+1], bank[k:k+1])[0]``."""
+    _bank_shapes(qry_feat, bank)
+    if index is not None:
+        index = bank_index(index, qry_feat.shape[0], bank.shape[0])
+    _lib.load()
+    _chk_dev(qry_feat, bank)
+    if index is not None:
+        index = index.to(qry_feat.device, non_blocking=True)
+    return _cosine_bank(qry_feat, bank, dist_scalar, index, want_resp, pred, resp)
+
+
+def _bank_shapes(qry_feat, bank):
+    ldf = _nhwc(qry_feat, "qry_feat")
+    c = qry_feat.shape[3]
+    if bank.dim() != 3 or bank.dtype != torch.float32 or not bank.is_contiguous() or bank.shape[0] < 1 \
+            or bank.shape[1] < 2 or bank.shape[1] % 2:
+        raise ValueError(f"cosine_bank_max: bank must be contiguous fp32 [K,2p,c], got {tuple(bank.shape)} {bank.dtype}")
+    if bank.shape[2] != c:
+        raise ValueError(f"cosine_bank_max: bank has c = {bank.shape[2]}, the features have c = {c}")
+    return ldf
+
+
+def _cosine_bank(qry_feat, bank, dist_scalar, index_dev, want_resp=False, pred=None, resp=None):
+    """The launch of ``cosine_bank_max``.  ``index_dev``: None or an int32 DEVICE tensor [N] whose values the caller has
+    checked on the host (``bank_index``) -- the static index buffer of a captured graph comes in here."""
+    lib = _lib.load()
+    _chk_dev(qry_feat, bank, index_dev)
+    ldf = _bank_shapes(qry_feat, bank)
+    n, h, w, c = qry_feat.shape
+    k, p = bank.shape[0], bank.shape[1] // 2
+    index = index_dev
+    if index is not None and (index.dtype != torch.int32 or tuple(index.shape) != (n,) or not index.is_contiguous()):
+        raise ValueError(f"cosine_bank_max: the device index must be contiguous int32 [{n}]")
+    lead = (n,) if index is not None else (n, k)
+    if pred is None:
+        pred = torch.empty(lead + (2, h, w), dtype=torch.float32, device=qry_feat.device)
+    if want_resp and resp is None:
+        resp = torch.empty(lead + (h, w), dtype=torch.uint8, device=qry_feat.device)
+    _lib.check(lib.pemp_cosine_bank_max_f32(_p(qry_feat), ldf, _p(bank), _p(index), _p(pred), _p(resp if want_resp else None),
+                                            n, k, h * w, c, p, float(dist_scalar), _stream()), "cosine_bank_max")
+    return (pred, resp) if want_resp else pred
+
+
 def upsample_bilinear_ac(pred, out_hw):
     lib = _lib.load()
     _chk_dev(pred)
