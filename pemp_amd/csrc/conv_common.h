@@ -53,6 +53,51 @@ __device__ __forceinline__ void store_quad(float* base, size_t off, const v4f& o
     *(u32x2*)((unsigned short*)base + off) = r;
 }
 
+// The epilogue's rounding contract, one quad of it: o = fmaf(v, scale, add), then max with 0 -- v the accumulator, add the shift
+// with whatever the variant adds to it (per-image shift, residual), in that variant's order.  The fma is explicit: written as
+// v * sc + add the contraction would be hipcc's choice per call site, and every epilogue variant must round identically (the
+// bit identity of the tile ids rests on it).  conv_stem_pool.hip applies the same expression per scalar (lane = channel).
+__device__ __forceinline__ v4f conv_affine_quad(const v4f& v, const v4f& sc, const v4f& add, bool relu) {
+    v4f o;
+    o.x = __builtin_fmaf(v.x, sc.x, add.x);
+    o.y = __builtin_fmaf(v.y, sc.y, add.y);
+    o.z = __builtin_fmaf(v.z, sc.z, add.z);
+    o.w = __builtin_fmaf(v.w, sc.w, add.w);
+    if (relu) {
+        o.x = fmaxf(o.x, 0.f);
+        o.y = fmaxf(o.y, 0.f);
+        o.z = fmaxf(o.z, 0.f);
+        o.w = fmaxf(o.w, 0.f);
+    }
+    return o;
+}
+
+// The split3 product of one K16 slice: a b with a = ah + am + al, b = bh + bm + bl (split3_bf16) is taken as the six bf16 x bf16
+// products whose size is above one fp32 rounding of it, in the FIXED order lh, hl, mm, mh, hm, hh -- smallest first, each exact in
+// the MFMA's fp32 sum.  The order is what makes every split3 tile id bit-identical to id 43; it is defined here.
+// (Two K loops write it out instead of calling this: conv_panel.hip interleaves the products of its accumulators, one hooked
+// instruction per MFMA slot, and picks product pr of this order by index; conv_dma2.hip's PEMP_MMA keeps its six lines because
+// the fp32-activation kernels come out with another schedule when they call it.)
+__device__ __forceinline__ void split3_mma6(f32x16& acc, bf16x8 ah, bf16x8 am, bf16x8 al, bf16x8 bh, bf16x8 bm, bf16x8 bl) {
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bm, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bh, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bm, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc, 0, 0, 0);
+}
+
+// LDS image of a split3 operand stage: a row holds 12 quads, position = plane * 4 + quad, and the quad is XORed with bits 2..3 of
+// the row.  -> the position of the row's 192 bytes in memory that belongs at LDS position ``pos`` (the map is its own inverse).
+// (A macro, like PEMP_CONV_PATCH_PUT below: as functions the two are simplified on their own before they are inlined, and the
+// address arithmetic of every kernel comes out differently -- other registers, in some kernels more of them.)
+#define PEMP_SPLIT3_SWZ(row_, pos_) (((pos_) & ~3) | (((pos_) & 3) ^ (((row_) >> 2) & 3)))
+
+// A 32 x 32 accumulator (lane (lr_, lh_) = (lane & 31, lane >> 5): column lr_, 16 registers = rows (e & 3) + 8 (e >> 2) + 4 lh_)
+// into the wave's 4 KB transpose patch S_, row-major.  The caller waits for the writes (lgkmcnt(0)) before it reads the patch.
+#define PEMP_CONV_PATCH_PUT(S_, acc_, lr_, lh_) \
+    _Pragma("unroll") for (int e = 0; e < 16; ++e) (S_)[((e & 3) + 8 * (e >> 2) + 4 * (lh_)) * 32 + (lr_)] = (acc_)[e]
+
 struct ConvArgs {
     const float* x;
     const float* w;
@@ -97,6 +142,23 @@ struct ConvGroupArgs {
 // neighbouring M tiles (3x3 halos) should therefore get ids that are congruent mod 8.  This
 // bijection hands every XCD one contiguous range of the logical (M-major, N-minor) tile order.
 // Placement only affects speed, never results.
+// XcdTileRange: XCD (bid & 7)'s range [first, first + count) of ``tiles`` tiles in that order, and block ``bid``'s place in it: it
+// is block ``idx`` of the ``step`` blocks of its XCD in a grid of ``nblk``.  One tile per block (nblk == tiles): tile first + idx,
+// which is xcd_tile_order (below, in its own words: the one-tile kernels keep their emitted code).
+// The persistent kernels (a resident grid, nblk <= tiles): tiles first + j for j = idx, idx + step, ... < count -- no counter, flag
+// or atomic; which block computes a tile, and when, is all that changes.
+struct XcdTileRange {
+    int first, count, step, idx;
+    __device__ __forceinline__ XcdTileRange(int tiles, int bid, int nblk) {
+        const int xcd = bid & 7;
+        idx = bid >> 3;
+        const int q8 = tiles >> 3, r8 = tiles & 7;
+        first = xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8;
+        count = q8 + (xcd < r8 ? 1 : 0);
+        step = (nblk - xcd + 7) >> 3;
+    }
+};
+
 __device__ __forceinline__ int xcd_tile_order(int bid, int nblk) {
     const int x = bid & 7, idx = bid >> 3;
     const int q = nblk >> 3, rem = nblk & 7;
@@ -125,7 +187,7 @@ __device__ __forceinline__ int xcd_tile_order(int bid, int nblk) {
 // [M][Cout / 32][3][32], per row and 32-channel group the planes h, m, l of split3_bf16 -- for a split3 conv that reads it with
 // PEMP_CONV_IN_SPLIT3 (conv_dma2.hip, A3).  A lane owns 8 consecutive channels of one row (4 lanes per row, 16 rows per pass), so
 // that every plane goes out as one 16-byte store and a row's 192 bytes are written by 4 neighbouring lanes.  The value that is
-// split is conv_epilogue_lds_pre's, statement for statement (no residual: the entry refuses one).
+// split is conv_affine_quad's, of the accumulator and the shift (+ per-image shift; no residual: the entry refuses one).
 // (conv_split3_affine: the scale / shift quads of the lane's 8 channels n .. n + 7; conv_store_split3_to: the store itself, to y3,
 // with those quads given -- the persistent kernels load them once per tile, beside their other epilogue loads)
 __device__ __forceinline__ void conv_split3_affine(const ConvArgs& a, int n, v4f (&sc)[2], v4f (&sh)[2]) {
@@ -154,16 +216,7 @@ __device__ __forceinline__ void conv_store_split3_to(const ConvArgs& a, unsigned
             const v4f v = *(const v4f*)(S + row * 32 + c8 + 4 * u);
             v4f add = sh[u];
             if (per_img && m < a.M) add += *(const v4f*)(a.shift + (size_t)(m / a.HoWo) * a.Cout + n + 4 * u);
-            o[u].x = __builtin_fmaf(v.x, sc[u].x, add.x);
-            o[u].y = __builtin_fmaf(v.y, sc[u].y, add.y);
-            o[u].z = __builtin_fmaf(v.z, sc[u].z, add.z);
-            o[u].w = __builtin_fmaf(v.w, sc[u].w, add.w);
-            if (relu) {
-                o[u].x = fmaxf(o[u].x, 0.f);
-                o[u].y = fmaxf(o[u].y, 0.f);
-                o[u].z = fmaxf(o[u].z, 0.f);
-                o[u].w = fmaxf(o[u].w, 0.f);
-            }
+            o[u] = conv_affine_quad(v, sc[u], add, relu);
         }
         if (m < a.M) {
             bf16x8 h, md, l;
@@ -228,8 +281,7 @@ __device__ __forceinline__ void conv_epilogue_lds_pre(const ConvArgs& a, f32x16 
                     }
                 }
             }
-#pragma unroll
-            for (int e = 0; e < 16; ++e) S[((e & 3) + 8 * (e >> 2) + 4 * lh) * 32 + lr] = acc[mi][ni][e];
+            PEMP_CONV_PATCH_PUT(S, acc[mi][ni], lr, lh);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // this wave's writes have landed (DS is in-order per wave)
             v4f s1 = {0.f, 0.f, 0.f, 0.f}, s2 = {0.f, 0.f, 0.f, 0.f};
             if (OS3 == 1 && EPI == 0 && !DB && (a.flags & PEMP_CONV_OUT_SPLIT3)) conv_store_split3(a, S, m_base + mi * 32, n_base + ni * 32, lane);
@@ -246,17 +298,7 @@ __device__ __forceinline__ void conv_epilogue_lds_pre(const ConvArgs& a, f32x16 
                         if constexpr (PRE) add += pre[(mi * TN + ni) * 4 + i];
                         else add += load_quad(a.res, (size_t)m * a.ldr + n, a.flags & PEMP_CONV_BF16_IO);
                     }
-                    v4f o;
-                    o.x = __builtin_fmaf(v.x, sc.x, add.x);      // explicit: every epilogue variant must round identically
-                    o.y = __builtin_fmaf(v.y, sc.y, add.y);
-                    o.z = __builtin_fmaf(v.z, sc.z, add.z);
-                    o.w = __builtin_fmaf(v.w, sc.w, add.w);
-                    if (relu) {
-                        o.x = fmaxf(o.x, 0.f);
-                        o.y = fmaxf(o.y, 0.f);
-                        o.z = fmaxf(o.z, 0.f);
-                        o.w = fmaxf(o.w, 0.f);
-                    }
+                    v4f o = conv_affine_quad(v, sc, add, relu);
                     if constexpr (DB) {                           // DropBlock2D.forward / its backward, fused (dropout.hip: pixel_scale_kernel)
                         const float k = a.rowmask[m];
                         o.x = __fdiv_rn(__fmul_rn(__fmul_rn(o.x, k), db_numel), db_sum);
@@ -330,9 +372,52 @@ __device__ __forceinline__ void conv_epilogue_lds(const ConvArgs& a, f32x16 (&ac
     conv_epilogue_lds_pre<TM, TN, 1, 0, DB, OS3>(a, acc, S, m_base, n_base, lane, none);
 }
 
+// The fp32 stores of one 32 x 32 sub-tile (rows m_base .., channels n32 ..) from the wave's patch S, for the persistent kernels,
+// whose operands are in registers already: sc / sh = the scale / shift quads of the lane's channels n32 + 4 (lane & 7) .., res =
+// the residual quads of its four rows (lane >> 3) + 8 i, requested by the caller ahead of time (nullptr: the kernel has no
+// residual path).  conv_epilogue_lds_pre's EPI 0 arithmetic, in its order: shift, per-image shift, residual.
+__device__ __forceinline__ void conv_patch_store_f32(const ConvArgs& a, const float* S, int m_base, int n32, int lane, const v4f& sc,
+                                                     const v4f& sh, bool per_img, const v4f* res, unsigned bf16) {
+    const bool relu = a.flags & PEMP_CONV_RELU;
+    const int rr = lane >> 3, c4 = (lane & 7) * 4, n = n32 + c4;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int row = rr + 8 * i;
+        const int m = m_base + row;
+        const v4f v = *(const v4f*)(S + row * 32 + c4);
+        if (m < a.M) {
+            v4f add = sh;
+            if (per_img) add += *(const v4f*)(a.shift + (size_t)(m / a.HoWo) * a.Cout + n);
+            if (res && a.res) add += res[i];
+            store_quad(a.y, (size_t)m * a.ldy + n, conv_affine_quad(v, sc, add, relu), bf16);
+        }
+    }
+}
+
+// Epilogue of the persistent split3 kernels (conv_dma2.hip: conv_dma2_s3p_body; conv_row3.hip): the residual quads of the wave tile
+// (order [mi][ni][i]) and the scale / shift quads of every column group were loaded by the caller in one batch, so the epilogue
+// waits once and its stores issue back to back.  PLAIN: no residual, per-image shift or bf16 output (the entry refuses them).
+template <int TM, int TN, bool PLAIN = false>
+__device__ __forceinline__ void conv_epilogue_s3p(const ConvArgs& a, f32x16 (&acc)[TM][TN], float* S, int m_base, int n_base,
+                                                  int lane, const v4f* pre, const v4f (&scv)[TN], const v4f (&shv)[TN]) {
+    const bool per_img = !PLAIN && (a.flags & PEMP_CONV_SHIFT_PER_IMAGE);
+    const int lr = lane & 31, lh = lane >> 5;
+#pragma unroll
+    for (int ni = 0; ni < TN; ++ni) {
+#pragma unroll
+        for (int mi = 0; mi < TM; ++mi) {
+            PEMP_CONV_PATCH_PUT(S, acc[mi][ni], lr, lh);
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // this wave's writes have landed (DS is in-order per wave)
+            conv_patch_store_f32(a, S, m_base + mi * 32, n_base + ni * 32, lane, scv[ni], shv[ni], per_img,
+                                 PLAIN ? nullptr : pre + (mi * TN + ni) * 4, PLAIN ? 0u : a.flags & PEMP_CONV_BF16_IO);
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // reads done before the patch is rewritten
+        }
+    }
+}
+
 // Epilogue of the 16-row wave tiles (conv_dma2.hip, R16): TN accumulators of 16 x 16 (rows 4 (lane >> 4) + e, column lane & 15) go
 // through a 16 x (16 TN) LDS patch (row stride + 4 floats: the four lane groups write different banks) so that a lane owns 4
-// consecutive channels of one pixel; the arithmetic is conv_epilogue_lds_pre's, statement for statement (identical rounding).
+// consecutive channels of one pixel; shift, per-image shift and residual are added in conv_epilogue_lds_pre's order.
 template <int TN>
 __device__ __forceinline__ void conv_epilogue_r16(const ConvArgs& a, v4f (&acc)[TN], float* S, int m_base, int n_base, int lane) {
     constexpr int WN = TN * 16, LD = WN + 4, QPR = WN / 4;
@@ -358,18 +443,7 @@ __device__ __forceinline__ void conv_epilogue_r16(const ConvArgs& a, v4f (&acc)[
             v4f add = sh;
             if (per_img) add += *(const v4f*)(a.shift + (size_t)(m / a.HoWo) * a.Cout + n);
             if (a.res) add += load_quad(a.res, (size_t)m * a.ldr + n, a.flags & PEMP_CONV_BF16_IO);
-            v4f o;
-            o.x = __builtin_fmaf(v.x, sc.x, add.x);
-            o.y = __builtin_fmaf(v.y, sc.y, add.y);
-            o.z = __builtin_fmaf(v.z, sc.z, add.z);
-            o.w = __builtin_fmaf(v.w, sc.w, add.w);
-            if (relu) {
-                o.x = fmaxf(o.x, 0.f);
-                o.y = fmaxf(o.y, 0.f);
-                o.z = fmaxf(o.z, 0.f);
-                o.w = fmaxf(o.w, 0.f);
-            }
-            store_quad(a.y, (size_t)m * a.ldy + n, o, a.flags & PEMP_CONV_BF16_IO);
+            store_quad(a.y, (size_t)m * a.ldy + n, conv_affine_quad(v, sc, add, relu), a.flags & PEMP_CONV_BF16_IO);
         }
     }
 }
@@ -415,5 +489,29 @@ int pack_split3(const float* w, void* out, int cout, int kpad, hipStream_t st);
 // conv_stem_pool.hip: the 7x7 / 2 / 3 NHWC4 stem (split3 weights) + its 3 / 2 / 1 ceil-mode max-pool in one launch (PEMP_CONV_POOL3S2)
 int launch_conv_stem_pool(const ConvArgs& a, hipStream_t st);
 int conv_stem_pool_out(int i);
+
+// Grid of a persistent kernel (XcdTileRange's walk): the blocks that are resident at once -- the occupancy of the kernel, asked
+// for once and kept in ``occ_cache`` (zero on entry; one per instantiation; racing fills write the same value), times the CUs --
+// at least 8 (every XCD's range needs a block), at most ``tiles``.  -> 0 and the grid, or an error (set; ``what`` names the kernel).
+template <class Kern> int allow_lds(Kern kern, size_t lds);      // conv_tiles.h
+template <class Kern>
+int persistent_grid(Kern kern, int threads, size_t lds, long long tiles, int& occ_cache, const char* what, int& grid_out) {
+    if (!occ_cache) {
+        const int rc = allow_lds(kern, lds);        // the occupancy query wants what the launch will have
+        if (rc) return rc;
+        int v = 0;
+        hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, (const void*)kern, threads, lds);
+        if (e != hipSuccess || v <= 0) {
+            set_error("%s: occupancy query failed (%s, %d blocks)", what, hipGetErrorString(e), v);
+            return -1;
+        }
+        occ_cache = v;
+    }
+    long long grid = (long long)occ_cache * (conv_dma2_simds() / 4);
+    if (grid < 8) grid = 8;
+    if (grid > tiles) grid = tiles;
+    grid_out = (int)grid;
+    return 0;
+}
 
 }  // namespace pemp

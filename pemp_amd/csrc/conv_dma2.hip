@@ -49,9 +49,8 @@ typedef __attribute__((address_space(3))) void* lptr_t;
 // two rounds, the second 27 % full, 64 % of the chip's MFMA time at best -- and 2608 of 16 x 32 -- three rounds of half the
 // length, 85 %.  It pays twice the LDS reads per flop for that, so it only wins where a launch is a few rounds long.
 // S3 (tile ids 41..46 / 51..56, pemp_hip.h): fp32 operands on the bf16 MFMA pipe.  Every fp32 x is split exactly into three bf16
-// pieces x = h + m + l (round to nearest at each stage: |m| <= 2^-8 |x|, |l| <= 2^-16 |x|); a product a b is taken as the six
-// bf16 x bf16 products whose size is above one fp32 rounding of it (lh, hl, mm, mh, hm, hh -- in that fixed order, smallest
-// first), each exact in the MFMA's fp32 sum.  The activations stay fp32 in memory and in LDS (same DMA, swizzle, tap masks and
+// pieces x = h + m + l (round to nearest at each stage: |m| <= 2^-8 |x|, |l| <= 2^-16 |x|); a product a b is taken as six bf16 x
+// bf16 products in a fixed order (split3_mma6, conv_common.h).  The activations stay fp32 in memory and in LDS (same DMA, swizzle, tap masks and
 // padding values as the fp32 kernels) and are split in registers after the fragment read; the weights come pre-split
 // (pemp_pack_split3_bf16: per row and 32-channel K step, three 64-byte planes h, m, l), 192 bytes per row and K step in LDS.
 // A K step is two K16 slices of v_mfma_f32_32x32x16_bf16 (lane half lh of slice s: channels 16 s + 8 lh .. + 7); every
@@ -146,7 +145,7 @@ __device__ __forceinline__ void conv_dma2_body(const ConvArgs& a, const int bid,
         if constexpr (A3) {     // LDS quad q of the A tile = row q / 12, position q % 12: the B tile's layout and swizzle
             const int q = i * NW * 64 + tid, pos = q % 12;
             arow_ = q / 12;
-            asrc_ = ((pos & ~3) | ((pos & 3) ^ ((arow_ >> 2) & 3))) * 16;
+            asrc_ = PEMP_SPLIT3_SWZ(arow_, pos) * 16;
         }
         const int m = m0 + arow_;
         const bool ok = m < a.M;
@@ -177,7 +176,7 @@ __device__ __forceinline__ void conv_dma2_body(const ConvArgs& a, const int bid,
     for (int i = 0; i < BL; ++i) {
         if constexpr (S3) {     // LDS quad q of the tile = row q / 12, position q % 12 = plane * 4 + (quad ^ ((row >> 2) & 3))
             const int q = i * NW * 64 + tid, row = q / 12, pos = q - row * 12;
-            const int src = (pos & ~3) | ((pos & 3) ^ ((row >> 2) & 3));
+            const int src = PEMP_SPLIT3_SWZ(row, pos);
             b_voff[i] = (unsigned)((n0 + row) * a.Kpad * 6 + src * 16);
         } else {
             b_voff[i] = (unsigned)((n0 + r + RPI * i) * a.Kpad + sq * 4) * 4u;
@@ -348,6 +347,8 @@ __device__ __forceinline__ void conv_dma2_body(const ConvArgs& a, const int bid,
                 const bf16x8 bh_ = __builtin_bit_cast(bf16x8, bf3[src_][ni][0]);                                  \
                 const bf16x8 bm_ = __builtin_bit_cast(bf16x8, bf3[src_][ni][1]);                                  \
                 const bf16x8 bl_ = __builtin_bit_cast(bf16x8, bf3[src_][ni][2]);                                  \
+                /* split3_mma6's products, in its order (as a call of it the K loops of the fp32-activation kernels */ \
+                /* come out with another schedule and other register counts) */                                   \
                 acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al_[mi], bh_, acc[mi][ni], 0, 0, 0);        \
                 acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah_[mi], bl_, acc[mi][ni], 0, 0, 0);        \
                 acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am_[mi], bm_, acc[mi][ni], 0, 0, 0);        \
@@ -588,11 +589,8 @@ __global__ __launch_bounds__(NW * 64) void conv_dma2_kernel(ConvArgs a) {
 
 // ---- persistent split3 form (tile ids 47, 49 = the shapes of 43, 46; pemp_hip.h).  (41's shape, 128 x 128 in 4 waves, needs
 // scratch at 2 waves per SIMD in this form: no id.)  The grid is the number of blocks
-// that are resident at once (occupancy x CUs, at most the tile count), and every block walks a fixed sequence of tiles: the
-// blocks of XCD x (block ids = x mod 8) share XCD x's contiguous range of the M-major tile order (xcd_tile_order's ranges), block
-// 8 i + x takes tiles i, i + gx, i + 2 gx, ... of it (gx = the XCD's block count).  No counter, no flag, no atomic: which block
-// computes a tile, and when, is all that changes -- each accumulator sees the same MFMAs in the same order as in ids 41..46, and
-// the epilogue does the same arithmetic: bit-identical.
+// that are resident at once (persistent_grid), and every block walks a fixed sequence of tiles (XcdTileRange, conv_common.h).
+// Each accumulator sees the same MFMAs in the same order as in ids 41..46, and the epilogue does the same arithmetic: bit-identical.
 // What the loop buys: one block per tile starts cold (two DMA stages issued and waited for in full before its first MFMA) and
 // ends with a serial epilogue (residual loads in series with the LDS transpose and the stores).  Here, inside a block,
 //  * the NEXT tile's step-0 DMA is issued at the barrier of this tile's second-to-last K step, into the stage buffer that step
@@ -605,96 +603,23 @@ __global__ __launch_bounds__(NW * 64) void conv_dma2_kernel(ConvArgs a) {
 //    stores then issue back to back;
 //  * the next tile's step-1 DMA follows the epilogue's stores, and the wait before its first MFMA is counted past the stores
 //    (vector memory operations retire in order: stage 0 -> residual / scale loads -> stores -> stage 1).
-// Epilogue of the persistent form: conv_epilogue_lds_pre (EPI 0, no DropBlock) statement for statement, with the scale / shift
-// quads of every column group loaded by the caller together with the residual quads.
-template <int TM, int TN>
-__device__ __forceinline__ void conv_epilogue_s3p(const ConvArgs& a, f32x16 (&acc)[TM][TN], float* S, int m_base, int n_base,
-                                                  int lane, const v4f (&pre)[TM * TN * 4], const v4f (&scv)[TN], const v4f (&shv)[TN]) {
-    const bool relu = a.flags & PEMP_CONV_RELU;
-    const bool per_img = a.flags & PEMP_CONV_SHIFT_PER_IMAGE;
-    const int lr = lane & 31, lh = lane >> 5;
-    const int rr = lane >> 3, c4 = (lane & 7) * 4;
-#pragma unroll
-    for (int ni = 0; ni < TN; ++ni) {
-        const int n = n_base + ni * 32 + c4;
-        const v4f sc = scv[ni], sh = shv[ni];
-#pragma unroll
-        for (int mi = 0; mi < TM; ++mi) {
-#pragma unroll
-            for (int e = 0; e < 16; ++e) S[((e & 3) + 8 * (e >> 2) + 4 * lh) * 32 + lr] = acc[mi][ni][e];
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // this wave's writes have landed (DS is in-order per wave)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int row = rr + 8 * i;
-                const int m = m_base + mi * 32 + row;
-                const v4f v = *(const v4f*)(S + row * 32 + c4);
-                if (m < a.M) {
-                    v4f add = sh;
-                    if (per_img) add += *(const v4f*)(a.shift + (size_t)(m / a.HoWo) * a.Cout + n);
-                    if (a.res) add += pre[(mi * TN + ni) * 4 + i];
-                    v4f o;
-                    o.x = __builtin_fmaf(v.x, sc.x, add.x);      // explicit: every epilogue variant must round identically
-                    o.y = __builtin_fmaf(v.y, sc.y, add.y);
-                    o.z = __builtin_fmaf(v.z, sc.z, add.z);
-                    o.w = __builtin_fmaf(v.w, sc.w, add.w);
-                    if (relu) {
-                        o.x = fmaxf(o.x, 0.f);
-                        o.y = fmaxf(o.y, 0.f);
-                        o.z = fmaxf(o.z, 0.f);
-                        o.w = fmaxf(o.w, 0.f);
-                    }
-                    store_quad(a.y, (size_t)m * a.ldy + n, o, a.flags & PEMP_CONV_BF16_IO);
-                }
-            }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // reads done before the patch is rewritten
-        }
-    }
-}
-
+// (The epilogue of OUT 0 is conv_epilogue_s3p, conv_common.h.)
 // OUT 1 / 2 (below): the tile goes out pre-split (conv_store_split3_to on every 32 x 32 sub-tile, the scale / shift quads of the lane's
-// 8 channels given), with ALSO behind the fp32 stores of conv_epilogue_s3p's loop -- no residual in either.
+// 8 channels given), with ALSO behind the sub-tile's fp32 stores (conv_patch_store_f32) -- no residual in either.
 template <int TM, int TN, bool ALSO>
 __device__ __forceinline__ void conv_epilogue_s3p_split(const ConvArgs& a, f32x16 (&acc)[TM][TN], float* S, int m_base, int n_base, int lane,
                                                         const v4f (&scv)[ALSO ? TN : 1], const v4f (&shv)[ALSO ? TN : 1],
                                                         const v4f (&sc8)[TN][2], const v4f (&sh8)[TN][2]) {
-    const bool relu = a.flags & PEMP_CONV_RELU;
-    const bool per_img = a.flags & PEMP_CONV_SHIFT_PER_IMAGE;
     const int lr = lane & 31, lh = lane >> 5;
-    const int rr = lane >> 3, c4 = (lane & 7) * 4;
     unsigned short* y3 = (unsigned short*)(ALSO ? (void*)a.res : (void*)a.y);
 #pragma unroll
     for (int ni = 0; ni < TN; ++ni) {
-        const int n = n_base + ni * 32 + c4;
 #pragma unroll
         for (int mi = 0; mi < TM; ++mi) {
-#pragma unroll
-            for (int e = 0; e < 16; ++e) S[((e & 3) + 8 * (e >> 2) + 4 * lh) * 32 + lr] = acc[mi][ni][e];
+            PEMP_CONV_PATCH_PUT(S, acc[mi][ni], lr, lh);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // this wave's writes have landed (DS is in-order per wave)
-            if constexpr (ALSO) {
-                const v4f sc = scv[ni], sh = shv[ni];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const int row = rr + 8 * i;
-                    const int m = m_base + mi * 32 + row;
-                    const v4f v = *(const v4f*)(S + row * 32 + c4);
-                    if (m < a.M) {
-                        v4f add = sh;
-                        if (per_img) add += *(const v4f*)(a.shift + (size_t)(m / a.HoWo) * a.Cout + n);
-                        v4f o;
-                        o.x = __builtin_fmaf(v.x, sc.x, add.x);      // explicit: every epilogue variant must round identically
-                        o.y = __builtin_fmaf(v.y, sc.y, add.y);
-                        o.z = __builtin_fmaf(v.z, sc.z, add.z);
-                        o.w = __builtin_fmaf(v.w, sc.w, add.w);
-                        if (relu) {
-                            o.x = fmaxf(o.x, 0.f);
-                            o.y = fmaxf(o.y, 0.f);
-                            o.z = fmaxf(o.z, 0.f);
-                            o.w = fmaxf(o.w, 0.f);
-                        }
-                        store_quad(a.y, (size_t)m * a.ldy + n, o, 0);
-                    }
-                }
-            }
+            if constexpr (ALSO)
+                conv_patch_store_f32(a, S, m_base + mi * 32, n_base + ni * 32, lane, scv[ni], shv[ni], a.flags & PEMP_CONV_SHIFT_PER_IMAGE, nullptr, 0);
             conv_store_split3_to(a, y3, S, m_base + mi * 32, n_base + ni * 32, lane, sc8[ni], sh8[ni]);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // reads done before the patch is rewritten
         }
@@ -737,17 +662,12 @@ __device__ __forceinline__ void conv_dma2_s3p_body(const ConvArgs& a) {
     const int wn0 = (wave % WGN) * WN;
     const int lr = lane & 31, lh = lane >> 5;
 
-    // the block's tile sequence: tiles [t_first + j] of its XCD's range, j = idx, idx + gx, ... < t_cnt
+    // the block's tile sequence: tiles tr.first + j, j = tr.idx, tr.idx + tr.step, ... < tr.count
     const int ntn = a.Cout / BN;
-    const int T = (a.M + BM - 1) / BM * ntn;
-    const int xcd = (int)blockIdx.x & 7, idx = (int)blockIdx.x >> 3;
-    const int q8 = T >> 3, r8 = T & 7;
-    const int t_first = xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8;
-    const int t_cnt = q8 + (xcd < r8 ? 1 : 0);
-    const int gx = ((int)gridDim.x - xcd + 7) >> 3;
-    if (idx >= t_cnt) return;                   // (the launch clamps the grid to the tile count: not expected)
-    int j = idx;
-    int m0 = (a.bm_first + (t_first + j) / ntn) * BM, n0 = ((t_first + j) % ntn) * BN;
+    const XcdTileRange tr((a.M + BM - 1) / BM * ntn, (int)blockIdx.x, (int)gridDim.x);
+    if (tr.idx >= tr.count) return;             // (the launch clamps the grid to the tile count: not expected)
+    int j = tr.idx;
+    int m0 = (a.bm_first + (tr.first + j) / ntn) * BM, n0 = ((tr.first + j) % ntn) * BN;
 
     const int p = tid & 7;
     const int r = tid >> 3;
@@ -770,7 +690,7 @@ __device__ __forceinline__ void conv_dma2_s3p_body(const ConvArgs& a) {
             if constexpr (A3) {     // LDS quad q of the A tile = row q / 12, position q % 12: the B tile's layout and swizzle
                 const int q = i * NW * 64 + tid, pos = q % 12;
                 arow_ = q / 12;
-                asrc_ = ((pos & ~3) | ((pos & 3) ^ ((arow_ >> 2) & 3))) * 16;
+                asrc_ = PEMP_SPLIT3_SWZ(arow_, pos) * 16;
             }
             const int m = m0_ + arow_;
             const bool ok = m < a.M;
@@ -800,7 +720,7 @@ __device__ __forceinline__ void conv_dma2_s3p_body(const ConvArgs& a) {
 #pragma unroll
         for (int i = 0; i < BL; ++i) {
             const int q = i * NW * 64 + tid, row = q / 12, pos = q - row * 12;
-            const int src = (pos & ~3) | ((pos & 3) ^ ((row >> 2) & 3));
+            const int src = PEMP_SPLIT3_SWZ(row, pos);
             b_voff[i] = (unsigned)((n0_ + row) * a.Kpad * 6 + src * 16);
         }
     };
@@ -847,9 +767,9 @@ __device__ __forceinline__ void conv_dma2_s3p_body(const ConvArgs& a) {
             for (int ni = 0; ni < TN; ++ni)
 #pragma unroll
                 for (int e = 0; e < 16; ++e) acc[mi][ni][e] = 0.f;
-        const int jn = j + gx;
-        const bool more = jn < t_cnt;
-        const int m0n = more ? (a.bm_first + (t_first + jn) / ntn) * BM : m0, n0n = more ? ((t_first + jn) % ntn) * BN : n0;
+        const int jn = j + tr.step;
+        const bool more = jn < tr.count;
+        const int m0n = more ? (a.bm_first + (tr.first + jn) / ntn) * BM : m0, n0n = more ? ((tr.first + jn) % ntn) * BN : n0;
 
         int kt = 0;
         PEMP_READ(0, pb, 0);
@@ -1207,24 +1127,11 @@ static int launch_dma2_s3p(const ConvArgs& a, hipStream_t st) {
         else return conv_dma2_s3p_kernel<T::BM, T::BN, T::WGM, T::NW, decltype(padv)::value>;
     };
     auto kern = a.padv ? s3p_kernel(std::true_type{}) : s3p_kernel(std::false_type{});
-    static int occ[2] = {0, 0};          // blocks per CU of the two instantiations (racing fills write the same value)
-    int& o = occ[a.padv ? 1 : 0];
-    if (!o) {
-        const int rc = allow_lds(kern, lds);       // the occupancy query wants what the launch will have
-        if (rc) return rc;
-        int v = 0;
-        hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, (const void*)kern, T::NW * 64, lds);
-        if (e != hipSuccess || v <= 0) {
-            set_error("conv split3 persistent: occupancy query failed (%s, %d blocks)", hipGetErrorString(e), v);
-            return -1;
-        }
-        o = v;
-    }
-    const long long tiles = tile_grid<T>(a);
-    long long grid = (long long)o * (conv_dma2_simds() / 4);
-    if (grid < 8) grid = 8;              // every XCD's range needs a block
-    if (grid > tiles) grid = tiles;
-    return launch_with_lds(kern, (int)grid, T::NW * 64, lds, st, a, "conv_dma2/split3/persistent");
+    static int occ[2] = {0, 0};          // blocks per CU of the two instantiations
+    int grid = 0;
+    const int rc = persistent_grid(kern, T::NW * 64, lds, tile_grid<T>(a), occ[a.padv ? 1 : 0], "conv split3 persistent", grid);
+    if (rc) return rc;
+    return launch_with_lds(kern, grid, T::NW * 64, lds, st, a, "conv_dma2/split3/persistent");
 }
 
 // the shapes whose persistent form has a producer variant (PEMP_CONV_OUT_SPLIT3): both -- 64 x 64 keeps its 128 registers

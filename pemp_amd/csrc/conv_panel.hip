@@ -12,9 +12,9 @@
 //    K step of BN weight rows in the S3 image of conv_dma2.hip (12 quads per row, same swizzle, same LDS-DMA), NS stages in a
 //    ring (panel_stages), the DMA of stage t + NS issued behind the barrier in the middle of stage t.  The K loop is MFMAs, B
 //    fragment reads and DMA issue: no A reads, no split;
-//  * per accumulator the order is K16 slices ascending, inside a slice lh, hl, mm, mh, hm, hh: BIT-IDENTICAL to ids 41..49 (the
+//  * per accumulator the order is K16 slices ascending, inside a slice split3_mma6's: BIT-IDENTICAL to ids 41..49 (the
 //    accumulators of one slice are interleaved product by product, so that consecutive MFMAs do not depend on each other);
-//  * the epilogue is conv_epilogue_lds_pre's arithmetic, statement for statement.  Its stores are buffer stores that are ALWAYS
+//  * the epilogue is PEMP_CONV_PATCH_PUT and conv_affine_quad on the patch's quads.  Its stores are buffer stores that are ALWAYS
 //    issued (a row >= M gets an offset behind the descriptor's range and is dropped), so that their number is a constant and the
 //    wait for a weight stage can be counted past them: they drain under the MFMAs of tile n + 1.
 // Vector memory operations of a wave retire in issue order (the persistent kernels of conv_dma2.hip count on the same), so the
@@ -117,7 +117,7 @@ __device__ __forceinline__ void conv_panel_body(const ConvArgs& a) {
 #pragma unroll
     for (int i = 0; i < BL; ++i) {
         const int q = i * NW * 64 + tid, row = q / 12, pos = q - row * 12;
-        const int src = (pos & ~3) | ((pos & 3) ^ ((row >> 2) & 3));
+        const int src = PEMP_SPLIT3_SWZ(row, pos);
         b_voff[i] = (unsigned)(row * a.Kpad * 6 + src * 16);
     }
     const int tile_bytes = BN * a.Kpad * 6;         // weight bytes of one N tile
@@ -173,7 +173,8 @@ __device__ __forceinline__ void conv_panel_body(const ConvArgs& a) {
             _Pragma("unroll") for (int pl = 0; pl < 3; ++pl)                                                      \
                 bfr[dst_][ni][pl] = Bb_[brow3 + ni * 32 * 12 + pl * 4 + pb_];                                     \
     } while (0)
-    // K16 slice s_: per accumulator lh, hl, mm, mh, hm, hh; the TN accumulators take turns.  HOOK_(j) follows MFMA j of the slice.
+    // K16 slice s_: product pr of split3_mma6's order (conv_common.h) for each of the TN accumulators in turn -- not a call of it: the
+    // accumulators take turns product by product, with HOOK_(j) behind MFMA j of the slice.
 #define PEMP_PANEL_MMA_HOOKED(src_, s_, HOOK_)                                                                    \
     do {                                                                                                          \
         _Pragma("unroll") for (int pr = 0; pr < 6; ++pr)                                                          \
@@ -275,30 +276,18 @@ __device__ __forceinline__ void conv_panel_body(const ConvArgs& a) {
             __builtin_amdgcn_sched_barrier(0);
             cur = nxt;
         }
-        // ---- epilogue of N tile n: conv_epilogue_lds_pre's arithmetic (EPI 0, no per-image shift, no DropBlock) ----
+        // ---- epilogue of N tile n: conv_epilogue_lds_pre's EPI 0 without a per-image shift, every store issued ----
 #pragma unroll
         for (int ni = 0; ni < TN; ++ni) {
-            const v4f sc = scv[ni], sh = shv[ni];
-#pragma unroll
-            for (int e = 0; e < 16; ++e) patch[((e & 3) + 8 * (e >> 2) + 4 * lh) * 32 + lr] = acc[ni][e];
+            PEMP_CONV_PATCH_PUT(patch, acc[ni], lr, lh);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // this wave's writes have landed (DS is in-order per wave)
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const int row = er + 8 * i;
                 const v4f v = *(const v4f*)(patch + row * 32 + c4);
-                v4f add = sh;
+                v4f add = shv[ni];
                 if (a.res) add += rres[ni * 4 + i];
-                v4f o;
-                o.x = __builtin_fmaf(v.x, sc.x, add.x);      // explicit: every epilogue variant must round identically
-                o.y = __builtin_fmaf(v.y, sc.y, add.y);
-                o.z = __builtin_fmaf(v.z, sc.z, add.z);
-                o.w = __builtin_fmaf(v.w, sc.w, add.w);
-                if (relu) {
-                    o.x = fmaxf(o.x, 0.f);
-                    o.y = fmaxf(o.y, 0.f);
-                    o.z = fmaxf(o.z, 0.f);
-                    o.w = fmaxf(o.w, 0.f);
-                }
+                const v4f o = conv_affine_quad(v, scv[ni], add, relu);
                 __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u, o), ry, y_off[i] + (unsigned)(n * BN + ni * 32) * 4u, 0, 0);
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // reads done before the patch is rewritten

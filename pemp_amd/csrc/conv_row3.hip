@@ -20,7 +20,7 @@
 //  * a reader applies the swizzle of the row it reads: position plane * 4 + (quad ^ ((row >> 2) & 3)) with row = s(m) + (kw - 1) d.
 //    The six fragment addresses per lane and K16 slice (2 row tiles x 3 kw) are computed once per tile.
 // Tile (256 x 128, 8 waves as 4 x 2 of 64 x 64), weights (pemp_pack_split3_bf16, the B swizzle), the order of the K16 slices per
-// accumulator (chunk, kh, kw ascending; inside a slice lh, hl, mm, mh, hm, hh) and the epilogue (conv_epilogue_lds) are those of
+// accumulator (chunk, kh, kw ascending; inside a slice split3_mma6's products) and the epilogue (conv_epilogue_lds) are those of
 // id 146: BIT-IDENTICAL to ids 146 / 149, and to id 43 on the fp32 tensor.
 //
 // Pipeline.  K step kt = 3 g + ph (group g, ph = kw).  B keeps its two-deep ring: B(kt + 2) goes out behind the barrier of step
@@ -39,8 +39,7 @@
 // Stages past the last one are still issued, with every offset out of range (zeros into a free buffer, no memory read): one form
 // of the step, constant counts.  They are drained (vmcnt(0) + barrier) before the transpose patches reuse the stage buffers.
 //
-// Persistent form (id 249): the tile walk of conv_dma2.hip's id 149 -- a resident grid, the blocks of XCD x share XCD x's range of
-// the M-major tile order, no counter, flag or atomic.  Groups and steps are numbered THROUGH the walk (the buffer of a group / step
+// Persistent form (id 249): the tile walk of conv_dma2.hip's id 149 (XcdTileRange, conv_common.h).  Groups and steps are numbered THROUGH the walk (the buffer of a group / step
 // is its running number's parity) and the (chunk, kh, kw) state wraps at the end of a tile, so the issue schedule above simply
 // runs on into the next tile: A(g + 1), A(g + 2) and B(kt + 2) of a tile's last groups ARE the next tile's first stages, issued
 // under its last steps with the next tile's offsets.  Those are exchanged in place where the current tile has issued its last
@@ -48,8 +47,8 @@
 // tails of ph 0 and ph 1 of the last group (after the block's last tile: every offset out of range).  What differs at a tile's end:
 //  * the last step issues nothing and reads no next fragments, and its barrier waits for the LDS reads only: the next tile's
 //    A(0) and B(0) fly on under the epilogue, whose patches go to the A buffer that step read;
-//  * the epilogue is conv_epilogue_s3p's (conv_dma2.hip) without its residual and per-image branches, statement for statement: the
-//    scale / shift quads in one batch behind the last MFMAs, the stores back to back;
+//  * the epilogue is conv_epilogue_s3p (conv_common.h) in its PLAIN form, without residual and per-image branches: the scale /
+//    shift quads in one batch behind the last MFMAs, the stores back to back;
 //  * B(1) and A(1) pieces 0..2 of the next tile -- the tail the last step did not issue; A(1) goes to the buffer the patches are
 //    in -- follow a barrier behind the epilogue, and the wait in front of the next tile's first MFMA counts past them and past the
 //    NST stores (a wave whose rows are not all inside M issues fewer stores and does not count them): vmcnt(row3_behind_first()
@@ -115,7 +114,7 @@ __global__ __launch_bounds__(ROW3_NW * 64) __attribute__((amdgpu_waves_per_eu(2)
 #pragma unroll
     for (int i = 0; i < AL; ++i) {
         const int q = i * NW * 64 + tid, srow = q / 12, pos = q - srow * 12;
-        const int src = (pos & ~3) | ((pos & 3) ^ ((srow >> 2) & 3));
+        const int src = PEMP_SPLIT3_SWZ(srow, pos);
         const int t = srow + c0, rr = t / Wd, cc = t - rr * Wd;
         const int f = (R0 + rr) * W + cc;
         const bool pix = srow < ROW3_SR && cc < W && f >= 0 && f < a.M && f < m0 + BM + d;
@@ -128,7 +127,7 @@ __global__ __launch_bounds__(ROW3_NW * 64) __attribute__((amdgpu_waves_per_eu(2)
 #pragma unroll
     for (int i = 0; i < BL; ++i) {
         const int q = i * NW * 64 + tid, row = q / 12, pos = q - row * 12;
-        const int src = (pos & ~3) | ((pos & 3) ^ ((row >> 2) & 3));
+        const int src = PEMP_SPLIT3_SWZ(row, pos);
         b_voff[i] = (unsigned)((n0 + row) * a.Kpad * 6 + src * 16);
     }
     const int taph = d * W * rowb;
@@ -189,7 +188,7 @@ __global__ __launch_bounds__(ROW3_NW * 64) __attribute__((amdgpu_waves_per_eu(2)
                 bf3[dst_][ni][pl] = Bb_[brow3 + ni * 32 * 12 + pl * 4 + pb_];                                     \
     } while (0)
 
-    // the six products of a K16 slice, conv_dma2.hip's PEMP_MMA (S3, A3) statement for statement
+    // the K16 slice in registers src_: every accumulator's six products (split3_mma6)
 #define PEMP_ROW3_MMA(src_)                                                                                       \
     do {                                                                                                          \
         _Pragma("unroll") for (int mi = 0; mi < TM; ++mi) _Pragma("unroll") for (int ni = 0; ni < TN; ++ni) {     \
@@ -199,12 +198,7 @@ __global__ __launch_bounds__(ROW3_NW * 64) __attribute__((amdgpu_waves_per_eu(2)
             const bf16x8 bh_ = __builtin_bit_cast(bf16x8, bf3[src_][ni][0]);                                      \
             const bf16x8 bm_ = __builtin_bit_cast(bf16x8, bf3[src_][ni][1]);                                      \
             const bf16x8 bl_ = __builtin_bit_cast(bf16x8, bf3[src_][ni][2]);                                      \
-            acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al_, bh_, acc[mi][ni], 0, 0, 0);                \
-            acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah_, bl_, acc[mi][ni], 0, 0, 0);                \
-            acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am_, bm_, acc[mi][ni], 0, 0, 0);                \
-            acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am_, bh_, acc[mi][ni], 0, 0, 0);                \
-            acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah_, bm_, acc[mi][ni], 0, 0, 0);                \
-            acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah_, bh_, acc[mi][ni], 0, 0, 0);                \
+            split3_mma6(acc[mi][ni], ah_, am_, al_, bh_, bm_, bl_);                                               \
         }                                                                                                         \
     } while (0)
 
@@ -274,48 +268,6 @@ __global__ __launch_bounds__(ROW3_NW * 64) __attribute__((amdgpu_waves_per_eu(2)
 #endif
 }
 
-// conv_epilogue_s3p (conv_dma2.hip) without its residual and per-image branches (the entry refuses both), statement for statement
-template <int TM, int TN>
-__device__ __forceinline__ void conv_row3_epilogue(const ConvArgs& a, f32x16 (&acc)[TM][TN], float* S, int m_base, int n_base, int lane,
-                                                   const v4f (&scv)[TN], const v4f (&shv)[TN]) {
-    const bool relu = a.flags & PEMP_CONV_RELU;
-    const int lr = lane & 31, lh = lane >> 5;
-    const int rr = lane >> 3, c4 = (lane & 7) * 4;
-#pragma unroll
-    for (int ni = 0; ni < TN; ++ni) {
-        const int n = n_base + ni * 32 + c4;
-        const v4f sc = scv[ni], sh = shv[ni];
-#pragma unroll
-        for (int mi = 0; mi < TM; ++mi) {
-#pragma unroll
-            for (int e = 0; e < 16; ++e) S[((e & 3) + 8 * (e >> 2) + 4 * lh) * 32 + lr] = acc[mi][ni][e];
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // this wave's writes have landed (DS is in-order per wave)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int row = rr + 8 * i;
-                const int m = m_base + mi * 32 + row;
-                const v4f v = *(const v4f*)(S + row * 32 + c4);
-                if (m < a.M) {
-                    const v4f add = sh;
-                    v4f o;
-                    o.x = __builtin_fmaf(v.x, sc.x, add.x);      // explicit: every epilogue variant must round identically
-                    o.y = __builtin_fmaf(v.y, sc.y, add.y);
-                    o.z = __builtin_fmaf(v.z, sc.z, add.z);
-                    o.w = __builtin_fmaf(v.w, sc.w, add.w);
-                    if (relu) {
-                        o.x = fmaxf(o.x, 0.f);
-                        o.y = fmaxf(o.y, 0.f);
-                        o.z = fmaxf(o.z, 0.f);
-                        o.w = fmaxf(o.w, 0.f);
-                    }
-                    store_quad(a.y, (size_t)m * a.ldy + n, o, 0);
-                }
-            }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // reads done before the patch is rewritten
-        }
-    }
-}
-
 // the persistent form (id 249; file header)
 __global__ __launch_bounds__(ROW3_NW * 64) __attribute__((amdgpu_waves_per_eu(2))) void conv_row3p_kernel(ConvArgs a) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -337,17 +289,12 @@ __global__ __launch_bounds__(ROW3_NW * 64) __attribute__((amdgpu_waves_per_eu(2)
     const int wm0 = (wave / WGN) * WM, wn0 = (wave % WGN) * WN;
     const int lr = lane & 31, lh = lane >> 5;
 
-    // the block's tile sequence (conv_dma2_s3p_body's): tiles [t_first + j] of its XCD's range, j = idx, idx + gx, ... < t_cnt
+    // the block's tile sequence: tiles tr.first + j, j = tr.idx, tr.idx + tr.step, ... < tr.count
     const int ntn = a.Cout / BN;
-    const int T = (a.M + BM - 1) / BM * ntn;
-    const int xcd = (int)blockIdx.x & 7, idx = (int)blockIdx.x >> 3;
-    const int q8 = T >> 3, r8 = T & 7;
-    const int t_first = xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8;
-    const int t_cnt = q8 + (xcd < r8 ? 1 : 0);
-    const int gx = ((int)gridDim.x - xcd + 7) >> 3;
-    if (idx >= t_cnt) return;                   // (the launch clamps the grid to the tile count: not expected)
-    int j = idx;
-    int m0 = ((t_first + j) / ntn) * BM, n0 = ((t_first + j) % ntn) * BN;
+    const XcdTileRange tr((a.M + BM - 1) / BM * ntn, (int)blockIdx.x, (int)gridDim.x);
+    if (tr.idx >= tr.count) return;             // (the launch clamps the grid to the tile count: not expected)
+    int j = tr.idx;
+    int m0 = ((tr.first + j) / ntn) * BM, n0 = ((tr.first + j) % ntn) * BN;
 
     const int d = a.dil, W = a.W, Wd = W + d;
     const int rowb = a.ldx * 6;
@@ -365,7 +312,7 @@ __global__ __launch_bounds__(ROW3_NW * 64) __attribute__((amdgpu_waves_per_eu(2)
 #pragma unroll
         for (int i = 0; i < AL; ++i) {
             const int q = i * NW * 64 + tid, srow = q / 12, pos = q - srow * 12;
-            const int src = (pos & ~3) | ((pos & 3) ^ ((srow >> 2) & 3));
+            const int src = PEMP_SPLIT3_SWZ(srow, pos);
             const int t = srow + c0, rr = t / Wd, cc = t - rr * Wd;
             const int f = (R0 + rr) * W + cc;
             const bool pix = ok_ && srow < ROW3_SR && cc < W && f >= 0 && f < a.M && f < m0_ + BM + d;
@@ -380,7 +327,7 @@ __global__ __launch_bounds__(ROW3_NW * 64) __attribute__((amdgpu_waves_per_eu(2)
 #pragma unroll
         for (int i = 0; i < BL; ++i) {
             const int q = i * NW * 64 + tid, row = q / 12, pos = q - row * 12;
-            const int src = (pos & ~3) | ((pos & 3) ^ ((row >> 2) & 3));
+            const int src = PEMP_SPLIT3_SWZ(row, pos);
             b_voff[i] = ok_ ? (unsigned)((n0_ + row) * a.Kpad * 6 + src * 16) : 0x80000000u;
         }
     };
@@ -429,9 +376,9 @@ __global__ __launch_bounds__(ROW3_NW * 64) __attribute__((amdgpu_waves_per_eu(2)
             for (int ni = 0; ni < TN; ++ni)
 #pragma unroll
                 for (int e = 0; e < 16; ++e) acc[mi][ni][e] = 0.f;
-        const int jn = j + gx;
-        const bool more = jn < t_cnt;
-        const int m0n = more ? ((t_first + jn) / ntn) * BM : m0, n0n = more ? ((t_first + jn) % ntn) * BN : n0;
+        const int jn = j + tr.step;
+        const bool more = jn < tr.count;
+        const int m0n = more ? ((tr.first + jn) / ntn) * BM : m0, n0n = more ? ((tr.first + jn) % ntn) * BN : n0;
         reader(m0);
 
         PEMP_ROW3_READ(0, gg & 1, gg & 1, 0, 0);
@@ -484,7 +431,7 @@ __global__ __launch_bounds__(ROW3_NW * 64) __attribute__((amdgpu_waves_per_eu(2)
             shv[ni] = a.shift ? *(const v4f*)(a.shift + n) : v4f{0.f, 0.f, 0.f, 0.f};
         }
         static_assert(NW * 256 <= ROW3_AQ, "one 4 KB transpose patch per wave inside ONE stage buffer");
-        conv_row3_epilogue<TM, TN>(a, acc, (float*)(As + abl * ROW3_AQ + wave * 256), m0 + wm0, n0 + wn0, lane, scv, shv);
+        conv_epilogue_s3p<TM, TN, true>(a, acc, (float*)(As + abl * ROW3_AQ + wave * 256), m0 + wm0, n0 + wn0, lane, nullptr, scv, shv);
         if (!more) {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // no LDS-DMA outlives the block
             break;
@@ -542,23 +489,11 @@ int launch_conv_row3(bool persistent, const ConvArgs& a, hipStream_t st) {
     }
     const int tiles = cdiv(a.M, ROW3_BM) * (a.Cout / ROW3_BN);
     if (!persistent) return launch_with_lds(conv_row3_kernel, tiles, ROW3_NW * 64, row3_lds(), st, a, "conv_row3");
-    // grid = resident blocks (occupancy x CUs, taken once), at most the tile count: launch_dma2_s3p's rule (conv_dma2.hip)
-    static int occ = 0;                  // (racing fills write the same value)
-    if (!occ) {
-        const int rc = allow_lds(conv_row3p_kernel, row3_lds());       // the occupancy query wants what the launch will have
-        if (rc) return rc;
-        int v = 0;
-        hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, (const void*)conv_row3p_kernel, ROW3_NW * 64, row3_lds());
-        if (e != hipSuccess || v <= 0) {
-            set_error("conv split3 row3 persistent: occupancy query failed (%s, %d blocks)", hipGetErrorString(e), v);
-            return -1;
-        }
-        occ = v;
-    }
-    long long grid = (long long)occ * (conv_dma2_simds() / 4);
-    if (grid < 8) grid = 8;              // every XCD's range needs a block
-    if (grid > tiles) grid = tiles;
-    return launch_with_lds(conv_row3p_kernel, (int)grid, ROW3_NW * 64, row3_lds(), st, a, "conv_row3/persistent");
+    static int occ = 0;
+    int grid = 0;
+    const int rc = persistent_grid(conv_row3p_kernel, ROW3_NW * 64, row3_lds(), tiles, occ, "conv split3 row3 persistent", grid);
+    if (rc) return rc;
+    return launch_with_lds(conv_row3p_kernel, grid, ROW3_NW * 64, row3_lds(), st, a, "conv_row3/persistent");
 }
 
 }  // namespace pemp

@@ -14,11 +14,11 @@
 // v_mfma_f32_32x32x16_bf16 each: lane half lh of slice s feeds taps 8 kt + 4 s + 2 lh, + 1.  The weights come from
 // pemp_pack_split3_bf16 (192 bytes per row and K step), one K step per stage buffer, double buffered; LDS image, swizzle and
 // fragment reads are conv_dma2.hip's.  Every accumulator sees the slices in ascending K order and per slice the six products in
-// the family's order (lh, hl, mm, mh, hm, hh), so the result does not depend on tile, batch or grid.  Taps 49..55 are padding
+// the family's order (split3_mma6), so the result does not depend on tile, batch or grid.  Taps 49..55 are padding
 // (zero weights); the activations fed for them are zeros, and the last slice (taps 52..55: nothing but padding) is not issued.
 //
-// Epilogue.  scale / shift / ReLU on the accumulators (conv_epilogue_lds_pre's expression: fmaf(v, scale, shift), then max with
-// 0), the 17 x 17 x 64 fp32 conv patch goes to LDS over the operand buffers, and every thread takes the maximum of the IN-IMAGE
+// Epilogue.  scale / shift / ReLU on the accumulators (conv_affine_quad's rule, conv_common.h, per scalar: lane = channel),
+// the 17 x 17 x 64 fp32 conv patch goes to LDS over the operand buffers, and every thread takes the maximum of the IN-IMAGE
 // conv pixels of one pool window for four channels (a pixel outside the conv's Ho x Wo is skipped by its coordinates, never read
 // as a value) and stores one 16-byte quad: 16 lanes = the 256 contiguous bytes of a pooled pixel.
 #include "conv_common.h"
@@ -85,7 +85,7 @@ __global__ __launch_bounds__(SP_NW * 64) void conv_stem_pool_kernel(ConvArgs a, 
 #define PEMP_SP_DMA_B(kt_, buf_)                                                                                  \
     for (int i = wave; i < SP_BQ / 64; i += SP_NW) {                                                              \
         const int q = i * 64 + lane, row = q / 12, pos = q - row * 12;                                            \
-        const int src = (pos & ~3) | ((pos & 3) ^ ((row >> 2) & 3));                                              \
+        const int src = PEMP_SPLIT3_SWZ(row, pos);                                                                \
         const unsigned vo = (unsigned)((n0 + row) * a.Kpad * 6 + src * 16);                                       \
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (lptr_t)(Bs + (buf_) * SP_BQ + i * 64), 16, vo, (kt_) * 192, 0, 0); \
     }
@@ -130,12 +130,7 @@ __global__ __launch_bounds__(SP_NW * 64) void conv_stem_pool_kernel(ConvArgs a, 
                 const bf16x8 bh = __builtin_bit_cast(bf16x8, Bb[ni * 32 * 12 + pb]);
                 const bf16x8 bm = __builtin_bit_cast(bf16x8, Bb[ni * 32 * 12 + 4 + pb]);
                 const bf16x8 bl = __builtin_bit_cast(bf16x8, Bb[ni * 32 * 12 + 8 + pb]);
-                acc[ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc[ni], 0, 0, 0);
-                acc[ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc[ni], 0, 0, 0);
-                acc[ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bm, acc[ni], 0, 0, 0);
-                acc[ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bh, acc[ni], 0, 0, 0);
-                acc[ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bm, acc[ni], 0, 0, 0);
-                acc[ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc[ni], 0, 0, 0);
+                split3_mma6(acc[ni], ah, am, al, bh, bm, bl);
             }
         }
     }
