@@ -40,6 +40,12 @@ extern "C" {
 #define PEMP_CONV_IN_SPLIT3 32u    /* x is such a tensor (tile ids 146 / 149 only)                                            */
 #define PEMP_CONV_OUT_SPLIT3_ALSO 64u /* y is written as fp32 as usual AND the same values pre-split, through the pointer passed as
                                       `residual`: no residual is read (tile ids 146 / 149, pemp_conv2d_nhwc_f32 / _padv_ only)   */
+#define PEMP_CONV_RES_S2 128u      /* the residual lies on a grid TWICE AS FINE as the output: an NHWC tensor [N][Hr][Wr] with
+                                      per-pixel stride ldr, output row (n, ho, wo) adds its pixel (n, 2 ho, 2 wo); Ho = (Hr - 1) / 2
+                                      + 1, Wo likewise (see "Strided residual" below; tile ids 43, 71, 72, pemp_conv2d_nhwc_f32 only) */
+/* 256u is taken inside the library (the bf16 entry's internal flag) */
+#define PEMP_CONV_RES_HEVEN 512u   /* with PEMP_CONV_RES_S2: Hr is even -- Hr = 2 Ho - 1 + (this bit set)                        */
+#define PEMP_CONV_RES_WEVEN 1024u  /* ... and Wr = 2 Wo - 1 + (this bit set)                                                     */
 
 typedef struct pemp_conv_desc {
     int32_t N, H, W;        /* input images, input spatial size                                  */
@@ -169,6 +175,15 @@ int pemp_conv2d_group_nhwc_f32(int n, const pemp_conv_desc* d, const float* cons
  *   is read.  Compile-time variants: conv_dma2_a3o_kernel (146) and conv_dma2_a3po_kernel<..., 2> (149).  Refused with
  *   PEMP_CONV_OUT_SPLIT3, split-K, a workspace, the grouped / DropBlock / statistics / bf16 entries, the stem and every other tile
  *   id (the panel ids included), and when the two outputs overlap.
+ * Strided residual (PEMP_CONV_RES_S2 with PEMP_CONV_RES_HEVEN / _WEVEN; pemp_conv2d_nhwc_f32 only).  A bottleneck whose output is
+ *   read by stride-2 1x1 convs alone needs only the rows on the even grid; its last conv then runs on the compact Ho x Wo grid
+ *   while the shortcut it adds still lies on the full Hr x Wr one.  With the flag `residual` is that tensor, [N][Hr][Wr] with
+ *   per-pixel stride ldr, and output row (n, ho, wo) adds the Cout channels of its pixel (n, 2 ho, 2 wo); Hr = 2 Ho - 1 + HEVEN,
+ *   Wr = 2 Wo - 1 + WEVEN, N * Hr * Wr * ldr below 2^31 elements.  Same dot products, same epilogue arithmetic: bit-identical to
+ *   the same id on the gathered dense residual.  Compile-time variants of two kernels take it: conv_panel_rs2_kernel (id 72 at
+ *   Kpad 64 or 128, id 71 at Kpad 64) and conv_dma2_rs2_kernel (id 43, any M).  Everything else refuses it, never reads it as dense: the
+ *   persistent ids 47 / 49, the other split3 ids, split-K and a workspace, a padding value, the stem, PEMP_CONV_OUT_SPLIT3 /
+ *   _IN_SPLIT3 / _OUT_SPLIT3_ALSO, the fp32-chain ids (0 included), and the grouped / DropBlock / statistics / bf16 entries.
  * pemp_pack_split3_bf16: [Cout][Kpad] fp32 (Kpad % 32 == 0) -> [Cout][Kpad / 32][3][32] bf16 (Cout * Kpad * 6 bytes): per row and
  * 32-channel K step the h, m and l planes, channel order unchanged.                                                           */
 int pemp_pack_split3_bf16(const float* w, void* out, int cout, int kpad, void* stream);

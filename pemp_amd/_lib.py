@@ -38,6 +38,9 @@ CONV_POOL3S2 = 8
 CONV_OUT_SPLIT3 = 16
 CONV_IN_SPLIT3 = 32
 CONV_OUT_SPLIT3_ALSO = 64
+CONV_RES_S2 = 128           # (256 is taken inside the library)
+CONV_RES_HEVEN = 512
+CONV_RES_WEVEN = 1024
 
 #: every symbol include/pemp_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {

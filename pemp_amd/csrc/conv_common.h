@@ -126,7 +126,19 @@ struct ConvArgs {
     unsigned flags;
     int M, HoWo, cin_steps, nk, ntaps;
     int bm_first = 0;       // conv_dma2.hip: the launch's first row tile (in units of its BM; 0 except in the hybrid launch's second member)
+    int Hr = 0, Wr = 0;     // PEMP_CONV_RES_S2: the residual's own grid [N][Hr][Wr] (0: dense, the residual lies on the output grid)
 };
+
+// PEMP_CONV_RES_S2: the residual pixel of output row m = (img, ho, wo) -- pixel (img, 2 ho, 2 wo) of the [N][Hr][Wr] grid; its
+// element offset is this times ldr.  (101 != 2 x 51: not affine in m, so no ldr fakes it.  The kernels that take the flag do this
+// once per row they own, as a compile-time variant: conv_panel.hip and conv_dma2.hip, RS2.)
+__device__ __forceinline__ int conv_res_s2_pixel(const ConvArgs& a, int m) {
+    const int img = m / a.HoWo;
+    const int rem = m - img * a.HoWo;
+    const int ho = rem / a.Wo;
+    const int wo = rem - ho * a.Wo;
+    return (img * a.Hr + 2 * ho) * a.Wr + 2 * wo;
+}
 
 // up to CONV_GROUP_MAX independent convs of one tile shape in one launch (conv_dma2.hip: conv_dma2_group_kernel)
 constexpr int CONV_GROUP_MAX = 4;

@@ -63,7 +63,7 @@ typedef __attribute__((address_space(3))) void* lptr_t;
 // pre-split padding vector), three 16-byte fragment reads per half step that go straight into the MFMAs.  No split3_bf16 in the K
 // loop; MFMA order, accumulators and epilogue are S3's, and the pieces are those split3_bf16 would have made: bit-identical.
 template <int BM, int BN, int WGM, int NW, bool PADV, int EPI = 0, bool SK = false, bool BF16 = false, bool DB = false, bool R16 = false,
-          bool S3 = false, bool A3 = false, bool ALSO = false>
+          bool S3 = false, bool A3 = false, bool ALSO = false, bool RS2 = false>
 __device__ __forceinline__ void conv_dma2_body(const ConvArgs& a, const int bid, const int nblk) {
 #if defined(__HIP_DEVICE_COMPILE__)     // the host pass only needs the launch stub (buffer-resource builtins / "s" asm operands are device-only)
     constexpr int WGN = NW / WGM;
@@ -440,6 +440,9 @@ __device__ __forceinline__ void conv_dma2_body(const ConvArgs& a, const int bid,
     // the epilogue where every tile would wait out a full memory latency between its LDS transpose and its stores.
     constexpr bool PRE = !R16 && TM * TN <= 2;
     static_assert(!ALSO || !PRE, "ALSO: a.res is no residual");
+    // RS2 (PEMP_CONV_RES_S2; conv_dma2_rs2_kernel): the residual lies on a grid twice as fine as the output -- the prefetch below is
+    // the one place of this body that addresses it, so the variant is this prefetch with conv_res_s2_pixel for the row
+    static_assert(!RS2 || (PRE && S3 && !A3 && !SK && !PADV && EPI == 0), "RS2: the prefetched residual of the plain unsplit S3 form");
     v4f rpre[PRE ? TM * TN * 4 : 1];
 #pragma unroll
     for (int i = 0; i < (PRE ? TM * TN * 4 : 1); ++i) rpre[i] = v4f{0.f, 0.f, 0.f, 0.f};
@@ -453,7 +456,8 @@ __device__ __forceinline__ void conv_dma2_body(const ConvArgs& a, const int bid,
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
                         const int m = m0 + wm0 + mi * 32 + rr_ + 8 * i, n = n0 + wn0 + ni * 32 + c4_;
-                        rpre[(mi * TN + ni) * 4 + i] = m < a.M ? load_quad(a.res, (size_t)m * a.ldr + n, a.flags & PEMP_CONV_BF16_IO) : v4f{0.f, 0.f, 0.f, 0.f};
+                        if constexpr (RS2) rpre[(mi * TN + ni) * 4 + i] = m < a.M ? *(const v4f*)(a.res + (size_t)conv_res_s2_pixel(a, m) * a.ldr + n) : v4f{0.f, 0.f, 0.f, 0.f};
+                        else rpre[(mi * TN + ni) * 4 + i] = m < a.M ? load_quad(a.res, (size_t)m * a.ldr + n, a.flags & PEMP_CONV_BF16_IO) : v4f{0.f, 0.f, 0.f, 0.f};
                     }
         }
     }
@@ -585,6 +589,13 @@ template <int BM, int BN, int WGM, int NW, bool PADV, int EPI = 0, bool SK = fal
           bool S3 = false>
 __global__ __launch_bounds__(NW * 64) void conv_dma2_kernel(ConvArgs a) {
     conv_dma2_body<BM, BN, WGM, NW, PADV, EPI, SK, BF16, DB, R16, S3>(a, blockIdx.x, gridDim.x);
+}
+
+// the plain split3 form with a strided residual (PEMP_CONV_RES_S2; a kernel of its own: the instantiations of conv_dma2_kernel keep
+// their names and their code).  Instantiated for id 43's shape: the one-tile id that serves any M
+template <int BM, int BN, int WGM, int NW>
+__global__ __launch_bounds__(NW * 64) void conv_dma2_rs2_kernel(ConvArgs a) {
+    conv_dma2_body<BM, BN, WGM, NW, false, 0, false, false, false, false, true, false, false, true>(a, blockIdx.x, gridDim.x);
 }
 
 // ---- persistent split3 form (tile ids 47, 49 = the shapes of 43, 46; pemp_hip.h).  (41's shape, 128 x 128 in 4 waves, needs
@@ -1090,6 +1101,15 @@ int launch_conv_dma2_split3(int shape, ConvArgs a, void* ws, size_t ws_bytes, bo
     const SplitKPlan p = split ? conv_dma2_splitk_plan(shape, a) : SplitKPlan{0, 0, 1, 0};
     const int sk_grid = p.pieces >= 2 ? bind_splitk(a, p, ws, ws_bytes) : 0;
     if (sk_grid < 0) return -1;
+    if (a.flags & PEMP_CONV_RES_S2) {    // the residual on a grid twice as fine: id 43's shape, unsplit, zero padding
+        if (shape != 3 || split || a.padv || !a.res || a.Hr < 1 || a.Wr < 1) {
+            set_error("conv split3: PEMP_CONV_RES_S2 needs the 64 x 64 tile (id 43), unsplit, with a residual and no padding value");
+            return -1;
+        }
+        using T = Tile<3, true>;
+        return launch_with_lds(conv_dma2_rs2_kernel<T::BM, T::BN, T::WGM, T::NW>, tile_grid<T>(a), T::NW * 64, tile_lds_s3<T>(), st, a,
+                               "conv_dma2/split3/res_s2");
+    }
     return with_tile<FamSplit3>(shape, [&](auto t) {
         using T = decltype(t);
         auto kern = sk_grid ? (a.padv ? dma2_kernel<T, true, 0, true, false, false, false, true> : dma2_kernel<T, false, 0, true, false, false, false, true>)

@@ -283,6 +283,8 @@ static int conv_fill(const pemp_conv_desc* d, const float* x, const float* w, fl
     PEMP_REQUIRE(pooled || !(d->flags & (PEMP_CONV_OUT_SPLIT3 | PEMP_CONV_IN_SPLIT3 | PEMP_CONV_OUT_SPLIT3_ALSO)),
                  "conv2d: pre-split activations belong to pemp_conv2d_nhwc_f32 / _padv_ (no grouped / dropblock / statistics / bf16 form)");
     PEMP_REQUIRE(pooled || !(d->flags & PEMP_CONV_POOL3S2), "conv2d: PEMP_CONV_POOL3S2 belongs to pemp_conv2d_nhwc_f32 (no grouped / dropblock / statistics / bf16 form)");
+    PEMP_REQUIRE(pooled || !(d->flags & (PEMP_CONV_RES_S2 | PEMP_CONV_RES_HEVEN | PEMP_CONV_RES_WEVEN)),
+                 "conv2d: PEMP_CONV_RES_S2 belongs to pemp_conv2d_nhwc_f32 (no grouped / dropblock / statistics / bf16 form)");
     PEMP_REQUIRE(!pad_value || (!(d->flags & PEMP_CONV_STEM4) && (any_taps || d->KH * d->KW > 1) && ((uintptr_t)pad_value & 15) == 0),
                  "conv2d: pad_value needs a multi-tap non-stem conv and a 16-byte aligned [Cin] vector");
     PEMP_REQUIRE(d->N > 0 && d->H > 0 && d->W > 0 && d->Cin > 0 && d->Cout > 0, "conv2d: bad dims");
@@ -357,6 +359,21 @@ static int conv2d_impl(const pemp_conv_desc* d, const float* x, const float* w, 
         const char *y0 = (const char*)y, *y1 = y0 + ((size_t)(a.M - 1) * a.ldy + a.Cout) * 4;
         const char *s0 = (const char*)residual, *s1 = s0 + (size_t)a.M * a.Cout * 6;
         PEMP_REQUIRE(y1 <= s0 || s1 <= y0, "conv2d: PEMP_CONV_OUT_SPLIT3_ALSO: y and the pre-split tensor overlap");
+    }
+    // the residual on a grid twice as fine, [N][Hr][Wr] (row (n, ho, wo) adds pixel (n, 2 ho, 2 wo)): compile-time variants of ids
+    // 71 / 72 at Kpad 64 / 128 (conv_panel_rs2_kernel) and of id 43 (conv_dma2_rs2_kernel); nothing else reads a residual that way
+    const bool res_s2 = d->flags & PEMP_CONV_RES_S2;
+    PEMP_REQUIRE(res_s2 || !(d->flags & (PEMP_CONV_RES_HEVEN | PEMP_CONV_RES_WEVEN)), "conv2d: PEMP_CONV_RES_HEVEN / _WEVEN come with PEMP_CONV_RES_S2");
+    if (res_s2) {
+        PEMP_REQUIRE(residual && !out_split3 && !also_split3 && !(d->flags & PEMP_CONV_IN_SPLIT3) && !ws && !stem && !pad_value,
+                     "conv2d: PEMP_CONV_RES_S2 needs a residual, no pre-split operands / PEMP_CONV_OUT_SPLIT3_ALSO / split-K / workspace / stem / padding value");
+        PEMP_REQUIRE(t.family == TILE_SPLIT3 && t.exists && !t.splitk && !t.persistent && !t.presplit &&
+                         (t.panel ? (a.nk == 2 || (a.nk == 4 && t.shape == 2)) : t.shape == 3),
+                     "conv2d: PEMP_CONV_RES_S2 needs tile id 43, 72 with Kpad 64 or 128, or 71 with Kpad 64 (tile %d, Kpad %d: the persistent, split-K, "
+                     "pre-split and fp32-chain ids have no strided-residual form)", tile, a.Kpad);
+        a.Hr = 2 * a.Ho - 1 + ((d->flags & PEMP_CONV_RES_HEVEN) ? 1 : 0);
+        a.Wr = 2 * a.Wo - 1 + ((d->flags & PEMP_CONV_RES_WEVEN) ? 1 : 0);
+        PEMP_REQUIRE((long long)a.N * a.Hr * a.Wr * a.ldr < (1ll << 31), "conv2d: PEMP_CONV_RES_S2: residual too large for 32-bit indexing");
     }
     if (d->flags & PEMP_CONV_POOL3S2) {     // the fused stem (conv_stem_pool.hip): y is the pooled tensor
         PEMP_REQUIRE(stem && t.family == TILE_SPLIT3 && !t.splitk && !t.panel && !residual && !pad_value,
@@ -534,7 +551,7 @@ extern "C" int pemp_conv2d_bf16_nhwc(const pemp_conv_desc* d, const void* x, con
 static TileId stats_tile(const pemp_conv_desc* d) { return decode_tile(d->tile == 0 ? 23 : d->tile); }
 
 static int conv_stats_fill(const char* what, const pemp_conv_desc* d, ConvArgs& a) {
-    PEMP_REQUIRE(!(d->flags & (PEMP_CONV_STEM4 | PEMP_CONV_RELU | PEMP_CONV_SHIFT_PER_IMAGE | PEMP_CONV_POOL3S2 | PEMP_CONV_OUT_SPLIT3 | PEMP_CONV_IN_SPLIT3 | PEMP_CONV_OUT_SPLIT3_ALSO)), "%s: plain conv only (no stem / ReLU / per-image shift)", what);
+    PEMP_REQUIRE(!(d->flags & (PEMP_CONV_STEM4 | PEMP_CONV_RELU | PEMP_CONV_SHIFT_PER_IMAGE | PEMP_CONV_POOL3S2 | PEMP_CONV_OUT_SPLIT3 | PEMP_CONV_IN_SPLIT3 | PEMP_CONV_OUT_SPLIT3_ALSO | PEMP_CONV_RES_S2 | PEMP_CONV_RES_HEVEN | PEMP_CONV_RES_WEVEN)), "%s: plain conv only (no stem / ReLU / per-image shift)", what);
     PEMP_REQUIRE(d->N > 0 && d->H > 0 && d->W > 0 && d->Cin > 0 && d->Cout > 0 && d->KH > 0 && d->KW > 0 && d->stride > 0 && d->dil > 0 && d->pad >= 0,
                  "%s: bad geometry", what);
     const int ho = (d->H + 2 * d->pad - d->dil * (d->KH - 1) - 1) / d->stride + 1;

@@ -82,7 +82,10 @@ __device__ __forceinline__ void panel_wait(int kt) {
     }
 }
 
-template <int NK, int BN, int NW>
+// RS2 (PEMP_CONV_RES_S2, a compile-time variant: conv_panel_rs2_kernel): the residual lies on a grid twice as fine as the output.
+// A lane's four epilogue rows are the same for every N tile, so their residual pixels (conv_res_s2_pixel) are worked out once per
+// block, where the dense form multiplies the row by ldr; the K loop and the epilogue are the dense form's.
+template <int NK, int BN, int NW, bool RS2 = false>
 __device__ __forceinline__ void conv_panel_body(const ConvArgs& a) {
 #if defined(__HIP_DEVICE_COMPILE__)
     constexpr int TN = BN / 32;
@@ -219,7 +222,8 @@ __device__ __forceinline__ void conv_panel_body(const ConvArgs& a) {
     for (int i = 0; i < 4; ++i) {
         const int m = m_wave + er + 8 * i;
         y_off[i] = m < a.M ? (unsigned)(m * a.ldy + c4) * 4u : 0x80000000u;
-        r_off[i] = m < a.M ? (unsigned)(m * a.ldr + c4) * 4u : 0x80000000u;
+        if constexpr (RS2) r_off[i] = m < a.M ? (unsigned)(conv_res_s2_pixel(a, m) * a.ldr + c4) * 4u : 0x80000000u;
+        else r_off[i] = m < a.M ? (unsigned)(m * a.ldr + c4) * 4u : 0x80000000u;
     }
 
     // the scale / shift quads of N tile n_
@@ -316,6 +320,13 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(panel_t
     conv_panel_body<NK, BN, NW>(a);
 }
 
+// the strided-residual variant (a kernel of its own: the instantiations of conv_panel_kernel keep their names and their code);
+// K = 64 and 128 only, the two-blocks-per-CU forms included
+template <int NK, int BN, int NW>
+__global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(panel_two_blocks<NK, BN>() ? 2 : 1))) void conv_panel_rs2_kernel(ConvArgs a) {
+    conv_panel_body<NK, BN, NW, true>(a);
+}
+
 constexpr int PANEL_NW = 4;
 template <int NK, int BN> constexpr size_t panel_lds() { return (size_t)(panel_stages<NK, BN>() * BN * 12 + PANEL_NW * 256) * sizeof(v4f); }
 static_assert(panel_lds<8, 128>() <= 160 * 1024 && 2 * panel_lds<4, 64>() <= 160 * 1024, "LDS of a CU");
@@ -333,21 +344,40 @@ static int launch_panel_nk(const ConvArgs& a, hipStream_t st) {
     }
 }
 
+template <int BN, int NK>
+static int launch_panel_rs2(const ConvArgs& a, hipStream_t st) {
+    return launch_with_lds(conv_panel_rs2_kernel<NK, BN, PANEL_NW>, cdiv(a.M, 32 * PANEL_NW), PANEL_NW * 64, panel_lds<NK, BN>(), st, a,
+                           "conv_panel/res_s2");
+}
+
 // what the family takes: 1x1, no padding, Kpad <= 256, plain epilogue without a per-image shift, operands whose byte offsets fit
-// the 2 GiB window of a buffer descriptor
+// the 2 GiB window of a buffer descriptor (a strided residual: all of its own grid); PEMP_CONV_RES_S2 at Kpad 64 and 128 only
 bool conv_panel_supported(const ConvArgs& a) {
     if (a.KH != 1 || a.KW != 1 || a.pad != 0 || a.nk < 1 || a.nk > 8 || a.Kpad != a.Cin || (a.flags & (PEMP_CONV_STEM4 | PEMP_CONV_SHIFT_PER_IMAGE | PEMP_CONV_BF16_IO)))
         return false;
     if (a.padv || a.stats || a.rowmask || a.sk_S > 1 || a.bm_first) return false;
+    const bool rs2 = a.flags & PEMP_CONV_RES_S2;
+    if (rs2 && (!a.res || a.Hr < 1 || a.Wr < 1 || (a.nk != 2 && a.nk != 4))) return false;      // (launch_conv_panel: 128 columns at K = 64 only)
     const long long lim = 1ll << 31;
-    return (long long)a.N * a.H * a.W * a.ldx * 4 < lim && (long long)a.M * a.ldy * 4 < lim && (!a.res || (long long)a.M * a.ldr * 4 < lim) &&
+    const long long res_rows = rs2 ? (long long)a.N * a.Hr * a.Wr : a.M;
+    return (long long)a.N * a.H * a.W * a.ldx * 4 < lim && (long long)a.M * a.ldy * 4 < lim && (!a.res || res_rows * a.ldr * 4 < lim) &&
            (long long)a.Cout * a.Kpad * 6 < lim;
 }
 
 int launch_conv_panel(int shape, const ConvArgs& a, hipStream_t st) {
     if (!conv_panel_supported(a)) {
-        set_error("conv split3 panel: needs a 1x1 conv without padding, Kpad <= 256, no padding value / per-image shift, operands < 2 GiB");
+        set_error("conv split3 panel: needs a 1x1 conv without padding, Kpad <= 256 (64 or 128 with PEMP_CONV_RES_S2), no padding value / per-image shift, operands < 2 GiB");
         return -1;
+    }
+    if (a.flags & PEMP_CONV_RES_S2) {
+        // <4, 128> is not instantiated: like its dense form it would hold 16 VGPRs in AGPRs (counted as spilled), and a new
+        // instantiation may have none -- id 71 refuses the flag at K = 128
+        if (kTileShapes[shape].bn == 128) {
+            if (a.nk == 2) return launch_panel_rs2<128, 2>(a, st);
+            set_error("conv split3 panel: PEMP_CONV_RES_S2 on tile 71 needs Kpad 64 (Kpad 128: tile 72 or 43)");
+            return -1;
+        }
+        return a.nk == 2 ? launch_panel_rs2<64, 2>(a, st) : launch_panel_rs2<64, 4>(a, st);
     }
     return kTileShapes[shape].bn == 128 ? launch_panel_nk<128>(a, st) : launch_panel_nk<64>(a, st);
 }

@@ -7,6 +7,7 @@ ATen's eval kernel: alpha = weight * rsqrt(var + eps), beta = bias - mean * alph
 Dropout2d are identities).  Also what the model engines (canet_engine, pfenet_engine, rpmms_engine) and networks/ share:
 the episode packer, the padded-Cin and 2-class packers, the bottleneck walker of both ResNet trunks.
 """
+import copy
 import os
 
 import torch
@@ -144,6 +145,20 @@ def presplit_pair(prod, cons, x, rows, enabled=True):
 PRESPLIT_ASPP = True
 
 
+#: Row pruning (DESIGN.md "Row pruning").  Where a stage's output is read by the next stage's stride-2 1x1 convs alone (block 0's
+#: conv1 and downsample conv: torchvision v1 puts the stride there), three quarters of its rows are never read.  ResNetEngine.forward
+#: then runs the stage's LAST block on the even grid only: conv2 at twice its stride, conv3 on the compact tensor with the block input
+#: as a stride-2 residual (ops.conv2d residual_stride=2), and the next block 0 at stride 1 on the compact tensor.  Same dot products:
+#: the step's results do not change by a bit.  PEMP_PRUNE_ROWS=0 restores the full block (the A/B switch).
+PRUNE_ROWS = os.environ.get("PEMP_PRUNE_ROWS", "1") != "0"
+
+
+def restrided(cp, stride):
+    """``cp`` at another stride: a ConvParams that shares its tensors."""
+    return ConvParams(cp.w, cp.scale, cp.shift, cp.cin, cp.cout, cp.kh, cp.kw, stride, cp.pad, cp.dil, cp.kpad, cp.stem, cp.relu,
+                      cp.w3, cp.w3pool)
+
+
 def presplit_readers(prod, readers, x, rows, enabled=True):
     """Whether ``prod`` (fed ``x``) may write a second, pre-split copy of its output for the multi-tap layers among ``readers``:
     every one of them qualifies under ``presplit_pair``'s rule."""
@@ -199,9 +214,13 @@ class _BottleneckTrunk:
     #: conv1 hands y1 to conv2 pre-split (presplit_pair).  Off on the deep-base trunk for the same reason.
     PRESPLIT = True
 
-    def _block(self, x, bp, tag, c1_shift=None, ds_shift=None, out=None):
+    def _block(self, x, bp, tag, c1_shift=None, ds_shift=None, out=None, prune=False):
         """``out``: where the block's result goes (an NHWC view, e.g. a channel slice of a wider buffer); None: the arena's
-        ping-pong buffer of ``tag``."""
+        ping-pong buffer of ``tag``.  ``prune`` (a block without a downsample conv whose only readers are stride-2 1x1 convs): only
+        the output rows on the even grid are computed -- conv2 at twice its stride, conv3 with ``x`` as a stride-2 residual -- and
+        the compact tensor is returned."""
+        if prune:
+            bp = self._pruned_plan(bp)
         a = self.arena
         n, h, w, _ = x.shape
         h1, w1 = (ops.conv_out_size(v, k, bp.c1.stride, bp.c1.pad, bp.c1.dil) for v, k in ((h, bp.c1.kh), (w, bp.c1.kw)))
@@ -221,14 +240,55 @@ class _BottleneckTrunk:
         y2 = ops.conv2d(y1, bp.c2, out=a.get("y2", (n, ho, wo, bp.c2.cout)), x_split3=pre)
         if bp.ds is not None and not grouped:
             ops.conv2d(x, bp.ds, out=res, shift_override=ds_shift, per_image_shift=ds_shift is not None)
-        return ops.conv2d(y2, bp.c3, out=out, residual=res)
+        return ops.conv2d(y2, bp.c3, out=out, residual=res, residual_stride=2 if prune else 1)
 
-    def _stage(self, x, si, final_out=None):
-        """Stage ``si``; ``final_out``: an NHWC view its last block writes to (e.g. a channel slice of a wider buffer)."""
+    def _plan_copy(self, bp, what, **convs):
+        """``bp`` with the layers ``convs`` replaced: made once per block and kept (the layers share their tensors with ``bp``'s)."""
+        cache = self.__dict__.setdefault("_plan_copies", {})
+        key = (id(bp), what)
+        if key not in cache:
+            q = copy.copy(bp)
+            for name, cp in convs.items():
+                setattr(q, name, cp)
+            cache[key] = (bp, q)            # (bp is kept alive: its id stays its own)
+        return cache[key][1]
+
+    def _pruned_plan(self, bp):
+        """The last block of a pruned stage: conv2 at twice its stride."""
+        if bp.ds is not None:
+            raise ValueError("row pruning: the block has a downsample conv of its own")
+        return self._plan_copy(bp, "pruned", c2=restrided(bp.c2, 2 * bp.c2.stride))
+
+    def _compact_plan(self, bp):
+        """Block 0 behind a pruned stage: its stride-2 conv1 and downsample conv read the compact tensor at stride 1."""
+        return self._plan_copy(bp, "compact", c1=restrided(bp.c1, 1), ds=restrided(bp.ds, 1))
+
+    def _stage(self, x, si, final_out=None, compact_in=False, prune=False):
+        """Stage ``si``; ``final_out``: an NHWC view its last block writes to (e.g. a channel slice of a wider buffer).
+        ``compact_in``: ``x`` comes from a pruned stage (only the rows block 0's stride-2 convs read); ``prune``: the stage's last
+        block computes only the rows the next stage reads (``_prunes``)."""
         blocks = self.stages[si]
         for bi, bp in enumerate(blocks):
-            x = self._block(x, bp, (si, bi & 1), out=final_out if bi == len(blocks) - 1 else None)
+            last = bi == len(blocks) - 1
+            if bi == 0 and compact_in:
+                bp = self._compact_plan(bp)
+            x = self._block(x, bp, (si, bi & 1), out=final_out if last else None, prune=prune and last)
         return x
+
+    def _prunes(self, si, stage_outs=None):
+        """Whether stage ``si``'s output may be computed on the even grid only: a split3 engine on an fp32 arena, nobody but the next
+        stage reads the output, that stage's block 0 reads it through two 1x1 / pad 0 / stride 2 convs, the last block of ``si`` adds
+        its own input (no downsample conv) behind a 1x1 conv3, and a tile id takes the strided residual for that conv."""
+        if not PRUNE_ROWS or self.arena.dtype != torch.float32 or si + 1 >= len(self.stages) or (stage_outs and si in stage_outs):
+            return False
+        last, nxt = self.stages[si][-1], self.stages[si + 1][0]
+        if len(self.stages[si]) < 2 or last.ds is not None or nxt.ds is None:
+            return False
+        if any(c.w3 is None for c in (last.c1, last.c2, last.c3, nxt.c1, nxt.ds)):
+            return False
+        if any((c.kh, c.kw, c.pad, c.stride) != (1, 1, 0, 2) for c in (nxt.c1, nxt.ds)):
+            return False
+        return (last.c3.kh, last.c3.kw, last.c3.pad, last.c3.stride) == (1, 1, 0, 1) and bool(ops.res_s2_tiles(last.c3))
 
 
 class ResNetEngine(_BottleneckTrunk):
@@ -260,8 +320,11 @@ class ResNetEngine(_BottleneckTrunk):
         """``stage_outs`` {stage index: NHWC view}: the last block of that stage writes there (CANet: layer2 and layer3 into
         the channel slices of one buffer, so that their concatenation is never formed)."""
         x = self.stem_forward(x4)
+        pruned = False                  # x holds only the rows the next stage's stride-2 convs read (PRUNE_ROWS)
         for si in range(len(self.stages)):
-            x = self._stage(x, si, stage_outs.get(si) if stage_outs else None)
+            prune = self._prunes(si, stage_outs)
+            x = self._stage(x, si, stage_outs.get(si) if stage_outs else None, compact_in=pruned, prune=prune)
+            pruned = prune
         return x
 
 

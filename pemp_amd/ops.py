@@ -15,6 +15,7 @@ import torch
 
 from . import _lib
 from ._lib import ConvDesc, CONV_RELU, CONV_SHIFT_PER_IMAGE, CONV_STEM4, CONV_POOL3S2, CONV_OUT_SPLIT3, CONV_IN_SPLIT3, CONV_OUT_SPLIT3_ALSO  # noqa: F401
+from ._lib import CONV_RES_S2, CONV_RES_HEVEN, CONV_RES_WEVEN
 
 
 def _stream():
@@ -280,6 +281,21 @@ def _panel_ok(p, n, ho, wo, ldx, ldy, ldr, h, w, pad_value, splitk, per_image_sh
             and n * ho * wo * max(ldy, ldr) * 4 < lim)
 
 
+#: the split3 ids with a strided-residual form (``conv2d(residual_stride=2)``, PEMP_CONV_RES_S2): 43 for any layer and any M, and the
+#: panel ids where the variant is instantiated (``res_s2_tiles``).  The persistent, split-K and pre-split ids refuse the flag
+SPLIT3_RES_S2_TILES = (43, 72, 71)
+
+
+def res_s2_tiles(p):
+    """The tile ids that take ``conv2d(residual_stride=2)`` for layer ``p``, in the order they are timed: 43; 72 for 1x1 / pad 0
+    layers of K = 64 or 128; 71 at K = 64 (its K = 128 form would spill).  () for a layer without split weights."""
+    if p.w3 is None or p.stem:
+        return ()
+    panel = p.kh == 1 and p.kw == 1 and p.pad == 0
+    return tuple(t for t in SPLIT3_RES_S2_TILES
+                 if t == 43 or (panel and p.cout % _tile_bn(t) == 0 and (p.kpad == 64 or (p.kpad == 128 and t == 72))))
+
+
 def row3_stage_rows(w, dil):
     """Stage rows a 256-row tile of csrc/conv_row3.hip can need on maps of width ``w``: 256 + 2 d pixels and d zero rows per image-row
     boundary inside them (row3_stage_rows there)."""
@@ -338,10 +354,11 @@ def _split3_dims(t, name):
     return tuple(t.shape[:3]) + (t.shape[3] * 32,)
 
 
-def _conv_geom(who, x, p, out, residual, dtype=torch.float32, out_dtype=None, x_split3=False, out_split3=False):
+def _conv_geom(who, x, p, out, residual, dtype=torch.float32, out_dtype=None, x_split3=False, out_split3=False, residual_stride=1):
     """What every conv wrapper checks of its tensors: x an NHWC view of the layer's channel count, ``out`` (allocated when None)
     and ``residual`` NHWC views of the output's shape.  ``x_split3`` / ``out_split3``: that tensor is in the pre-split form
-    (``split3_shape``: dense, so its per-pixel stride is the channel count).  -> (n, h, w, cin, ldx, ho, wo, out, ldy, ldr)"""
+    (``split3_shape``: dense, so its per-pixel stride is the channel count).  ``residual_stride`` 2: the residual is [n, Hr, Wr, cout]
+    on a grid twice as fine, ho == (Hr - 1) // 2 + 1 and wo likewise.  -> (n, h, w, cin, ldx, ho, wo, out, ldy, ldr)"""
     if x_split3:
         n, h, w, cin = _split3_dims(x, "x")
         ldx = cin
@@ -370,14 +387,23 @@ def _conv_geom(who, x, p, out, residual, dtype=torch.float32, out_dtype=None, x_
     ldr = 0
     if residual is not None:
         ldr = _nhwc(residual, "residual", dtype)
-        if tuple(residual.shape) != tuple(out.shape):
+        if residual_stride == 2:
+            rn, hr, wr, rc = residual.shape
+            if (rn, rc) != (n, p.cout) or (hr - 1) // 2 + 1 != ho or (wr - 1) // 2 + 1 != wo:
+                raise ValueError(f"{who}: a stride-2 residual of shape {tuple(residual.shape)} does not cover the output {tuple(out.shape)}")
+        elif tuple(residual.shape) != tuple(out.shape):
             raise ValueError(f"{who}: residual shape mismatch")
+    elif residual_stride != 1:
+        raise ValueError(f"{who}: residual_stride without a residual")
     return n, h, w, cin, ldx, ho, wo, out, ldy, ldr
 
 
 def conv2d(x, p, out=None, residual=None, shift_override=None, per_image_shift=False, relu=None, tile=0,
-           pad_value=None, splitk=False, dropblock=None, out_split3=False, x_split3=False, also_split3=None):
+           pad_value=None, splitk=False, dropblock=None, out_split3=False, x_split3=False, also_split3=None, residual_stride=1):
     """y = act(scale * conv(x, w) + shift (+ residual)).  x: NHWC view, returns NHWC tensor/view ``out``.
+    ``residual_stride`` 2: ``residual`` is [n, Hr, Wr, cout] on a grid twice as fine as the output (ho == (Hr - 1) // 2 + 1, wo
+    likewise) and output pixel (i, j) adds its pixel (2 i, 2 j) -- bit-identical to the same id on ``residual[:, ::2, ::2]``, without
+    the gather.  Split3 layers only, and only the ids of ``res_s2_tiles``; no pre-split operand, padding value, split-K or DropBlock.
     ``out_split3``: ``out`` is written PRE-SPLIT (bf16 ``split3_shape``: the split3 pieces of the fp32 result, for ONE reader that
     takes it with ``x_split3``); split3 layers only, no residual / split-K / DropBlock, never the panel ids.
     ``x_split3``: ``x`` is such a tensor (a ``pad_value`` then the same split of the [Cin] vector, bf16 [Cin / 32, 3, 32]); multi-tap
@@ -405,9 +431,20 @@ def conv2d(x, p, out=None, residual=None, shift_override=None, per_image_shift=F
         raise ValueError("conv2d: a second, pre-split output needs a pre-split input (x_split3), no out_split3, no residual")
     if (tile in SPLIT3_PRESPLIT_TILES + SPLIT3_ROW3_TILES) != bool(x_split3) and (tile or not x_split3):
         raise ValueError(f"conv2d: the tile ids {SPLIT3_PRESPLIT_TILES + SPLIT3_ROW3_TILES} and x_split3 come together (tile {tile})")
+    res_s2 = residual_stride == 2
+    if residual_stride not in (1, 2):
+        raise ValueError(f"conv2d: residual_stride must be 1 or 2, got {residual_stride}")
+    if res_s2:                       # what the library refuses for this form (csrc/conv_igemm.hip: conv2d_impl)
+        if p.w3 is None or p.stem or x.dtype != torch.float32:
+            raise ValueError("conv2d: a stride-2 residual needs a split3 layer (ConvParams.w3) on fp32 activations")
+        if residual is None or out_split3 or x_split3 or also_split3 is not None or pad_value is not None or splitk or dropblock is not None:
+            raise ValueError("conv2d: a stride-2 residual comes with a residual and without pre-split operands, padding value, split-K or DropBlock")
+        if tile and tile not in res_s2_tiles(p):
+            raise ValueError(f"conv2d: a stride-2 residual needs one of the tile ids {res_s2_tiles(p)} for this layer, got {tile}")
     if x.dtype == torch.bfloat16 and not x_split3:
         return _conv2d_bf16(x, p, out, residual, shift_override, per_image_shift, relu, tile, pad_value)
-    n, h, w, cin, ldx, ho, wo, out, ldy, ldr = _conv_geom("conv2d", x, p, out, residual, x_split3=x_split3, out_split3=out_split3)
+    n, h, w, cin, ldx, ho, wo, out, ldy, ldr = _conv_geom("conv2d", x, p, out, residual, x_split3=x_split3, out_split3=out_split3,
+                                                          residual_stride=residual_stride)
     if also_split3 is not None and _split3_dims(also_split3, "also_split3") != (n, ho, wo, p.cout):
         raise ValueError(f"conv2d: also_split3 shape {tuple(also_split3.shape)} != {split3_shape(n, ho, wo, p.cout)}")
     lib = _lib.load()
@@ -429,8 +466,10 @@ def conv2d(x, p, out=None, residual=None, shift_override=None, per_image_shift=F
         flags |= CONV_SHIFT_PER_IMAGE
     if p.stem:
         flags |= CONV_STEM4
+    if res_s2:
+        flags |= CONV_RES_S2 | (CONV_RES_HEVEN if residual.shape[1] % 2 == 0 else 0) | (CONV_RES_WEVEN if residual.shape[2] % 2 == 0 else 0)
     splitk = ((splitk and SPLITK) or (EVAL_SPLITK and n * ho * wo <= EVAL_SPLITK_MAX_ROWS)) and not p.stem \
-        and not out_split3 and not x_split3
+        and not out_split3 and not x_split3 and not res_s2
     # split3: the layer carries split weights (inference engines; the layer's geometry decided it) and plain epilogue.  A call
     # outside the buffer-addressed kernels (an input of 2 GiB or more; a padding vector that does not sit far enough behind a
     # small map under a large dilation) runs the fp32 chain, whose pointer-addressed fall-back takes it
@@ -441,6 +480,8 @@ def conv2d(x, p, out=None, residual=None, shift_override=None, per_image_shift=F
     if (out_split3 or x_split3) and not s3:
         raise ValueError("conv2d: pre-split activations need a geometry of the buffer-addressed kernels (<= 32 taps, operands < 2 GiB, "
                          "a padding value behind the activations)")
+    if res_s2 and not (s3 and residual.numel() // p.cout * ldr < 1 << 31):
+        raise ValueError("conv2d: a stride-2 residual needs a geometry of the buffer-addressed kernels and a residual below 2^31 elements")
 
     if dropblock is not None:
         dmask, dcnt = dropblock
@@ -494,6 +535,13 @@ def conv2d(x, p, out=None, residual=None, shift_override=None, per_image_shift=F
                 key += (246,)
             cands = lambda: _fits(list(SPLIT3_PRESPLIT_TILES if x_split3 else SPLIT3_TILES) +
                                   (list(SPLIT3_ROW3_TILES) if row3 and PICK_HOOK is None else []), p.cout)
+        elif res_s2:
+            # a key of its own (128): a pick made with a dense residual is never replayed on the strided one, nor the reverse.  Only
+            # the ids that take the flag are offered; the panel ones under their usual rule (and the residual's own extent < 2 GiB)
+            panel = _panel_ok(p, n, ho, wo, ldx, ldy, ldr, h, w, pad_value, splitk, per_image_shift) \
+                and residual.numel() // p.cout * ldr * 4 < 1 << 31
+            key += (128,) + ((71,) if panel else ())
+            cands = lambda: _fits([t for t in res_s2_tiles(p) if panel or t not in SPLIT3_PANEL_TILES], p.cout)
         elif s3:
             # a pick among candidates that include the panel ids is remembered under a key of its own (71): a call of the same
             # geometry that they do not take (a per-image shift, operands of 2 GiB) must never replay it

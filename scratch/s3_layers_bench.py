@@ -33,6 +33,11 @@ LAYERS = ((256, 1024, 1, 1, True, False), (512, 1024, 1, 1, False, False), (1024
           # the other 3x3 widths (layer2: stride 1 at 51 x 51 and stride 2 from 101 x 101; layer1 at 101 x 101) and layer2's conv1
           (128, 128, 3, 1, False, False), (128, 128, 3, 1, False, False, 2, 101), (64, 64, 3, 1, False, False, 1, 101),
           (512, 128, 1, 1, False, False),
+          # layer1's last conv3 with row pruning: M = 130 050 compact rows, the residual on the 101 x 101 grid (residual_stride=2; a 9th
+          # field: the residual's grid).  Against the dense-residual row 64-256-k1-hw101-res1 at M = 510 050
+          (64, 256, 1, 1, True, False, 1, 51, 101),
+          # ... and its conv2 at stride 2 (against 64-64-k3-hw101-res0)
+          (64, 64, 3, 1, False, False, 2, 101),
           # a dilated ASPP branch (dilation 12) with its padding vector
           (256, 256, 3, 12, False, True))
 
@@ -66,6 +71,31 @@ def digest(t):
     return hashlib.sha1(t.cpu().numpy().tobytes()).hexdigest()[:16]
 
 
+def rs2_row(dev, N, HW, HR, cin, cout, name, keep, reps):
+    """A 1x1 conv on N compact maps of HW x HW with the residual on the HR x HR grid (ops.conv2d residual_stride=2), every id that takes
+    it; ! = differs from id 43 on the gathered dense residual."""
+    g = torch.Generator().manual_seed(cin * 7 + cout * 3 + 1001)
+    x = torch.randn(N * HW * HW, cin, generator=g).to(dev).view(N, HW, HW, cin)
+    w = (torch.randn(cout, cin, 1, 1, generator=g) * (1.0 / cin ** 0.5)).to(dev)
+    packed, kpad = ops.pack_conv_weight(w)
+    packed = packed.contiguous()
+    prm = ops.ConvParams(packed, None, torch.randn(cout, generator=g).to(dev), cin, cout, 1, 1, 1, 0, 1, kpad, False, True, ops.pack_split3(packed))
+    res = torch.randn(N, HR, HR, cout, generator=g).to(dev)
+    ref = ops.conv2d(x, prm, residual=res[:, ::2, ::2, :].contiguous(), tile=43).clone()
+    out = torch.empty_like(ref)
+    fl = 2.0 * N * HW * HW * cout * cin
+    cells = []
+    for tile in keep(ops.res_s2_tiles(prm)):
+        run = lambda: ops.conv2d(x, prm, residual=res, residual_stride=2, out=out, tile=tile)
+        out.zero_()
+        run()
+        same = torch.equal(out, ref)
+        us, worst = timed(run, reps)
+        cells.append(f"{tile}: {us:7.1f}..{worst:6.1f}us {fl / us / 1e6:5.1f}TF{'' if same else ' !'}")
+    print(f"{name:>16} k1 d1 res1 | " + " | ".join(cells), flush=True)
+    print(f"{'':>16} hash 43={digest(ref)}", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", default="", help="cin-cout-kK[-padv]: one layer")
@@ -78,12 +108,16 @@ def main():
     keep = lambda ids: tuple(t for t in ids if not args.ids or str(t) in args.ids.split(","))
     for layer in LAYERS:
         cin, cout, k, dil, has_res, padv = layer[:6]
-        stride, HW = layer[6:] if len(layer) > 6 else (1, 51)
-        has_res = has_res if args.res is None else bool(args.res)
+        stride, HW = layer[6:8] if len(layer) > 6 else (1, 51)
+        RS2 = layer[8] if len(layer) > 8 else 0          # the strided residual's grid
+        has_res = has_res if args.res is None or RS2 else bool(args.res)
         M = N * HW * HW
         HO = (HW - 1) // stride + 1
-        name = f"{cin}-{cout}-k{k}" + (f"-d{dil}" if k == 3 and dil > 2 else "") + ("-padv" if padv else "") + (f"-s{stride}" if stride > 1 else "") + (f"-hw{HW}-res{int(has_res)}" if HW != 51 else "")
+        name = f"{cin}-{cout}-k{k}" + (f"-d{dil}" if k == 3 and dil > 2 else "") + ("-padv" if padv else "") + (f"-s{stride}" if stride > 1 else "") + (f"-hw{HW}-res{int(has_res)}" if HW != 51 else "") + ("-rs2" if RS2 else "")
         if args.only and name not in args.only.split(","):
+            continue
+        if RS2:
+            rs2_row(dev, N, HW, RS2, cin, cout, name, keep, args.reps)
             continue
         g = torch.Generator().manual_seed(cin * 7 + cout * 3 + k)
         buf = torch.empty(M + 4, cin, device=dev)
