@@ -630,6 +630,30 @@ int pemp_episode_preprocess(const uint8_t* blob, const pemp_sample_desc* descs_h
 size_t pemp_prior_mask_workspace_bytes(int B, int S, int HW);
 int pemp_prior_mask_f32(const float* q, int ldq, const float* s, int lds, const float* mask, float* out, void* ws,
                         size_t ws_bytes, int B, int S, int HW, int C, void* stream);
+/* Support banks of the prior: the support operand of K classes stored once, met by any number of queries.
+ * Pack: s NHWC [K*S][HW][C] (pixel stride lds), mask [K*S][HW] -> one slot of cap rows per (class, shot):
+ *   rows  [K*S][cap][C]  fl(m_p * s_p) of the pixels with m_p != 0, in pixel order; then ONE all-zero row if a pixel with
+ *                        m_p == 0 exists (such a pixel's similarity is exactly +0 for every query)
+ *   norms [K*S][cap]     |m_p s_p| per stored row, summed in pemp_prior_mask_f32's order
+ *   count [K*S] int32    rows stored, 1 .. HW (device memory)
+ * Slots at or beyond count are not written; a row that does not fit into cap is dropped while count still says how many
+ * rows the image needs (the caller compares it with cap).  rows == norms == NULL: only count is written (s, C, cap unused).
+ * cap % 64 == 0, C % 32 == 0.  Deterministic: the compaction is an integer scan.                                      */
+int pemp_prior_bank_pack_f32(const float* s, int lds, const float* mask, float* rows, float* norms, int32_t* count,
+                             int KS, int HW, int C, int cap, void* stream);
+/* The prior of N queries against a packed bank: q NHWC [N][HW][C] (ldq).
+ *   index NULL:            every query against every class -> out [N][K][HW]
+ *   index [N] int32 (dev): query n against class index[n] (clamped into 0..K-1) -> out [N][HW]
+ * One block per (query tile, shot, query-class pair) walks the ceil(count / 64) support tiles of its slot on the fp32
+ * MFMA and keeps the max in registers; then the per-shot min-max normalisation and the shot mean of pemp_prior_mask_f32.
+ * For every (n, k) the output is bit for bit pemp_prior_mask_f32's on query n and the supports class k was packed from.
+ * Query-class pairs and S <= 65535.  ws: pemp_prior_bank_workspace_bytes(pairs, S, HW).                             */
+size_t pemp_prior_bank_workspace_bytes(int pairs, int S, int HW);
+int pemp_prior_bank_f32(const float* q, int ldq, const float* rows, const float* norms, const int32_t* count,
+                        const int32_t* index, float* out, void* ws, size_t ws_bytes, int N, int K, int S, int HW, int C,
+                        int cap, void* stream);
+/* Rows of a [K][C] table by the same selection: index [N] -> dst [N][C] = src[index[n]]; NULL -> dst [N][K][C] = src[k]. */
+int pemp_bank_gather_rows_f32(const float* src, const int32_t* index, float* dst, int N, int K, int C, void* stream);
 /* nn.AdaptiveAvgPool2d((Ho, Wo)) on NHWC (pfenet.py:244-247): windows [floor(i H / Ho), ceil((i + 1) H / Ho)), also for
  * Ho > H; x and y are channel slices with pixel strides ldx / ldy.                                                    */
 int pemp_adaptive_avgpool_nhwc_f32(const float* x, int ldx, float* y, int ldy, int N, int H, int W, int C, int Ho, int Wo,

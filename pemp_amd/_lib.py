@@ -148,6 +148,10 @@ SYMBOLS = {
     # PFENet inference
     "pemp_prior_mask_workspace_bytes": (c_size, [c_int] * 3),
     "pemp_prior_mask_f32": (c_int, [c_fp, c_int, c_fp, c_int, c_fp, c_fp, c_fp, c_size] + [c_int] * 4 + [c_fp]),
+    "pemp_prior_bank_pack_f32": (c_int, [c_fp, c_int, c_fp, c_fp, c_fp, c_fp] + [c_int] * 4 + [c_fp]),
+    "pemp_prior_bank_workspace_bytes": (c_size, [c_int] * 3),
+    "pemp_prior_bank_f32": (c_int, [c_fp, c_int, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_size] + [c_int] * 6 + [c_fp]),
+    "pemp_bank_gather_rows_f32": (c_int, [c_fp, c_fp, c_fp, c_int, c_int, c_int, c_fp]),
     "pemp_adaptive_avgpool_nhwc_f32": (c_int, [c_fp, c_int, c_fp] + [c_int] * 7 + [c_fp]),
     "pemp_resize_bilinear_ac_nhwc_f32": (c_int, [c_fp, C.c_longlong, c_int, c_int, c_fp, C.c_longlong, c_int, c_int] + [c_int] * 7
                                          + [c_fp]),

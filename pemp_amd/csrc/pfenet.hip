@@ -152,6 +152,170 @@ __global__ __launch_bounds__(1024) void prior_finish_kernel(const float* __restr
     }
 }
 
+// -- support banks: the support side of the prior GEMM stored once per (class, shot), met by any number of queries ---------------
+// Pack: one block per support image.  The pixels with m != 0 are compacted in pixel order (chunks of 256 pixels, an integer
+// ballot / popcount scan: exact, the same layout on every run); row j of the slot is fl(m_p s_p), its norm is accumulated with
+// prior_tile_kernel's own partial sums (lane t & 7 owns channels 4 (t & 7) .. + 3 of every 32-channel step, fma chain x y z w,
+// xor-1/2/4 butterfly, __fsqrt_rn), so the stored norm is the number that kernel forms for the pixel.  One all-zero row follows
+// when a pixel with m == 0 exists.  rows == nullptr: only the count is written.  Rows at or beyond cap are not written.
+__global__ __launch_bounds__(256) void prior_bank_pack_kernel(const float* __restrict__ s, int lds, const float* __restrict__ mask,
+                                                              float* __restrict__ rows, float* __restrict__ norms,
+                                                              int* __restrict__ count, int HW, int C, int cap) {
+    __shared__ int src[256];
+    __shared__ int wtot[4];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const size_t img = blockIdx.x;
+    const float* mp = mask + img * HW;
+    const int g = t >> 3, kc = (t & 7) * 4;
+    int run = 0;
+    for (int c0 = 0; c0 < HW; c0 += 256) {
+        const int p = c0 + t;
+        const bool fg = p < HW && mp[p] != 0.f;
+        const unsigned long long bal = __ballot(fg);
+        const int pre = __popcll(bal & ((1ull << lane) - 1ull));
+        __syncthreads();                                // the previous chunk's readers of src / wtot are done
+        if (lane == 0) wtot[wave] = __popcll(bal);
+        __syncthreads();
+        int base = 0;
+        for (int i = 0; i < wave; ++i) base += wtot[i];
+        const int tot = wtot[0] + wtot[1] + wtot[2] + wtot[3];
+        if (fg) src[base + pre] = p;
+        __syncthreads();
+        if (rows) {
+            for (int j0 = 0; j0 < tot; j0 += 32) {      // 32 rows per pass, 8 lanes per row
+                const int j = j0 + g, dst = run + j;
+                const bool ok = j < tot && dst < cap;
+                const int sp = ok ? src[j] : 0;
+                const float m = ok ? mp[sp] : 0.f;
+                const float* in = s + (img * HW + sp) * lds + kc;
+                float* o = rows + (img * cap + (ok ? dst : 0)) * C + kc;
+                float ss = 0.f;
+                for (int k0 = 0; k0 < C; k0 += PK) {
+                    if (ok) {
+                        const float4 v = *(const float4*)(in + k0);
+                        const float4 a = make_float4(__fmul_rn(v.x, m), __fmul_rn(v.y, m), __fmul_rn(v.z, m), __fmul_rn(v.w, m));
+                        *(float4*)(o + k0) = a;
+                        ss = __fmaf_rn(a.w, a.w, __fmaf_rn(a.z, a.z, __fmaf_rn(a.y, a.y, __fmaf_rn(a.x, a.x, ss))));
+                    }
+                }
+                ss += __shfl_xor(ss, 1, 64);
+                ss += __shfl_xor(ss, 2, 64);
+                ss += __shfl_xor(ss, 4, 64);
+                if (ok && (t & 7) == 0) norms[img * cap + dst] = __fsqrt_rn(ss);
+            }
+        }
+        run += tot;
+    }
+    if (rows && run < HW && run < cap) {                // the one row that stands for every pixel with m == 0
+        for (int i = t; i < C; i += 256) rows[(img * cap + run) * C + i] = 0.f;
+        if (t == 0) norms[img * cap + run] = 0.f;
+    }
+    if (t == 0) count[img] = run + (run < HW ? 1 : 0);
+}
+
+// One (query tile, shot, query-class pair) block: prior_tile_kernel's arithmetic with the support operand and its norms read from
+// the bank.  The block walks the ceil(count / 64) support tiles of its slot itself and keeps the running max in registers
+// -> sim[pair * S + shot][q]; every similarity is its own k-ordered MFMA chain, so the tile a row sits in does not matter.
+// index != nullptr: pair n meets class index[n] (clamped into 0..K-1); nullptr: pair n * K + k meets class k.
+__global__ __launch_bounds__(256) void prior_bank_kernel(const float* __restrict__ q, int ldq, const float* __restrict__ rows,
+                                                         const float* __restrict__ norms, const int* __restrict__ count,
+                                                         const int* __restrict__ index, float* __restrict__ sim, int K, int S,
+                                                         int HW, int C, int cap) {
+    __shared__ float As[PK][PLD];       // support operand, k-major
+    __shared__ float Bs[PK][PLD];       // query operand, k-major
+    __shared__ float nrm[2][PT];        // |m s| per stored row, |q| per query pixel
+    __shared__ float red[2][PT];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int wp = wave & 1, wq = wave >> 1;
+    const int si = blockIdx.y, pair = blockIdx.z;
+    const int n = index ? pair : pair / K;
+    const int k = index ? min(max(index[pair], 0), K - 1) : pair % K;
+    const size_t slot = (size_t)k * S + si;
+    const int cnt = min(max(count[slot], 1), cap);
+    const float* rbase = rows + slot * cap * C;
+    const float* nbase = norms + slot * cap;
+    const int q0 = blockIdx.x * PT;
+    const int r = t >> 3, kc = (t & 7) * 4;             // rows r and r + 32 of both tiles, channels kc..kc+3 of a step
+
+    const float* sp[2];
+    const float* qp[2];
+    for (int i = 0; i < 2; ++i) {
+        const int qq = q0 + r + 32 * i;
+        qp[i] = qq < HW ? q + ((size_t)n * HW + qq) * ldq + kc : nullptr;
+    }
+    float4 ra[2], rb[2];
+    float ssb[2] = {0.f, 0.f};
+    auto load = [&](int k0) {
+        for (int i = 0; i < 2; ++i) {
+            ra[i] = sp[i] ? *(const float4*)(sp[i] + k0) : make_float4(0.f, 0.f, 0.f, 0.f);
+            rb[i] = qp[i] ? *(const float4*)(qp[i] + k0) : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+    };
+    const int qc = wq * 32 + (lane & 31);
+    float mx = -INFINITY;
+    for (int p0 = 0; p0 < cnt; p0 += PT) {
+        for (int i = 0; i < 2; ++i) {
+            const int p = p0 + r + 32 * i;
+            sp[i] = p < cnt ? rbase + (size_t)p * C + kc : nullptr;
+        }
+        f32x16 acc = {};
+        load(0);
+        for (int k0 = 0; k0 < C; k0 += PK) {
+            __syncthreads();
+            if (k0 == 0 && t < PT) nrm[0][t] = p0 + t < cnt ? nbase[p0 + t] : 0.f;
+            for (int i = 0; i < 2; ++i) {
+                const int row = r + 32 * i;
+                As[kc + 0][row] = ra[i].x; As[kc + 1][row] = ra[i].y; As[kc + 2][row] = ra[i].z; As[kc + 3][row] = ra[i].w;
+                Bs[kc + 0][row] = rb[i].x; Bs[kc + 1][row] = rb[i].y; Bs[kc + 2][row] = rb[i].z; Bs[kc + 3][row] = rb[i].w;
+                if (p0 == 0)
+                    ssb[i] = __fmaf_rn(rb[i].w, rb[i].w, __fmaf_rn(rb[i].z, rb[i].z, __fmaf_rn(rb[i].y, rb[i].y, __fmaf_rn(rb[i].x, rb[i].x, ssb[i]))));
+            }
+            __syncthreads();
+            if (k0 + PK < C) load(k0 + PK);
+#pragma unroll
+            for (int kk = 0; kk < PK / 2; ++kk) {
+                const float a = As[2 * kk + (lane >> 5)][wp * 32 + (lane & 31)];
+                const float bq = Bs[2 * kk + (lane >> 5)][wq * 32 + (lane & 31)];
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, bq, acc, 0, 0, 0);
+            }
+        }
+        if (p0 == 0) {                  // the query norms: once, in prior_tile_kernel's summation order
+            for (int i = 0; i < 2; ++i) {
+                float xb = ssb[i];
+                xb += __shfl_xor(xb, 1, 64);
+                xb += __shfl_xor(xb, 2, 64);
+                xb += __shfl_xor(xb, 4, 64);
+                if ((t & 7) == 0) nrm[1][r + 32 * i] = __fsqrt_rn(xb);
+            }
+        }
+        __syncthreads();
+        const float nq = nrm[1][qc];
+#pragma unroll
+        for (int reg = 0; reg < 16; ++reg) {
+            const int pr = wp * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5);
+            if (p0 + pr < cnt) {
+                const float v = __fdiv_rn(acc[reg], __fadd_rn(__fmul_rn(nrm[0][pr], nq), COS_EPS));
+                mx = fmaxf(mx, v);
+            }
+        }
+    }
+    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+    if (lane < 32) red[wp][qc] = mx;
+    __syncthreads();
+    if (t < PT && q0 + t < HW) sim[((size_t)pair * S + si) * HW + q0 + t] = fmaxf(red[0][t], red[1][t]);
+}
+
+// dst[n] = src[index[n]] (index clamped into 0..K-1), or without an index dst[n * K + k] = src[k]: rows of C floats.
+__global__ void bank_gather_rows_kernel(const float* __restrict__ src, const int* __restrict__ index, float* __restrict__ dst,
+                                        int P, int K, int C) {
+    const long long total = (long long)P * C;
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const int c = (int)(i % C), pr = (int)(i / C);
+        const int k = index ? min(max(index[pr], 0), K - 1) : pr % K;
+        dst[i] = src[(size_t)k * C + c];
+    }
+}
+
 // nn.AdaptiveAvgPool2d on NHWC: window rows [floor(i in / out), ceil((i + 1) in / out)), sum row by row, / kh / kw.
 __global__ void adaptive_avgpool_kernel(const float* __restrict__ x, int ldx, float* __restrict__ y, int ldy, int N, int H, int W,
                                         int C, int Ho, int Wo) {
@@ -280,6 +444,55 @@ extern "C" int pemp_prior_mask_f32(const float* q, int ldq, const float* s, int 
     hipLaunchKernelGGL(prior_tilemax_kernel, dim3(cdiv(HW, 256), B * S), dim3(256), 0, (hipStream_t)stream, part, sim, HW, nbt);
     hipLaunchKernelGGL(prior_finish_kernel, dim3(B), dim3(1024), 0, (hipStream_t)stream, sim, out, S, HW);
     return launch_status("prior_mask");
+}
+
+extern "C" int pemp_prior_bank_pack_f32(const float* s, int lds, const float* mask, float* rows, float* norms, int32_t* count,
+                                        int KS, int HW, int C, int cap, void* stream) {
+    PEMP_REQUIRE(mask && count, "prior_bank_pack: null pointer");
+    PEMP_REQUIRE((rows != nullptr) == (norms != nullptr) && (!rows || s), "prior_bank_pack: rows, norms and s go together");
+    PEMP_REQUIRE(KS > 0 && HW > 0, "prior_bank_pack: bad sizes");
+    if (rows) {
+        PEMP_REQUIRE(C > 0 && C % PK == 0, "prior_bank_pack: bad sizes (C %% 32 == 0 required)");
+        PEMP_REQUIRE(cap > 0 && cap % PT == 0, "prior_bank_pack: cap must be a positive multiple of 64");
+        PEMP_REQUIRE(lds >= C && lds % 4 == 0 && ((uintptr_t)s & 15) == 0 && ((uintptr_t)rows & 15) == 0,
+                     "prior_bank_pack: lds must be >= C and a multiple of 4, s and rows 16-byte aligned");
+    }
+    hipLaunchKernelGGL(prior_bank_pack_kernel, dim3(KS), dim3(256), 0, (hipStream_t)stream, s, lds, mask, rows, norms, count, HW, C,
+                       cap);
+    return launch_status("prior_bank_pack");
+}
+
+extern "C" size_t pemp_prior_bank_workspace_bytes(int pairs, int S, int HW) {
+    if (pairs <= 0 || S <= 0 || HW <= 0) return 0;
+    return (size_t)pairs * S * HW * sizeof(float);                           // sim[pair * S + shot][q]
+}
+
+extern "C" int pemp_prior_bank_f32(const float* q, int ldq, const float* rows, const float* norms, const int32_t* count,
+                                   const int32_t* index, float* out, void* ws, size_t ws_bytes, int N, int K, int S, int HW, int C,
+                                   int cap, void* stream) {
+    PEMP_REQUIRE(q && rows && norms && count && out && ws, "prior_bank: null pointer");
+    PEMP_REQUIRE(N > 0 && K > 0 && S > 0 && HW > 0 && C > 0 && C % PK == 0, "prior_bank: bad sizes (C %% 32 == 0 required)");
+    PEMP_REQUIRE(cap > 0 && cap % PT == 0, "prior_bank: cap must be a positive multiple of 64");
+    PEMP_REQUIRE(ldq >= C && ldq % 4 == 0 && ((uintptr_t)q & 15) == 0 && ((uintptr_t)rows & 15) == 0,
+                 "prior_bank: ldq must be >= C and a multiple of 4, q and rows 16-byte aligned");
+    const long long pairs = index ? N : (long long)N * K;
+    PEMP_REQUIRE(pairs <= 65535 && S <= 65535, "prior_bank: more than 65535 query-class pairs or shots");
+    PEMP_REQUIRE(ws_bytes >= pemp_prior_bank_workspace_bytes((int)pairs, S, HW), "prior_bank: workspace too small");
+    float* sim = (float*)ws;
+    hipLaunchKernelGGL(prior_bank_kernel, dim3(cdiv(HW, PT), S, (int)pairs), dim3(256), 0, (hipStream_t)stream, q, ldq, rows, norms,
+                       count, index, sim, K, S, HW, C, cap);
+    hipLaunchKernelGGL(prior_finish_kernel, dim3((int)pairs), dim3(1024), 0, (hipStream_t)stream, sim, out, S, HW);
+    return launch_status("prior_bank");
+}
+
+extern "C" int pemp_bank_gather_rows_f32(const float* src, const int32_t* index, float* dst, int N, int K, int C, void* stream) {
+    PEMP_REQUIRE(src && dst, "bank_gather_rows: null pointer");
+    PEMP_REQUIRE(N > 0 && K > 0 && C > 0, "bank_gather_rows: bad sizes");
+    const long long P = index ? N : (long long)N * K;
+    PEMP_REQUIRE(P <= 0x7fffffff, "bank_gather_rows: too many rows");
+    hipLaunchKernelGGL(bank_gather_rows_kernel, dim3(grid_of(P * C)), dim3(256), 0, (hipStream_t)stream, src, index, dst, (int)P, K,
+                       C);
+    return launch_status("bank_gather_rows");
 }
 
 extern "C" int pemp_adaptive_avgpool_nhwc_f32(const float* x, int ldx, float* y, int ldy, int N, int H, int W, int C, int Ho,

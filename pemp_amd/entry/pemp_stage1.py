@@ -382,11 +382,10 @@ class BankEvaluator(Evaluator):
         return super().start_eval_loop(dataset, num_classes, split, te_epochs, logger, batch, dataset_name)
 
     def _enroll(self, slot, cls, sup_img, sup_mask):
-        from ..bank import PrototypeBank
         one = self.model.enroll(sup_img.to(self.device, non_blocking=True), sup_mask.to(self.device, non_blocking=True), labels=[cls])
-        if self.bank is None or len(self.bank) != len(self._labels) or tuple(self.bank.protos.shape[1:]) != tuple(one.protos.shape[1:]):
-            zeros = torch.zeros((len(self._labels),) + tuple(one.protos.shape[1:]), dtype=torch.float32, device=self.device)
-            self.bank = PrototypeBank(zeros, one.family, one.backbone, one.precision, one.dist_scalar, labels=self._labels)
+        if self.bank is None or len(self.bank) != len(self._labels) or not self.bank.holds(one):
+            # an empty sibling of the one-class bank: a PrototypeBank of zeros, or a PFENetBank whose slots hold any mask
+            self.bank = type(one).empty_like(one, len(self._labels), labels=self._labels)
         self.bank.update(slot, one)
 
     def _episodes(self, dataset, indices):
@@ -421,9 +420,10 @@ class BankEvaluator(Evaluator):
         return self.test_step_batch(episodes)
 
 
-def run_test_bank(_config, name, model_class, split, shot, exp_id, ckpt, seed=None):
+def run_test_bank(_config, name, model_class, split, shot, exp_id, ckpt, seed=None, **load_kw):
     """Body of the ``test_bank`` commands: ``test`` with the enroll-once protocol (``BankEvaluator``).  Same checkpoint
-    lookup, same episode source (``data.base_dir`` or synthetic), same result string; no configuration key of its own."""
+    lookup, same episode source (``data.base_dir`` or synthetic), same result string; no configuration key of its own.
+    ``model_class(logger)`` makes the model, ``load_kw`` goes to ``load_for_eval`` (PFENet's Wgen seed)."""
     import logging
     logging.basicConfig(level=logging.INFO, format="%(message)s")
     logger = logging.getLogger(name)
@@ -433,7 +433,7 @@ def run_test_bank(_config, name, model_class, split, shot, exp_id, ckpt, seed=No
         torch.manual_seed(seed)
     from ..core.snapshots import load_for_eval
     model = model_class(logger)
-    load_for_eval(model, _config, exp_id, ckpt, logger)
+    load_for_eval(model, _config, exp_id, ckpt, logger, **load_kw)
     model = model.cuda().eval()
     dcfg = _config["data"]
     data = eval_episodes(dcfg, shot, split)

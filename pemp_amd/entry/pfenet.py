@@ -1,6 +1,7 @@
 """PFENet evaluation harness on MI355X (counterpart of the reference's entry/pfenet.py: config :27-45, ``Evaluator.test_step``
 :54-60, ``test`` :129-148).  The stage-1 evaluator (batching, sharding, hipGraph replay, fused upsample + CE + argmax +
-tp/fp/fn tail) runs the model's feature-resolution logits (``PFENet.lowres``).  ``train_head`` trains the head behind the frozen
+tp/fp/fn tail) runs the model's feature-resolution logits (``PFENet.lowres``); ``test_bank`` is ``test`` with every class's
+supports enrolled once per round (``PFENet.enroll`` / ``segment_graphed``).  ``train_head`` trains the head behind the frozen
 trunk (``pemp_amd.train_pfenet``: the reference runs ``layer0 .. layer4`` under ``no_grad``) on synthetic episodes; ``train``, the
 reference's whole procedure on PASCAL-5i, raises."""
 from ..config import Experiment
@@ -58,6 +59,17 @@ def test(_config, split, shot, query, exp_id, ckpt):
     loss, miou, biou = ev.start_eval_loop(data, num_classes(d["dataset"]), split, _config["te"]["epochs"], logger,
                                           batch=d["test_bs"], dataset_name=d["dataset"])
     return f"Loss: {loss:.4f}, mIoU: {np.mean(miou) * 100:.2f}, bIoU: {np.mean(biou) * 100:.2f}"
+
+
+@ex.command
+def test_bank(_config, split, shot, query, exp_id, ckpt):
+    """``python -m pemp_amd.entry.pfenet test_bank with split=0 ckpt=wgen [shot=5]``: ``test`` with the enroll-once protocol
+    (entry.pemp_stage1.BankEvaluator): every class's supports are enrolled once per round into a support bank
+    (``PFENet.enroll``), every query of the round is segmented against its class (``PFENet.segment_graphed``)."""
+    from .pemp_stage1 import run_test_bank
+    if query != 1:
+        raise ValueError("PFENet takes exactly one query per episode (query=1)")
+    return run_test_bank(_config, NAME, lambda logger: ModelClass(shot, logger), split, shot, exp_id, ckpt, wgen_seed=WGEN_SEED)
 
 
 def head_train_batches(trainer, dcfg, shot, split, rank, steps_per_epoch, device):

@@ -237,10 +237,15 @@ class _HeadMixin:
         return dict(family=self._bank_family, backbone=self.backbone_name, precision=self.__dict__.get("_precision", "f32"),
                     p=int(p), c=int(self.feat_channels), dist_scalar=float(dist_scalar))
 
-    def _check_bank(self, bank, what):
+    @staticmethod
+    def _bank_class():
         from ..bank import PrototypeBank
-        if not isinstance(bank, PrototypeBank):
-            raise TypeError(f"{what}: expected a PrototypeBank, got {type(bank).__name__}")
+        return PrototypeBank
+
+    def _check_bank(self, bank, what):
+        cls = self._bank_class()
+        if not isinstance(bank, cls):
+            raise TypeError(f"{what}: expected a {cls.__name__}, got {type(bank).__name__}")
         for k, v in self._bank_desc().items():
             if getattr(bank, k) != v:
                 raise ValueError(f"{what}: the bank was made with {k} = {getattr(bank, k)!r}, this model has {k} = {v!r}")
@@ -281,7 +286,11 @@ class _HeadMixin:
             raise ValueError(f"{what}: ret_ind is a stage-1 option (the response map of its meta-prototypes)")
         if qry_img.dim() != 4:
             raise ValueError(f"{what}: qry_img must be [N,3,H,W], got {tuple(qry_img.shape)}")
+        self._bank_query_check(bank, qry_img, what)
         return None if index is None else ops.bank_index(index, qry_img.shape[0], len(bank))      # checked on the host
+
+    def _bank_query_check(self, bank, qry_img, what):
+        """A family's own rules for the queries a bank may meet (none here)."""
 
     def segment_lowres(self, bank, qry_img, index=None, ret_ind=False):
         """Queries ``qry_img`` [N,3,H,W] against an enrolled bank, at feature resolution: one query-only pass through the
@@ -289,7 +298,7 @@ class _HeadMixin:
         numbers, a Python sequence or a CPU tensor): query b against class index[b] -> pred [N,2,h,w].
         -> (pred, resp uint8 or None)."""
         idx = self._segment_args(bank, qry_img, index, ret_ind, "segment_lowres")
-        self._require_eval_gpu(self, qry_img, bank.protos)
+        self._require_eval_gpu(self, qry_img, *bank.tensors())
         with torch.no_grad():
             return self._segment_dev(bank, qry_img, None if idx is None else idx.to(qry_img.device, non_blocking=True), ret_ind)
 
@@ -310,13 +319,13 @@ class _HeadMixin:
         ``bank.protos`` where it lies -- ``bank.update`` / ``enroll(out=bank)`` need no recapture -- and the index through a
         static int32 buffer.  The returned tensors are the graph's static outputs."""
         idx = self._segment_args(bank, qry_img, index, ret_ind, "segment_graphed")
-        self._require_eval_gpu(self, qry_img, bank.protos)
+        self._require_eval_gpu(self, qry_img, *bank.tensors())
         inputs = [qry_img] if idx is None else [qry_img, idx]
-        key = ("bank", bank.protos.data_ptr()) + tuple((tuple(t.shape), t.dtype) for t in inputs) + \
+        key = ("bank",) + tuple(t.data_ptr() for t in bank.tensors()) + tuple((tuple(t.shape), t.dtype) for t in inputs) + \
               (len(bank), idx is not None, ret_ind, ops.EVAL_SPLITK)
         eng = self._engine_for(qry_img.device)
-        # the graph holds the prototypes' address, the copy into the static index buffer reads host memory: keep both alive
-        eng.setdefault("bank_refs", {})[key] = (bank.protos, idx)
+        # the graph holds the bank's addresses, the copy into the static index buffer reads host memory: keep both alive
+        eng.setdefault("bank_refs", {})[key] = (bank.tensors(), idx)
         run = lambda s: self._segment_dev(bank, s[0], s[1] if idx is not None else None, ret_ind)
         return self._replay(eng, key, inputs, run, run)
 

@@ -112,6 +112,83 @@ class PFENet(_HeadMixin, backbones.BaseModel):
         eng = self._engine_for(sup_img.device)
         return eng["pfenet"].lowres(sup_img, sup_mask, qry_img), None
 
+    # -- support banks (pemp_amd.bank.PFENetBank): enroll supports once, segment many queries --------------------------------
+    # ``segment`` / ``segment_lowres`` / ``segment_graphed`` are _HeadMixin's, with this family's bank and checks.
+    _bank_family = "pfenet"
+    _bank_backbone = "resnet50v2"         # the deep-base ResNet-50 (pretrained_weights above)
+
+    @staticmethod
+    def _bank_class():
+        from ..bank import PFENetBank
+        return PFENetBank
+
+    def _bank_desc(self):
+        return dict(family=self._bank_family, backbone=self._bank_backbone, precision=self.__dict__.get("_precision", "f32"),
+                    S=int(self.shot), C=2048)
+
+    @staticmethod
+    def _check_size(H, W, what):
+        if H != W:
+            raise ValueError(f"{what}: PFENet needs square inputs (its views assume H == W, pfenet.py:204,222,225), got {H}x{W}")
+        if (H - 1) % 8 != 0:
+            raise ValueError(f"{what}: PFENet needs (H - 1) % 8 == 0 (pfenet.py:164), got H = {H}")
+
+    def _bank_query_check(self, bank, qry_img, what):
+        H, W = qry_img.shape[-2:]
+        self._check_size(H, W, what)
+        hw = pfenet_engine.feat_size(H) ** 2
+        if hw != bank.HW:
+            raise ValueError(f"{what}: the bank was enrolled at HW = {bank.HW} feature pixels, a {H}x{W} query has {hw}")
+
+    def enroll(self, sup_img, sup_mask, labels=None, out=None, capacity=None):
+        """Supports of K classes, ``sup_img`` [K,S,3,H,W] and ``sup_mask`` [K,S,2,H,W] (S = ``self.shot``) -> ``PFENetBank``: one
+        supports-only pass through the trunk and the masked layer 4, ``down_supp`` + Weighted GAP, and the pack of the prior's
+        support operand (its foreground rows).  ``capacity``: rows per (class, shot) slot, a multiple of 64; default: the largest
+        count enrolled, rounded up to 64 (one host read of the counts).  ``out``: enroll into that bank (same K) in place --
+        its storage keeps its addresses, so captured graphs that read it see the new classes.  ValueError when a class needs
+        more rows than the capacity, before anything is written."""
+        from ..bank import PFENetBank
+        if out is not None:
+            self._check_bank(out, "enroll(out=)")
+        self._require_eval_gpu(self, sup_img, sup_mask)
+        if sup_img.dim() != 5:
+            raise ValueError(f"enroll: sup_img must be [K,S,3,H,W], got {tuple(sup_img.shape)}")
+        K, S, ch, H, W = sup_img.shape
+        if tuple(sup_mask.shape) != (K, S, 2, H, W):
+            raise ValueError(f"enroll: sup_mask must be [{K},{S},2,{H},{W}], got {tuple(sup_mask.shape)}")
+        if S != self.shot:
+            raise ValueError(f"the model was built for {self.shot} shot(s), got {S}")
+        self._check_size(H, W, "enroll")
+        fs = pfenet_engine.feat_size(H)
+        if out is not None:
+            if len(out) != K or not out.rows.is_cuda:
+                raise ValueError(f"enroll(out=): the bank holds {len(out)} classes on {out.rows.device}, {K} are enrolled")
+            if out.HW != fs * fs:
+                raise ValueError(f"enroll(out=): the bank was enrolled at HW = {out.HW} feature pixels, these supports have {fs * fs}")
+            if capacity is not None and int(capacity) != out.cap:
+                raise ValueError(f"enroll(out=): the bank's capacity is {out.cap}, not {capacity}")
+        elif capacity is not None and (int(capacity) < 64 or int(capacity) % 64):
+            raise ValueError(f"enroll: capacity must be a positive multiple of 64, got {capacity}")
+        eng = self._engine_for(sup_img.device)["pfenet"]
+        with torch.no_grad():
+            counts = eng.support_counts(sup_mask, (fs, fs)).cpu()              # the one host read: enrolment is off the hot path
+            need = int(counts.max())
+            cap = out.cap if out is not None else (-(-need // 64) * 64 if capacity is None else int(capacity))
+            if need > cap:
+                raise ValueError(f"enroll: a class needs {need} rows per shot, the bank's capacity is {cap}")
+            if out is None:
+                rows, norms, count, svec, hw = eng.enroll_supports(sup_img, sup_mask, cap=cap)
+                desc = self._bank_desc()
+                return PFENetBank(rows, norms, count, svec, hw, desc["backbone"], desc["precision"], labels=labels, count_host=counts)
+            eng.enroll_supports(sup_img, sup_mask, out.rows, out.norms, out.count, out.svec)
+            out.count_host.copy_(counts)
+        if labels is not None:
+            out.labels = PFENetBank._labels(labels, K)
+        return out
+
+    def _segment_dev(self, bank, qry_img, index_dev, ret_ind):
+        return self._engine_for(qry_img.device)["pfenet"].segment(bank, qry_img, index_dev), None
+
     def forward(self, sup_img, sup_mask, qry_img, qry_mask=None, out_shape=None):
         """Same contract as the reference's eval forward (pfenet.py:157-287): logits [B,2,Ho,Wo], ``out_shape`` default
         ((H - 1) / 8 * 8 + 1, ...) = (H, W).  ``qry_mask`` is only read by the reference's training loss."""

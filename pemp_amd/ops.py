@@ -1292,6 +1292,145 @@ def prior_mask(qry, sup, mask, S, out=None, ws_cache=None):
     return out
 
 
+def _round64(n):
+    return -(-int(n) // 64) * 64
+
+
+def _prior_bank_masks(mask, K, S):
+    if mask.dim() != 3 or mask.dtype != torch.float32 or not mask.is_contiguous() or mask.shape[0] != K * S or K < 1 or S < 1:
+        raise ValueError(f"prior_bank_pack: mask must be contiguous fp32 [K*S,h,w] with K*S = {K * S}, got {tuple(mask.shape)} "
+                         f"{mask.dtype}")
+
+
+def prior_bank_count(mask, K, S, out=None):
+    """Rows a packed bank slot needs per (class, shot): mask fp32 [K*S,h,w] -> int32 [K,S] on the device (the pixels with
+    m != 0, plus one if a pixel with m == 0 exists).  The count-only form of ``prior_bank_pack``."""
+    _prior_bank_masks(mask, K, S)
+    lib = _lib.load()
+    _chk_dev(mask, out)
+    if out is None:
+        out = torch.empty((K, S), dtype=torch.int32, device=mask.device)
+    if tuple(out.shape) != (K, S) or out.dtype != torch.int32 or not out.is_contiguous():
+        raise ValueError(f"prior_bank_count: out must be contiguous int32 [{K},{S}]")
+    _lib.check(lib.pemp_prior_bank_pack_f32(None, 0, _p(mask), None, None, _p(out), K * S, mask.shape[1] * mask.shape[2], 0, 0,
+                                            _stream()), "prior_bank_count")
+    return out
+
+
+def _prior_bank_store(rows, norms, count, what):
+    """The packed bank's tensors checked -> (K, S, cap, C)."""
+    if rows.dim() != 4 or rows.dtype != torch.float32 or not rows.is_contiguous() or min(rows.shape) < 1:
+        raise ValueError(f"{what}: rows must be contiguous fp32 [K,S,cap,C], got {tuple(rows.shape)} {rows.dtype}")
+    K, S, cap, C = rows.shape
+    if cap % 64:
+        raise ValueError(f"{what}: cap must be a multiple of 64, got {cap}")
+    if C % 32:
+        raise ValueError(f"{what}: C must be a multiple of 32, got {C}")
+    if tuple(norms.shape) != (K, S, cap) or norms.dtype != torch.float32 or not norms.is_contiguous():
+        raise ValueError(f"{what}: norms must be contiguous fp32 [{K},{S},{cap}], got {tuple(norms.shape)} {norms.dtype}")
+    if tuple(count.shape) != (K, S) or count.dtype != torch.int32 or not count.is_contiguous():
+        raise ValueError(f"{what}: count must be contiguous int32 [{K},{S}], got {tuple(count.shape)} {count.dtype}")
+    return K, S, cap, C
+
+
+def prior_bank_pack(sup, mask, K, S, cap=None, rows=None, norms=None, count=None):
+    """The support side of ``prior_mask`` stored per (class, shot): sup NHWC [K*S,h,w,C], mask fp32 [K*S,h,w] ->
+    (rows [K,S,cap,C], norms [K,S,cap], count int32 [K,S]).  Slot (k, s) holds fl(m * s) of the pixels with m != 0 in pixel
+    order, then one all-zero row if a pixel with m == 0 exists; slots beyond ``count`` are not written (a new store is zeroed).
+    A row that does not fit into ``cap`` is dropped and ``count`` says so: compare it with ``cap`` (``cap`` None without
+    ``rows``: h * w rounded up to 64, which always fits)."""
+    lds = _nhwc(sup, "sup")
+    ks, h, w, C = sup.shape
+    _prior_bank_masks(mask, K, S)
+    if tuple(mask.shape) != (ks, h, w):
+        raise ValueError(f"prior_bank_pack: mask {tuple(mask.shape)} does not match sup {tuple(sup.shape)}")
+    if rows is None:
+        cap = _round64(h * w) if cap is None else int(cap)
+        if cap < 64 or cap % 64:
+            raise ValueError(f"prior_bank_pack: cap must be a multiple of 64, got {cap}")
+        if C % 32:
+            raise ValueError(f"prior_bank_pack: C must be a multiple of 32, got {C}")
+        rows = torch.zeros((K, S, cap, C), dtype=torch.float32, device=sup.device)
+        norms = torch.zeros((K, S, cap), dtype=torch.float32, device=sup.device)
+        count = torch.ones((K, S), dtype=torch.int32, device=sup.device)
+    if norms is None or count is None:
+        raise ValueError("prior_bank_pack: rows, norms and count go together")
+    k2, s2, cap, c2 = _prior_bank_store(rows, norms, count, "prior_bank_pack")
+    if (k2, s2) != (K, S) or c2 != C:
+        raise ValueError(f"prior_bank_pack: the store is [K={k2},S={s2},cap,C={c2}], the supports are K={K}, S={S}, C={C}")
+    lib = _lib.load()
+    _chk_dev(sup, mask, rows, norms, count)
+    _lib.check(lib.pemp_prior_bank_pack_f32(_p(sup), lds, _p(mask), _p(rows), _p(norms), _p(count), K * S, h * w, C, cap, _stream()),
+               "prior_bank_pack")
+    return rows, norms, count
+
+
+def prior_bank(qry, rows, norms, count, index=None, out=None, ws_cache=None):
+    """``prior_mask`` of N queries against a packed bank (``prior_bank_pack``): qry NHWC [N,h,w,C].  ``index`` None: every
+    query against every class -> [N,K,h,w]; ``index`` (a Python sequence or a CPU integer tensor [N], checked here against
+    0 <= i < K, then uploaded as int32): query n against class index[n] -> [N,h,w].  [n, k] is bit for bit
+    ``prior_mask(qry[n:n+1], sup[k*S:(k+1)*S], mask[k*S:(k+1)*S], S)[0]`` on the supports class k was packed from."""
+    _prior_bank_shapes(qry, rows, norms, count)
+    if index is not None:
+        index = bank_index(index, qry.shape[0], rows.shape[0])
+    _lib.load()
+    _chk_dev(qry, rows, norms, count, out)
+    if index is not None:
+        index = index.to(qry.device, non_blocking=True)
+    return _prior_bank(qry, rows, norms, count, index, out, ws_cache)
+
+
+def _prior_bank_shapes(qry, rows, norms, count):
+    ldq = _nhwc(qry, "qry")
+    K, S, cap, C = _prior_bank_store(rows, norms, count, "prior_bank")
+    if qry.shape[3] != C:
+        raise ValueError(f"prior_bank: the bank has C = {C}, the features have C = {qry.shape[3]}")
+    return ldq
+
+
+def _prior_bank(qry, rows, norms, count, index_dev, out=None, ws_cache=None):
+    """The launch of ``prior_bank``.  ``index_dev``: None or an int32 DEVICE tensor [N] whose values the caller has checked on
+    the host (``bank_index``) -- the static index buffer of a captured graph comes in here."""
+    ldq = _prior_bank_shapes(qry, rows, norms, count)
+    n, h, w, C = qry.shape
+    K, S, cap = rows.shape[:3]
+    index = index_dev
+    if index is not None and (not isinstance(index, torch.Tensor) or not index.is_cuda or index.dtype != torch.int32
+                              or tuple(index.shape) != (n,) or not index.is_contiguous()):
+        raise ValueError(f"prior_bank: the device index must be a contiguous int32 tensor [{n}] on the GPU")
+    lead = (n,) if index is not None else (n, K)
+    lib = _lib.load()
+    _chk_dev(qry, rows, norms, count, out)
+    if out is None:
+        out = torch.empty(lead + (h, w), dtype=torch.float32, device=qry.device)
+    if tuple(out.shape) != lead + (h, w) or not out.is_contiguous():
+        raise ValueError(f"prior_bank: out must be contiguous {list(lead + (h, w))}")
+    pairs = n if index is not None else n * K
+    ws = _ws(lib.pemp_prior_bank_workspace_bytes(pairs, S, h * w), qry.device, ws_cache, ("prior_bank", pairs, S, h * w))
+    _lib.check(lib.pemp_prior_bank_f32(_p(qry), ldq, _p(rows), _p(norms), _p(count), _p(index), _p(out), _p(ws), ws.numel(), n, K, S,
+                                       h * w, C, cap, _stream()), "prior_bank")
+    return out
+
+
+def bank_gather_rows(src, index_dev, n, out=None):
+    """Rows of a contiguous fp32 table src [K,C] by a bank's selection: ``index_dev`` int32 [n] on the device -> [n,C] =
+    src[index[i]]; None -> [n,K,C], every row for every one of the n queries."""
+    if src.dim() != 2 or src.dtype != torch.float32 or not src.is_contiguous():
+        raise ValueError(f"bank_gather_rows: src must be contiguous fp32 [K,C], got {tuple(src.shape)} {src.dtype}")
+    K, C = src.shape
+    if index_dev is not None and (index_dev.dtype != torch.int32 or tuple(index_dev.shape) != (n,) or not index_dev.is_contiguous()):
+        raise ValueError(f"bank_gather_rows: the device index must be contiguous int32 [{n}]")
+    lead = (n,) if index_dev is not None else (n, K)
+    lib = _lib.load()
+    _chk_dev(src, index_dev, out)
+    if out is None:
+        out = torch.empty(lead + (C,), dtype=torch.float32, device=src.device)
+    if tuple(out.shape) != lead + (C,) or not out.is_contiguous():
+        raise ValueError(f"bank_gather_rows: out must be contiguous {list(lead + (C,))}")
+    _lib.check(lib.pemp_bank_gather_rows_f32(_p(src), _p(index_dev), _p(out), n, K, C, _stream()), "bank_gather_rows")
+    return out
+
+
 def adaptive_avgpool(x, size, out=None):
     """nn.AdaptiveAvgPool2d(size) on an NHWC view (``out``: an NHWC view, e.g. a channel slice of a wider buffer)."""
     lib = _lib.load()

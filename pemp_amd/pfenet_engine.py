@@ -15,6 +15,11 @@ Layout choices:
 - the 256 -> 2 classifier conv is packed with 62 zero output channels (Cout % 64), its two live channels resized into the
   [B,2,h,w] logits in one pass;
 - ``inner_cls`` (:266) feeds only the training loss (:276-285): not run.
+
+Support banks (``pemp_amd.bank.PFENetBank``): everything the supports contribute -- their trunk passes, the masked layer 4,
+``down_supp`` + Weighted GAP and the masked, normalised support operand of the prior GEMM -- depends on them alone.
+``enroll_supports`` runs that side once and packs the prior operand (foreground rows only); ``segment`` runs the query side
+against the bank.  Both make the launches ``lowres`` makes on the same rows, so the results agree with it bit for bit.
 """
 import torch
 
@@ -25,6 +30,13 @@ from .ops import ConvParams
 PYRAMID_BINS = (60, 30, 15, 8)
 REDUCE = 256
 MERGE_CIN = REDUCE + 32                 # query channels + the prior channel, zero-padded to a multiple of 32
+
+
+def feat_size(H):
+    """Side of the layer-2 .. layer-4 maps for an H x H input: the stem's stride-2 conv, the max-pool, layer 2's stride."""
+    for _ in range(3):
+        H = ops.conv_out_size(H, 3, 2, 1, 1)
+    return H
 
 
 class DeepBaseResNetEngine(_BottleneckTrunk):
@@ -90,37 +102,107 @@ class PFENetEngine:
         self.cls3 = classifier2(model.cls[3])
         self._ones = set()
 
-    def lowres(self, sup_img, sup_mask, qry_img):
-        """sup_img [B,S,3,H,W], sup_mask [B,S,2,H,W] (plane 0: foreground), qry_img [B,1,3,H,W] on the device."""
+    # lowres() is three stages, each of them the same launches whether an episode's supports and queries pass together
+    # (lowres) or apart (enroll_supports / segment: support banks, pemp_amd.bank.PFENetBank): _layer4 (trunk, mask resize,
+    # masked layer 4) on any mix of ns supports and nq queries, _support_vector, and _tail (down_query + FEM + classifier).
+
+    def _layer4(self, groups, sup_mask, ns):
+        """``groups``: image groups (the ns supports first) -> (cat23 [n,h,w,1536], mfeat [n,h,w], f4 [n,h,w,2048])."""
         a = self.arena
-        B, S, ch, H, W = sup_img.shape
-        ns, n = B * S, B * S + B
-        x4 = pack_episode(a, (sup_img.flatten(0, 1), qry_img.flatten(0, 1)))
+        x4 = pack_episode(a, groups)
+        n, H, W = x4.shape[:3]
         cat23 = self.trunk.forward_to_layer3(x4)                                 # [n,h,w,1536]
         h, w = cat23.shape[1:3]
         # support masks at feature resolution (:182-185, == 1 then bilinear align_corners), the queries' rows = 1
-        mfeat = a.get("pf_mfeat", (n, h, w))
+        mfeat = a.get(("pf_mfeat", ns), (n, h, w))
         if mfeat.data_ptr() not in self._ones:
             mfeat[ns:].fill_(1.0)
             self._ones.add(mfeat.data_ptr())
-        fg = sup_mask.reshape(ns, 2, H, W)[:, 0].unsqueeze(-1)
-        ops.resize_bilinear_ac(fg, (h, w), out=mfeat[:ns].unsqueeze(-1), binarize=True)
+        if ns:
+            fg = sup_mask.reshape(ns, 2, H, W)[:, 0].unsqueeze(-1)
+            ops.resize_bilinear_ac(fg, (h, w), out=mfeat[:ns].unsqueeze(-1), binarize=True)
         # layer 4 over layer3 * mask (:193; the queries' layer 4 of :171 is the same chain on their unmasked rows)
         x4in = ops.scale_add(cat23[..., :1024], mask=mfeat, out=a.get("pf_l4in", (n, h, w, 1024)))
         f4 = self.trunk.layer4(x4in, a.get("pf_l4", (n, h, w, 2048)))
+        return cat23, mfeat, f4
+
+    def _support_vector(self, cat23_s, mfeat_s, S, out):
+        """down_supp (:195-196) and the Weighted-GAP support vector (:197,229-233) of ns = B * S supports -> ``out`` [B,256]."""
+        ns, h, w = mfeat_s.shape
+        dsup = ops.conv2d(cat23_s, self.down_s, out=self.arena.get("pf_ds", (ns, h, w, REDUCE)))
+        return ops.weighted_gap(dsup, mfeat_s, S, out=out)
+
+    def lowres(self, sup_img, sup_mask, qry_img):
+        """sup_img [B,S,3,H,W], sup_mask [B,S,2,H,W] (plane 0: foreground), qry_img [B,1,3,H,W] on the device."""
+        a = self.arena
+        B, S = sup_img.shape[:2]
+        ns = B * S
+        cat23, mfeat, f4 = self._layer4((sup_img.flatten(0, 1), qry_img.flatten(0, 1)), sup_mask, ns)
+        h, w = cat23.shape[1:3]
         self.last_layer4 = f4
         prior = ops.prior_mask(f4[ns:], f4[:ns], mfeat[:ns], S, out=a.get("pf_prior", (B, h, w)), ws_cache=a.ws)
         self.last_prior = prior
-        # down_query / down_supp (:175-176,195-196) and the support vector (:197,229-233)
+        # down_query (:175-176) comes first in _tail; down_supp and the support vector after it, as ever
         dq = ops.conv2d(cat23[ns:], self.down_q, out=a.get("pf_dq", (B, h, w, REDUCE)))
-        dsup = ops.conv2d(cat23[:ns], self.down_s, out=a.get("pf_ds", (ns, h, w, REDUCE)))
-        svec = ops.weighted_gap(dsup, mfeat[:ns], S, out=a.get("pf_svec", (B, REDUCE)))
+        svec = self._support_vector(cat23[:ns], mfeat[:ns], S, a.get("pf_svec", (B, REDUCE)))
         self.last_supp_vec = svec
+        return self._tail(dq, prior, svec, 1)
+
+    def enroll_supports(self, sup_img, sup_mask, rows=None, norms=None, count=None, svec=None, cap=None):
+        """The support side of ``lowres`` for K classes: sup_img [K,S,3,H,W], sup_mask [K,S,2,H,W] -> (rows, norms, count, svec,
+        HW): the packed prior operand (``ops.prior_bank_pack``) and the support vectors [K,256], written into the given
+        tensors (a bank's storage) or into new ones with ``cap`` rows per slot.  The caller has made sure that every class fits
+        (``support_counts``)."""
+        K, S = sup_img.shape[:2]
+        cat23, mfeat, f4 = self._layer4((sup_img.flatten(0, 1),), sup_mask, K * S)
+        if svec is None:
+            svec = torch.empty((K, REDUCE), dtype=torch.float32, device=f4.device)
+        self._support_vector(cat23, mfeat, S, svec)
+        rows, norms, count = ops.prior_bank_pack(f4, mfeat, K, S, cap=cap, rows=rows, norms=norms, count=count)
+        return rows, norms, count, svec, f4.shape[1] * f4.shape[2]
+
+    def support_counts(self, sup_mask, feat_hw):
+        """Rows every (class, shot) needs in a bank slot, before anything else runs: sup_mask [K,S,2,H,W] -> int32 [K,S] (device)."""
+        K, S, _, H, W = sup_mask.shape
+        mfeat = self.arena.get(("pf_mcount", K * S), (K * S,) + tuple(feat_hw))
+        ops.resize_bilinear_ac(sup_mask.reshape(K * S, 2, H, W)[:, 0].unsqueeze(-1), tuple(feat_hw), out=mfeat.unsqueeze(-1),
+                               binarize=True)
+        return ops.prior_bank_count(mfeat, K, S)
+
+    def segment(self, bank, qry_img, index_dev):
+        """The query side of ``lowres`` against a ``PFENetBank``: qry_img [N,3,H,W]; ``index_dev`` int32 [N] on the device
+        (query n meets class index[n]) -> logits [N,2,h,w]; None (every query meets every class) -> [N,K,2,h,w]."""
+        a = self.arena
+        N, K = qry_img.shape[0], len(bank)
+        cat23, _, f4 = self._layer4((qry_img,), None, 0)
+        h, w = cat23.shape[1:3]
+        lead = (N,) if index_dev is not None else (N, K)
+        prior = ops._prior_bank(f4, bank.rows, bank.norms, bank.count, index_dev, out=a.get("pf_bprior", lead + (h, w)), ws_cache=a.ws)
+        self.last_bank_prior = prior
+        dq = ops.conv2d(cat23, self.down_q, out=a.get("pf_dq", (N, h, w, REDUCE)))
+        svec = ops.bank_gather_rows(bank.svec, index_dev, N, out=a.get("pf_bsvec", lead + (REDUCE,)))
+        rep = 1 if index_dev is not None else K
+        pred = self._tail(dq, prior.view(N * rep, h, w), svec.view(N * rep, REDUCE), rep)
+        return pred.view(lead + tuple(pred.shape[1:]))
+
+    def _tail(self, dq, prior, svec, rep):
+        """The FEM (:238-268) and the classifier over P = N * rep (query, class) pairs: dq [N,h,w,256] (down_query, per query),
+        prior [P,h,w], svec [P,256], pair n * rep + k = query n.  What depends on the query alone -- the four adaptive pools of
+        dq -- runs once per query; rep > 1 copies it to the query's pairs."""
+        a = self.arena
+        N, h, w, _ = dq.shape
+        B = N * rep
         res1_in = a.get("pf_res1_in", (B, h, w, REDUCE * len(PYRAMID_BINS)))
         self.last_bins = []
         for idx, bn in enumerate(PYRAMID_BINS):                                  # FEM (:238-268)
             inp = a.get(("pf_mrg_in", idx), (B, bn, bn, MERGE_CIN), zero=True)  # channels 257.. stay zero
-            ops.adaptive_avgpool(dq, bn, out=inp[..., :REDUCE])
+            if rep == 1:
+                ops.adaptive_avgpool(dq, bn, out=inp[..., :REDUCE])
+            else:
+                pooled = ops.adaptive_avgpool(dq, bn, out=a.get(("pf_dqpool", idx), (N, bn, bn, REDUCE)))
+                per_query = inp.view(N, rep, bn, bn, MERGE_CIN)
+                for k in range(rep):                                             # identity resize: an exact strided copy
+                    ops.resize_bilinear_ac(pooled, bn, out=per_query[:, k, :, :, :REDUCE])
             ops.resize_bilinear_ac(prior.unsqueeze(-1), bn, out=inp[..., REDUCE:REDUCE + 1])
             self.last_bins.append(inp[..., REDUCE])
             shift = ops.conv2d(svec.view(B, 1, 1, REDUCE), self.merge_s[idx], out=a.get(("pf_mrg_s", idx), (B, 1, 1, REDUCE)))
