@@ -773,6 +773,22 @@ int pemp_rpmms_prob_map_f32(const float* qry, int ldq, const float* mu, float* o
  * query half of the weights, no bias, no ReLU.  C == 256.                                                                */
 int pemp_rpmms_proto_sum_f32(const float* wz, const float* mu, const float* base, int ldb, const float* bias, float* T,
                              float* out, int ldo, long long gstride, int B, int h, int w, int C, int dil, void* stream);
+/* RPMMs support banks.  The first launch of pemp_rpmms_proto_sum_f32 on its own, for K classes:
+ * T[k][i][tap][co] = sum_ci wz[tap][co][ci] mu[k][0][i][ci].   wz [9][C][C], mu [K][2][10][C], T [K][10][9][C].  C == 256. */
+int pemp_rpmms_proto_taps_f32(const float* wz, const float* mu, float* T, int K, int C, void* stream);
+/* layer56's input for P (query, class) pairs in ONE launch.  qry: layer5 of the queries, NHWC [N][h*w][C] (ldq).  base: their
+ * conv with the query half of layer55, NHWC (ldb), no bias, no ReLU.  mu [K][2][10][C], T [K][10][9][C] as above.
+ *   index NULL:                P = N * K, pair n * K + k is query n against class k
+ *   index (device int32 [N]):  P = N, pair n is query n against class index[n] (values checked by the caller on the host)
+ * For mixture g = 0..2 and pair r:
+ *   out[g * gstride + (r * h * w + p) * ldo + c], c < C = pemp_rpmms_proto_sum_f32's value for (base[n], bias, T[k])
+ *   out[... + C] = P_b, out[... + C + 1] = P_f          = pemp_rpmms_prob_map_f32's values for (qry[n], mu[k])
+ * bit for bit; channels C + 2 .. ldo - 1 are not written.  A block walks the classes of its query's 16-pixel chunk with the
+ * chunk's qry and base rows in LDS: they are read once per pixel, not once per class.  ldq, ldb, ldo, gstride % 4 == 0, ldo >= C + 2, operands 16-byte aligned,
+ * N * K <= 65535.  C == 256.                                                                                                */
+int pemp_rpmms_bank_l56_f32(const float* qry, int ldq, const float* base, int ldb, const float* bias, const float* mu,
+                            const float* T, const int32_t* index, float* out, int ldo, long long gstride, int N, int K, int h,
+                            int w, int C, int dil, void* stream);
 
 /* ---- RPMMs head training (csrc/rpmms_bwd.hip): layer55 over the ten prototype columns with one Dropout2d draw per column, its
  * adjoint, and the adjoint of the softmax that makes the next pass's history.  No atomics; the one cross-block sum goes through

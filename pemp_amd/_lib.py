@@ -181,6 +181,8 @@ SYMBOLS = {
     "pemp_rpmms_em_f32": (c_int, [c_fp, c_int, c_fp, c_fp, c_fp, c_fp] + [c_int] * 5 + [c_fp]),
     "pemp_rpmms_prob_map_f32": (c_int, [c_fp, c_int, c_fp, c_fp, c_int, C.c_longlong, c_int, c_int, c_int, c_fp]),
     "pemp_rpmms_proto_sum_f32": (c_int, [c_fp, c_fp, c_fp, c_int, c_fp, c_fp, c_fp, c_int, C.c_longlong] + [c_int] * 5 + [c_fp]),
+    "pemp_rpmms_proto_taps_f32": (c_int, [c_fp, c_fp, c_fp, c_int, c_int, c_fp]),
+    "pemp_rpmms_bank_l56_f32": (c_int, [c_fp, c_int, c_fp, c_int, c_fp, c_fp, c_fp, c_fp, c_fp, c_int, C.c_longlong] + [c_int] * 6 + [c_fp]),
     "pemp_rpmms_proto_sum_train_f32": (c_int, [c_fp, c_fp, c_fp, c_int, c_fp, c_fp, c_fp, c_fp, c_int, C.c_longlong] + [c_int] * 5 + [c_fp]),
     "pemp_rpmms_proto_sum_bwd_work_floats": (c_size, [c_int] * 4),
     "pemp_rpmms_proto_sum_bwd_f32": (c_int, [c_fp, c_int, C.c_longlong, c_fp, c_int, c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_fp, c_fp, c_int,

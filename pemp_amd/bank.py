@@ -8,9 +8,10 @@ first) together with what a query pass must agree with: the model family, its ba
 ``p``, ``c`` and ``dist_scalar``.
 
 PFENet's head conditions on the query, its support side does not: ``PFENetBank`` keeps that side -- the packed support operand
-of the prior GEMM and the support vectors -- with the same services.  Both classes offer ``empty_like`` (an empty K-slot sibling
-of a one-class bank), ``holds`` and ``tensors`` to the code that serves either (``entry.pemp_stage1.BankEvaluator``,
-``_HeadMixin.segment_graphed``)."""
+of the prior GEMM and the support vectors -- with the same services; ``RPMMsBank`` keeps what RPMMs' support side ends in, the
+prototypes of the mixture models and their products with ``layer55``.  All classes offer ``empty_like`` (an empty K-slot
+sibling of a one-class bank), ``holds`` and ``tensors`` to the code that serves any of them
+(``entry.pemp_stage1.BankEvaluator``, ``_HeadMixin.segment_graphed``)."""
 import torch
 
 _FIELDS = ("family", "backbone", "precision", "p", "c", "dist_scalar")
@@ -247,5 +248,119 @@ class PFENetBank:
     def require_like(self, other, what):
         """ValueError unless ``other`` was made by the same backbone / precision with the same S, HW and C."""
         for f in _PF_FIELDS:
+            if getattr(self, f) != getattr(other, f):
+                raise ValueError(f"{what}: bank mismatch in {f}: {getattr(other, f)!r} against {getattr(self, f)!r}")
+
+
+_RP_FIELDS = ("family", "backbone", "precision", "C")
+_RP_COLS = 10          # ops.RPMMS_COLS: the three mixtures K = 1 | 3 | 6 side by side
+
+
+class RPMMsBank:
+    """RPMMs' support bank.  Everything an episode's support contributes -- its trunk pass, ``layer5``, the mask resize and the
+    ten-iteration PMMs EM -- ends in ``mu`` [K,2,10,C] (side 0: foreground, 1: background; ``ops.rpmms_em``); ``taps`` [K,10,9,C]
+    are the products of the foreground prototypes with the prototype half of ``layer55`` (``ops.rpmms_proto_taps``).  112 KB per
+    class at C = 256.
+
+    ``mu`` and ``taps`` belong to the weights and to the ``pmm_mu0`` that were current at enrolment: a model whose weights
+    change, or whose initial mu is redrawn, does not change an enrolled bank.  The bank holds nothing that depends on the image
+    size: queries of any size the trunk takes may meet it, whatever size its supports had."""
+    family = "rpmms"
+    _labels = staticmethod(PrototypeBank._labels)
+
+    def __init__(self, mu, taps, backbone, precision, labels=None):
+        if mu.dim() != 4 or mu.dtype != torch.float32 or mu.shape[0] < 1 or tuple(mu.shape[1:3]) != (2, _RP_COLS) or mu.shape[3] < 1:
+            raise ValueError(f"RPMMsBank: mu must be fp32 [K,2,{_RP_COLS},C], got {tuple(mu.shape)} {mu.dtype}")
+        K, C = int(mu.shape[0]), int(mu.shape[3])
+        if tuple(taps.shape) != (K, _RP_COLS, 9, C) or taps.dtype != torch.float32:
+            raise ValueError(f"RPMMsBank: taps must be fp32 [{K},{_RP_COLS},9,{C}], got {tuple(taps.shape)} {taps.dtype}")
+        if taps.device != mu.device:
+            raise ValueError("RPMMsBank: mu and taps must lie on one device")
+        self.mu, self.taps = mu.contiguous(), taps.contiguous()
+        self.C = C
+        self.backbone, self.precision = str(backbone), str(precision)
+        self.labels = self._labels(labels, K)
+
+    def __len__(self):
+        return int(self.mu.shape[0])
+
+    def __repr__(self):
+        return f"RPMMsBank(K={len(self)}, C={self.C}, {self.family}/{self.backbone}/{self.precision}, device={self.mu.device})"
+
+    def nbytes(self):
+        """Bytes of device storage per class."""
+        return sum(t.numel() * t.element_size() for t in self.tensors()) // len(self)
+
+    def tensors(self):
+        """The device storage a captured graph reads."""
+        return (self.mu, self.taps)
+
+    @classmethod
+    def empty_like(cls, one, k, labels=None):
+        """A bank of ``k`` empty (all-zero) slots for classes enrolled like ``one``."""
+        dev, k = one.mu.device, int(k)
+        return cls(torch.zeros((k, 2, _RP_COLS, one.C), dtype=torch.float32, device=dev),
+                   torch.zeros((k, _RP_COLS, 9, one.C), dtype=torch.float32, device=dev), one.backbone, one.precision, labels=labels)
+
+    def holds(self, one):
+        """Whether a class enrolled as ``one`` fits a slot of this bank."""
+        return isinstance(one, RPMMsBank) and self.C == one.C
+
+    # -- persistence: plain tensors, ints and strings -------------------------------------------------------------
+    def state_dict(self):
+        sd = {k: getattr(self, k) for k in _RP_FIELDS}
+        sd["mu"], sd["taps"] = self.mu.detach().clone(), self.taps.detach().clone()
+        sd["labels"] = None if self.labels is None else list(self.labels)
+        return sd
+
+    @classmethod
+    def from_state_dict(cls, sd, device=None):
+        if sd.get("family") != cls.family:
+            raise ValueError(f"RPMMsBank: the saved bank's family is {sd.get('family')!r}")
+        mv = (lambda t: t.clone()) if device is None else (lambda t: t.to(device, copy=True))
+        return cls(mv(sd["mu"]), mv(sd["taps"]), sd["backbone"], sd["precision"], sd.get("labels"))
+
+    def load_state_dict(self, sd):
+        """In place: the saved bank must have this bank's shape (``from_state_dict`` makes a new one)."""
+        if tuple(sd["mu"].shape) != tuple(self.mu.shape) or tuple(sd["taps"].shape) != tuple(self.taps.shape) \
+                or sd.get("family") != self.family:
+            raise ValueError(f"RPMMsBank: saved mu {tuple(sd['mu'].shape)} ({sd.get('family')!r}) does not fit this bank's "
+                             f"{tuple(self.mu.shape)}")
+        self.mu.copy_(sd["mu"])
+        self.taps.copy_(sd["taps"])
+        self.backbone, self.precision = str(sd["backbone"]), str(sd["precision"])
+        self.labels = self._labels(sd.get("labels"), len(self))
+        return self
+
+    def to(self, device):
+        """A bank on ``device`` (this one if it is there already)."""
+        if self.mu.device == torch.device(device):
+            return self
+        return RPMMsBank(self.mu.to(device), self.taps.to(device), self.backbone, self.precision, self.labels)
+
+    # -- in-place updates: a captured graph that reads the bank sees them -------------------------------------------
+    def update(self, k, other, label=None):
+        """Class ``k`` <- ``other``, a one-class bank made by the same kind of model.  Copies into the bank's own storage."""
+        if not 0 <= int(k) < len(self):
+            raise IndexError(f"RPMMsBank.update: class {k} of a bank of {len(self)}")
+        if not isinstance(other, RPMMsBank):
+            raise TypeError(f"RPMMsBank.update: expected an RPMMsBank, got {type(other).__name__}")
+        self.require_like(other, "RPMMsBank.update")
+        if len(other) != 1:
+            raise ValueError(f"RPMMsBank.update: the source bank must hold one class, it holds {len(other)}")
+        k = int(k)
+        self.mu[k].copy_(other.mu[0])
+        self.taps[k].copy_(other.taps[0])
+        if label is None and other.labels is not None:
+            label = other.labels[0]
+        if label is not None:
+            if self.labels is None:
+                raise ValueError("RPMMsBank.update: this bank has no labels")
+            self.labels[k] = int(label)
+        return self
+
+    def require_like(self, other, what):
+        """ValueError unless ``other`` was made by the same backbone / precision with the same C."""
+        for f in _RP_FIELDS:
             if getattr(self, f) != getattr(other, f):
                 raise ValueError(f"{what}: bank mismatch in {f}: {getattr(other, f)!r} against {getattr(self, f)!r}")

@@ -318,6 +318,103 @@ __global__ __launch_bounds__(256) void proto_sum_kernel(const float* __restrict_
     }
 }
 
+// layer56's input of (query, class) pairs against a bank of K classes: prob_map_kernel and proto_sum_kernel in one walk.  Both
+// give a pixel to a wave and the channels 4 l .. 4 l + 3 to lane l, so a wave makes all 258 channels of its pixel from one read
+// of the query's layer5 row and one of its base row.  grid (chunks of BL_PIX pixels, N): a block keeps its chunk's rows in
+// LDS (BL_PIX / 4 pixels per wave, 32 KB) and walks its query's classes -- all K of them (index == nullptr, pair n * K + k) or
+// the one class index[n] (pair n); per class it reloads the 20 mu rows into LDS and the ten all-taps sums into registers.  Every
+// arithmetic statement is the one of the two episode kernels, in their order: a pair's bits are theirs on (qry[n], base[n],
+// mu[k], T[k]) and do not depend on N, K or the pair's place.
+constexpr int BL_PIX = 16, BL_PER_WAVE = BL_PIX / 4;
+__global__ __launch_bounds__(256) void bank_l56_kernel(const float* __restrict__ qry, int ldq, const float* __restrict__ base, int ldb,
+                                                       const float* __restrict__ bias, const float* __restrict__ mu,
+                                                       const float* __restrict__ T, const int* __restrict__ index,
+                                                       float* __restrict__ out, int ldo, long long gstride, int K, int h, int w,
+                                                       int dil) {
+    __shared__ float4 mus[2 * RP_J][RP_C / 4];
+    __shared__ float4 rows[4][BL_PER_WAVE][2][RP_C / 4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n = blockIdx.y, HW = h * w, c = 4 * lane;
+    const int p0 = blockIdx.x * BL_PIX + wave, p_end = min((blockIdx.x + 1) * BL_PIX, HW);
+    // the chunk's rows, read once: lane l parks its float4s of the wave's pixels in LDS (its own slots: no barrier) and takes
+    // them back per class; in registers they would cost the class loop its occupancy
+    const float4 bv = ld4(bias + c);
+    for (int s = 0; s < BL_PER_WAVE; ++s) {
+        const size_t px = (size_t)n * HW + min(p0 + 4 * s, HW - 1);
+        rows[wave][s][0][lane] = ld4(qry + px * ldq + c);
+        rows[wave][s][1][lane] = add4(ld4(base + px * ldb + c), bv);
+    }
+    const int k_first = index ? index[n] : 0, k_last = index ? k_first + 1 : K;
+    for (int k = k_first; k < k_last; ++k) {
+        const float* mb = mu + (size_t)k * 2 * RP_J * RP_C;
+        __syncthreads();                                     // the class before is read out
+        for (int i = tid; i < 2 * RP_J * RP_C / 4; i += 256) mus[i / (RP_C / 4)][i % (RP_C / 4)] = ld4(mb + 4 * i);
+        __syncthreads();
+        const float* Tk = T + (size_t)k * RP_J * 9 * RP_C + c;
+        float4 full[RP_J];
+#pragma unroll
+        for (int i = 0; i < RP_J; ++i) full[i] = full_taps(Tk + (size_t)i * 9 * RP_C);
+        const size_t r = index ? (size_t)n : (size_t)n * K + k;
+#pragma unroll 1
+        for (int s = 0; s < BL_PER_WAVE; ++s) {
+            const int p = p0 + 4 * s;
+            if (p >= p_end) break;                           // wave-uniform
+            float* op = out + (r * HW + p) * ldo;
+            const float4 bb = rows[wave][s][1][lane];
+            {   // proto_sum_kernel's pixel
+                const int y = p / w, x = p - y * w;
+                const bool interior = y >= dil && y + dil < h && x >= dil && x + dil < w;
+                float4 g0, g1, g2;
+#pragma unroll
+                for (int i = 0; i < RP_J; ++i) {
+                    float4 R = full[i];
+                    if (!interior) R = border_taps(Tk + (size_t)i * 9 * RP_C, y, x, h, w, dil);
+                    const float4 v = relu4(add4(bb, R));
+                    if (i == 0) g0 = v;
+                    else if (i == 1) g1 = v;
+                    else if (i < 4) g1 = add4(g1, v);
+                    else if (i == 4) g2 = v;
+                    else g2 = add4(g2, v);
+                }
+                *(float4*)(op + c) = g0;
+                *(float4*)(op + c + gstride) = g1;
+                *(float4*)(op + c + 2 * gstride) = g2;
+            }
+            {   // prob_map_kernel's pixel
+                const float4 v = rows[wave][s][0][lane];
+                float d[2 * RP_J];
+#pragma unroll
+                for (int m = 0; m < 2 * RP_J; ++m) {
+                    const float4 a = mus[m][lane];
+                    d[m] = wave_sum(__fmaf_rn(a.w, v.w, __fmaf_rn(a.z, v.z, __fmaf_rn(a.y, v.y, __fmul_rn(a.x, v.x)))));
+                }
+                if (lane < 3) {
+                    const int j0 = group_first(lane), Kg = group_size(lane);
+                    float mx = d[0];
+#pragma unroll
+                    for (int m = 0; m < 2 * RP_J; ++m) {
+                        const int j = m < RP_J ? m : m - RP_J;
+                        if (j >= j0 && j < j0 + Kg) mx = (m == j0) ? d[m] : fmaxf(mx, d[m]);
+                    }
+                    float sf = 0.f, sb = 0.f;
+#pragma unroll
+                    for (int m = 0; m < 2 * RP_J; ++m) {
+                        const int j = m < RP_J ? m : m - RP_J;
+                        if (j >= j0 && j < j0 + Kg) {
+                            const float e = expf(__fsub_rn(d[m], mx));
+                            if (m < RP_J) sf = __fadd_rn(sf, e);
+                            else sb = __fadd_rn(sb, e);
+                        }
+                    }
+                    const float den = __fadd_rn(sf, sb);
+                    float* pp = op + (size_t)lane * gstride + RP_C;
+                    pp[0] = __fdiv_rn(sb, den);
+                    pp[1] = __fdiv_rn(sf, den);
+                }
+            }
+        }
+    }
+}
+
 int em_blocks(int HW) { return std::min(RP_GMAX, cdiv(HW, 64)); }
 
 }  // namespace
@@ -371,4 +468,31 @@ extern "C" int pemp_rpmms_proto_sum_f32(const float* wz, const float* mu, const 
     hipLaunchKernelGGL(proto_sum_kernel, dim3(cdiv(h * w, PS_PIX), B), dim3(256), 0, st, base, ldb, bias, (const float*)T, out, ldo,
                        gstride, h, w, dil);
     return launch_status("rpmms_proto_sum");
+}
+
+extern "C" int pemp_rpmms_proto_taps_f32(const float* wz, const float* mu, float* T, int K, int C, void* stream) {
+    PEMP_REQUIRE(wz && mu && T, "rpmms_proto_taps: null pointer");
+    PEMP_REQUIRE(K > 0 && K <= 65535, "rpmms_proto_taps: bad sizes");
+    PEMP_REQUIRE(C == RP_C, "rpmms_proto_taps: the kernels are built for C = 256");
+    PEMP_REQUIRE(aligned16(wz) && aligned16(mu) && aligned16(T), "rpmms_proto_taps: operands 16-byte aligned");
+    const int rows = 9 * C;
+    hipLaunchKernelGGL(tap_gemv_kernel, dim3(cdiv(rows, 4), K), dim3(256), 0, (hipStream_t)stream, wz, mu, T, rows);
+    return launch_status("rpmms_proto_taps");
+}
+
+extern "C" int pemp_rpmms_bank_l56_f32(const float* qry, int ldq, const float* base, int ldb, const float* bias, const float* mu,
+                                       const float* T, const int* index, float* out, int ldo, long long gstride, int N, int K,
+                                       int h, int w, int C, int dil, void* stream) {
+    PEMP_REQUIRE(qry && base && bias && mu && T && out, "rpmms_bank_l56: null pointer");
+    PEMP_REQUIRE(N > 0 && K > 0 && (long long)N * K <= 65535 && h > 0 && w > 0 && (long long)h * w < (1 << 24) && dil > 0,
+                 "rpmms_bank_l56: bad sizes (N, K >= 1, N * K <= 65535)");
+    PEMP_REQUIRE(C == RP_C, "rpmms_bank_l56: the kernels are built for C = 256");
+    PEMP_REQUIRE(ldq >= C && ldq % 4 == 0 && ldb >= C && ldb % 4 == 0 && ldo >= C + 2 && ldo % 4 == 0 && gstride >= 0 &&
+                     gstride % 4 == 0,
+                 "rpmms_bank_l56: ldq, ldb, ldo and gstride must be multiples of 4, ldq / ldb >= C, ldo >= C + 2");
+    PEMP_REQUIRE(aligned16(qry) && aligned16(base) && aligned16(bias) && aligned16(mu) && aligned16(T) && aligned16(out),
+                 "rpmms_bank_l56: operands 16-byte aligned");
+    hipLaunchKernelGGL(bank_l56_kernel, dim3(cdiv(h * w, BL_PIX), N), dim3(256), 0, (hipStream_t)stream, qry, ldq, base, ldb, bias, mu,
+                       T, index, out, ldo, gstride, K, h, w, dil);
+    return launch_status("rpmms_bank_l56");
 }

@@ -420,10 +420,11 @@ class BankEvaluator(Evaluator):
         return self.test_step_batch(episodes)
 
 
-def run_test_bank(_config, name, model_class, split, shot, exp_id, ckpt, seed=None, **load_kw):
+def run_test_bank(_config, name, model_class, split, shot, exp_id, ckpt, seed=None, evaluator=None, loss_label="Loss", **load_kw):
     """Body of the ``test_bank`` commands: ``test`` with the enroll-once protocol (``BankEvaluator``).  Same checkpoint
     lookup, same episode source (``data.base_dir`` or synthetic), same result string; no configuration key of its own.
-    ``model_class(logger)`` makes the model, ``load_kw`` goes to ``load_for_eval`` (PFENet's Wgen seed)."""
+    ``model_class(logger)`` makes the model, ``load_kw`` goes to ``load_for_eval`` (PFENet's Wgen seed).  ``evaluator``: the
+    evaluator class (default ``BankEvaluator``), ``loss_label``: the name of the loss in the result line (RPMMs: ``Loss_p1``)."""
     import logging
     logging.basicConfig(level=logging.INFO, format="%(message)s")
     logger = logging.getLogger(name)
@@ -437,10 +438,10 @@ def run_test_bank(_config, name, model_class, split, shot, exp_id, ckpt, seed=No
     model = model.cuda().eval()
     dcfg = _config["data"]
     data = eval_episodes(dcfg, shot, split)
-    ev = BankEvaluator(model)
+    ev = (BankEvaluator if evaluator is None else evaluator)(model)
     loss, miou, biou = ev.start_eval_loop(data, num_classes(dcfg["dataset"]), split, _config["te"]["epochs"], logger,
                                           batch=dcfg["test_bs"], dataset_name=dcfg["dataset"])
-    return f"Loss: {loss:.4f}, mIoU: {np.mean(miou) * 100:.2f}, bIoU: {np.mean(biou) * 100:.2f}"
+    return f"{loss_label}: {loss:.4f}, mIoU: {np.mean(miou) * 100:.2f}, bIoU: {np.mean(biou) * 100:.2f}"
 
 
 @ex.command

@@ -9,6 +9,8 @@ The round loop is the shared one: it aggregates the cross-entropy of the final o
 with mIoU and bIoU, and the command's result line says ``Loss_p1``.  The sum of the three passes' losses is returned per step by
 ``test_step``; aggregating it over a round would need a wider ``DeviceRoundTable``.
 
+``test_bank`` is ``test`` with every class's support enrolled once per round into a support bank (``BankEvaluator`` below).
+
 ``train_head`` trains the head behind a FROZEN trunk (``pemp_amd.train_rpmms``): a deliberate departure from the reference, whose
 ``maybe_fix_params()`` freezes nothing for RPMMs so that its ``train`` also updates the trunk's convs.  ``train`` (the
 reference's command name) still raises: trunk training is not built."""
@@ -20,6 +22,7 @@ from ..config import Experiment
 from ..networks.rpmms import WGEN_SEED, ModelClass, net_ingredient  # noqa: F401
 from ..train_rpmms import RPMMsTrainer
 from .pemp_stage1 import INGREDIENTS, SyntheticEpisodes, eval_episodes, get_val_labels, num_classes  # noqa: F401
+from .pemp_stage1 import BankEvaluator as _BankEvaluator
 from .pemp_stage1 import Evaluator as _Evaluator
 
 NAME = "PEMP"
@@ -89,6 +92,30 @@ def test(_config, split, shot, query, exp_id, ckpt, seed):
     loss, miou, biou = ev.start_eval_loop(data, num_classes(d["dataset"]), split, _config["te"]["epochs"], logger,
                                           batch=d["test_bs"], dataset_name=d["dataset"])
     return f"Loss_p1: {loss:.4f}, mIoU: {np.mean(miou) * 100:.2f}, bIoU: {np.mean(biou) * 100:.2f}"
+
+
+class BankEvaluator(_BankEvaluator):
+    """The enroll-once evaluator (entry.pemp_stage1.BankEvaluator) on RPMMs' support banks, with one difference: it calls
+    ``model.step_pmm_init()`` before each enrolment.  That is one draw of the EM's initial mu per class and round, where ``test``
+    draws one per step (a pinned init stays as it is on both)."""
+
+    def _enroll(self, slot, cls, sup_img, sup_mask):
+        self.model.step_pmm_init()
+        super()._enroll(slot, cls, sup_img, sup_mask)
+
+
+@ex.command
+def test_bank(_config, split, shot, query, exp_id, ckpt, seed):
+    """``python -m pemp_amd.entry.rpmms test_bank with split=0 ckpt=wgen``: ``test`` with the enroll-once protocol: every class's
+    support is enrolled once per round into a support bank (``RPMMs.enroll``), every query of the round is segmented against
+    its class (``RPMMs.segment_graphed``)."""
+    from .pemp_stage1 import run_test_bank
+    if split < 0:
+        raise ValueError("Argument `split` is required! For example: `python -m pemp_amd.entry.rpmms test_bank with split=0`")
+    if shot != 1 or query != 1:
+        raise ValueError("RPMMs is 1-shot with one query per episode (shot=1 query=1), as the reference is (rpmms.py:129, 266-267)")
+    return run_test_bank(_config, NAME, ModelClass, split, shot, exp_id, ckpt, seed, evaluator=BankEvaluator, loss_label="Loss_p1",
+                         wgen_seed=WGEN_SEED)
 
 
 def head_train_batches(trainer, dcfg, shot, split, rank, steps_per_epoch, device):

@@ -161,6 +161,55 @@ class RPMMs(_HeadMixin, backbones.BaseModel):
         out0, out1, out2 = self._engine_for(sup_img.device)["rpmms"].lowres(sup_img, sup_mask, qry_img)
         return out2, out0, out1
 
+    # -- support banks (pemp_amd.bank.RPMMsBank): enroll supports once, segment many queries --------------------------------
+    # ``segment`` / ``segment_lowres`` / ``segment_graphed`` are _HeadMixin's, with this family's bank and checks.
+    _bank_family = "rpmms"
+    _bank_backbone = "resnet50"
+
+    @staticmethod
+    def _bank_class():
+        from ..bank import RPMMsBank
+        return RPMMsBank
+
+    def _bank_desc(self):
+        return dict(family=self._bank_family, backbone=self._bank_backbone, precision=self.__dict__.get("_precision", "f32"), C=256)
+
+    def enroll(self, sup_img, sup_mask, labels=None, out=None):
+        """Supports of K classes, ``sup_img`` [K,1,3,H,W] and ``sup_mask`` [K,1,2,H,W] -> ``RPMMsBank``: one supports-only pass
+        through the trunk and ``layer5``, the mask resize, the EM and the tap products of the foreground prototypes.  The EM
+        starts from ``pmm_mu0`` as it stands: nothing is drawn here, call ``step_pmm_init()`` first when a fresh draw is wanted.
+        ``out``: enroll into that bank (same K) in place -- its storage keeps its addresses, so captured graphs that read it see
+        the new classes."""
+        from ..bank import RPMMsBank
+        if out is not None:
+            self._check_bank(out, "enroll(out=)")
+        self._require_eval_gpu(self)
+        if sup_img.dim() != 5 or sup_img.shape[1] != 1:
+            raise ValueError(f"{_ONE_SHOT}; got support {tuple(sup_img.shape)}")
+        K, S, ch, H, W = sup_img.shape
+        if tuple(sup_mask.shape) != (K, S, 2, H, W):
+            raise ValueError(f"enroll: sup_mask must be [{K},{S},2,{H},{W}], got {tuple(sup_mask.shape)}")
+        self._require_eval_gpu(self, sup_img, sup_mask)
+        if out is not None and (len(out) != K or not out.mu.is_cuda):
+            raise ValueError(f"enroll(out=): the bank holds {len(out)} classes on {out.mu.device}, {K} are enrolled")
+        eng = self._engine_for(sup_img.device)["rpmms"]
+        with torch.no_grad():
+            if out is None:
+                mu, taps = eng.support_side(sup_img, sup_mask)
+                desc = self._bank_desc()
+                return RPMMsBank(mu, taps, desc["backbone"], desc["precision"], labels=labels)
+            eng.support_side(sup_img, sup_mask, out.mu, out.taps)
+        if labels is not None:
+            out.labels = RPMMsBank._labels(labels, K)
+        return out
+
+    def _segment_dev(self, bank, qry_img, index_dev, ret_ind):
+        """-> (final logits, None): [N,2,h,w] with an index, [N,K,2,h,w] without.  The three passes of the call stay with the
+        engine (``last_bank_passes``: out0, out1, out2 over the pairs, pair n * K + k without an index)."""
+        out2 = self._engine_for(qry_img.device)["rpmms"].segment(bank, qry_img, index_dev)[2]
+        lead = (qry_img.shape[0],) if index_dev is not None else (qry_img.shape[0], len(bank))
+        return out2.view(lead + tuple(out2.shape[1:])), None
+
     def forward(self, sup_img, sup_mask, qry_img, out_shape=None):
         """The reference's eval forward (rpmms.py:213-254): (support_feature [B,256,h,w], out0, out1, out2), the logits at
         feature resolution [B,2,h,w] (``out_shape`` is not read there either; ``get_pred`` / ``get_loss`` resize)."""

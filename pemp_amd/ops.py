@@ -1702,3 +1702,78 @@ def rpmms_proto_sum(wz, mu, base, bias, out, dil=2, taps=None):
     _lib.check(lib.pemp_rpmms_proto_sum_f32(_p(wz), _p(mu), _p(base), ldb, _p(bias), _p(taps), _p(out), ldo, gstride, b, h, w, c,
                                             int(dil), _stream()), "rpmms_proto_sum")
     return out
+
+
+# -- RPMMs support banks (pemp_amd.bank.RPMMsBank): what a class's support leaves behind, and a query's meeting with it ----------
+def _rpmms_bank_store(who, mu, taps, c):
+    if mu.dim() != 4 or tuple(mu.shape[1:]) != (2, RPMMS_COLS, c) or mu.shape[0] < 1 or not mu.is_contiguous() \
+            or mu.dtype != torch.float32:
+        raise ValueError(f"{who}: mu must be contiguous fp32 [K,2,{RPMMS_COLS},{c}], got {tuple(mu.shape)} {mu.dtype}")
+    k = mu.shape[0]
+    if taps is not None and (tuple(taps.shape) != (k, RPMMS_COLS, 9, c) or not taps.is_contiguous() or taps.dtype != torch.float32):
+        raise ValueError(f"{who}: taps must be contiguous fp32 [{k},{RPMMS_COLS},9,{c}], got {tuple(taps.shape)} {taps.dtype}")
+    return k
+
+
+def rpmms_proto_taps(wz, mu, out=None):
+    """The tap products of ``rpmms_proto_sum`` on their own, for the K classes of a bank: wz [9,256,256], mu [K,2,10,256] ->
+    taps [K,10,9,256], bit for bit the ``taps`` scratch ``rpmms_proto_sum`` leaves for the same mu."""
+    if wz.dim() != 3 or wz.shape[0] != 9 or wz.shape[1] != wz.shape[2] or not wz.is_contiguous() or wz.dtype != torch.float32:
+        raise ValueError(f"rpmms_proto_taps: wz must be contiguous fp32 [9,C,C], got {tuple(wz.shape)} {wz.dtype}")
+    c = wz.shape[1]
+    k = _rpmms_bank_store("rpmms_proto_taps", mu, out, c)
+    lib = _lib.load()
+    _chk_dev(wz, mu, out)
+    if out is None:
+        out = torch.empty((k, RPMMS_COLS, 9, c), dtype=torch.float32, device=mu.device)
+    _lib.check(lib.pemp_rpmms_proto_taps_f32(_p(wz), _p(mu), _p(out), k, c, _stream()), "rpmms_proto_taps")
+    return out
+
+
+def rpmms_bank_l56(qry, base, bias, mu, taps, out, index=None, dil=2):
+    """``rpmms_proto_sum`` + ``rpmms_prob_map`` of N queries against the K classes of a bank in one launch: qry, base NHWC
+    [N,h,w,256] (layer5 of the queries and their conv with the query half of layer55), bias [256], mu [K,2,10,256], taps
+    [K,10,9,256] (``rpmms_proto_taps``).  ``index`` None: every query against every class, ``out`` [3,N*K,h,w,ld >= 258], pair
+    n * K + k; ``index`` (a Python sequence or a CPU integer tensor [N], checked here against 0 <= i < K, then uploaded as int32):
+    query n against class index[n], ``out`` [3,N,h,w,ld].  Channels 258.. are not written.  A pair is bit for bit the two
+    episode kernels on (qry[n], base[n], mu[k], taps[k])."""
+    _rpmms_bank_shapes(qry, base, bias, mu, taps)
+    if index is not None:
+        index = bank_index(index, qry.shape[0], mu.shape[0])
+    _lib.load()
+    _chk_dev(qry, base, bias, mu, taps, out)
+    if index is not None:
+        index = index.to(qry.device, non_blocking=True)
+    return _rpmms_bank_l56(qry, base, bias, mu, taps, out, index, dil)
+
+
+def _rpmms_bank_shapes(qry, base, bias, mu, taps):
+    ldq, ldb = _nhwc(qry, "qry"), _nhwc(base, "base")
+    c = qry.shape[3]
+    if tuple(base.shape) != tuple(qry.shape):
+        raise ValueError(f"rpmms_bank_l56: base {tuple(base.shape)} must have qry's shape {tuple(qry.shape)}")
+    if tuple(bias.shape) != (c,) or not bias.is_contiguous() or bias.dtype != torch.float32:
+        raise ValueError(f"rpmms_bank_l56: bias must be contiguous fp32 [{c}]")
+    if taps is None:
+        raise ValueError("rpmms_bank_l56: taps must be given (rpmms_proto_taps)")
+    _rpmms_bank_store("rpmms_bank_l56", mu, taps, c)
+    return ldq, ldb
+
+
+def _rpmms_bank_l56(qry, base, bias, mu, taps, out, index_dev, dil=2):
+    """The launch of ``rpmms_bank_l56``.  ``index_dev``: None or an int32 DEVICE tensor [N] whose values the caller has checked
+    on the host (``bank_index``) -- the static index buffer of a captured graph comes in here."""
+    ldq, ldb = _rpmms_bank_shapes(qry, base, bias, mu, taps)
+    n, h, w, c = qry.shape
+    k = mu.shape[0]
+    index = index_dev
+    if index is not None and (not isinstance(index, torch.Tensor) or not index.is_cuda or index.dtype != torch.int32
+                              or tuple(index.shape) != (n,) or not index.is_contiguous()):
+        raise ValueError(f"rpmms_bank_l56: the device index must be a contiguous int32 tensor [{n}] on the GPU")
+    pairs = n if index is not None else n * k
+    ldo, gstride = _rpmms_groups_out("rpmms_bank_l56", out, pairs, h, w, c, c + 2)
+    lib = _lib.load()
+    _chk_dev(qry, base, bias, mu, taps, index, out)
+    _lib.check(lib.pemp_rpmms_bank_l56_f32(_p(qry), ldq, _p(base), ldb, _p(bias), _p(mu), _p(taps), _p(index), _p(out), ldo, gstride,
+                                           n, k, h, w, c, int(dil), _stream()), "rpmms_bank_l56")
+    return out
