@@ -311,6 +311,22 @@ int pemp_eval_tail_f32(const float* pred, const int64_t* target, uint8_t* pred_o
                        float* logits_out, double* stats, void* ws, size_t ws_bytes,
                        int B, int h, int w, int Ho, int Wo, void* stream);
 
+/* The K-class counterpart of that tail: the K binary maps of an all-classes bank call (pred [N][K][2][h][w], what
+ * pemp_cosine_bank_max_f32 and the other bank kernels leave without an index) fused into one label map.  U = the
+ * upsample above.  Class k claims a pixel iff U[n][k][1] > U[n][k][0] (the tail's own comparison: a tie is
+ * background); the label is 0 where no class claims, else 1 + the claiming k with the largest margin
+ * U[n][k][1] - U[n][k][0] (one fp32 subtraction; the lowest k wins equal margins).  Labels are slot numbers, K <= 255.
+ *   labels uint8 [N][Ho][Wo];  margin fp32 [N][Ho][Wo] or NULL: the winner's margin, or where nobody claims the
+ *   largest margin of all classes (<= 0).
+ *   target int64 [N][Ho][Wo] (255 = ignore), want int32 [N] on the device, stats double [N][8]: all three or none.
+ *   stats = {ce_sum, n_valid, tp_bg, fp_bg, fn_bg, tp_fg, fp_fg, fn_fg} as above: ce_sum and n_valid of class want[n]'s
+ *   own two logits (pemp_eval_tail_f32's terms on pred[n][want[n]]), the counts of the image
+ *   [label == want[n] + 1] against target: the class's IoU under competition.  Deterministic (no atomics).      */
+size_t pemp_nway_tail_workspace_bytes(int N, int Ho, int Wo);
+int pemp_nway_tail_f32(const float* pred, const int64_t* target, const int32_t* want, uint8_t* labels,
+                       float* margin, double* stats, void* ws, size_t ws_bytes,
+                       int N, int K, int h, int w, int Ho, int Wo, void* stream);
+
 /* ResNetCM.comm statistics (networks/backbones.py:208-216): mask' = max_pool2d(mask,3,stride,1);
  * mean over ALL pixels and max over pixels of x*mask' per image and channel.
  *   x [N][Hx*Wx][ldx], mask_in [N][Hm][Wm], mask_out [N][Hx][Wx], stat [N][2][C] (mean, max).

@@ -75,6 +75,8 @@ SYMBOLS = {
     "pemp_upsample_nearest_u8_i64": (c_int, [c_fp, c_fp] + [c_int] * 5 + [c_fp]),
     "pemp_eval_tail_workspace_bytes": (c_size, [c_int] * 3),
     "pemp_eval_tail_f32": (c_int, [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_size] + [c_int] * 5 + [c_fp]),
+    "pemp_nway_tail_workspace_bytes": (c_size, [c_int] * 3),
+    "pemp_nway_tail_f32": (c_int, [c_fp] * 7 + [c_size] + [c_int] * 6 + [c_fp]),
     "pemp_cm_reduce_f32": (c_int, [c_fp, c_int, c_fp, c_fp, c_fp] + [c_int] * 7 + [c_fp]),
     "pemp_argmax_masks_f32": (c_int, [c_fp, c_fp, c_int, c_int, c_fp]),
     "pemp_cm_reduce_arg_f32": (c_int, [c_fp, c_int, c_fp, c_fp, c_fp, c_fp] + [c_int] * 7 + [c_fp]),

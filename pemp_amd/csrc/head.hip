@@ -83,3 +83,11 @@ extern "C" int pemp_eval_tail_f32(const float* pred, const int64_t* target, uint
                                   void* stream) {
     return j8::pemp_eval_tail_weighted_f32(pred, target, nullptr, pred_out, logits_out, stats, ws, ws_bytes, B, h, w, Ho, Wo, stream);
 }
+
+extern "C" size_t pemp_nway_tail_workspace_bytes(int N, int Ho, int Wo) { return j8::pemp_nway_tail_workspace_bytes(N, Ho, Wo); }
+
+extern "C" int pemp_nway_tail_f32(const float* pred, const int64_t* target, const int32_t* want, uint8_t* labels,
+                                  float* margin, double* stats, void* ws, size_t ws_bytes, int N, int K, int h, int w,
+                                  int Ho, int Wo, void* stream) {
+    return j8::pemp_nway_tail_f32(pred, target, want, labels, margin, stats, ws, ws_bytes, N, K, h, w, Ho, Wo, stream);
+}

@@ -839,7 +839,7 @@ __global__ void upsample_bilinear_kernel(const float* __restrict__ in, float* __
         long long t = i / Wo;
         int Y = (int)(t % Ho);
         int bc = (int)(t / Ho);
-        out[i] = bilerp(in + (size_t)bc * h * w, w, bilin(Y, h, Ho), bilin(X, w, Wo));
+        out[i] = bilerp(in + (size_t)bc * h * w, w, bilin_exact(Y, h, Ho), bilin_exact(X, w, Wo));
     }
 }
 
@@ -856,13 +856,28 @@ __global__ void upsample_nearest_kernel(const uint8_t* __restrict__ in, int64_t*
     }
 }
 
+// The eight statistics of a 256-thread tail block, summed in a fixed order (butterfly per wave, then (w0 + w1) + (w2 + w3))
+// -> out[8].  Every thread of the block must call.
+__device__ __forceinline__ void tail_block_sums(const double (&v)[8], double* __restrict__ out) {
+    __shared__ double red[4][8];
+    for (int k = 0; k < 8; ++k) {
+        double x = v[k];
+        for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
+        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][k] = x;
+    }
+    __syncthreads();
+    if (threadIdx.x < 8) {
+        int k = threadIdx.x;
+        out[k] = (red[0][k] + red[1][k]) + (red[2][k] + red[3][k]);
+    }
+}
+
 // eval tail: upsample + argmax + CE partials + tp/fp/fn partials.  part[b][blk][8] doubles.
 __global__ __launch_bounds__(256) void eval_tail_kernel(const float* __restrict__ pred,
                                                         const int64_t* __restrict__ target,
                                                         const float* __restrict__ weight,
                                                         uint8_t* __restrict__ pred_out, float* __restrict__ logits,
                                                         double* __restrict__ part, int h, int w, int Ho, int Wo) {
-    __shared__ double red[4][8];
     const int b = blockIdx.y;
     const int npix = Ho * Wo;
     const float* p0 = pred + (size_t)b * 2 * h * w;
@@ -871,7 +886,7 @@ __global__ __launch_bounds__(256) void eval_tail_kernel(const float* __restrict_
     int cnt[7] = {0, 0, 0, 0, 0, 0, 0};  // valid, tp0, fp0, fn0, tp1, fp1, fn1
     for (int i = blockIdx.x * 256 + threadIdx.x; i < npix; i += gridDim.x * 256) {
         int Y = i / Wo, X = i - Y * Wo;
-        Bilin by = bilin(Y, h, Ho), bx = bilin(X, w, Wo);
+        Bilin by = bilin_exact(Y, h, Ho), bx = bilin_exact(X, w, Wo);
         float l0 = bilerp(p0, w, by, bx), l1 = bilerp(p1, w, by, bx);
         int am = l1 > l0 ? 1 : 0;
         pred_out[(size_t)b * npix + i] = (uint8_t)am;
@@ -886,9 +901,7 @@ __global__ __launch_bounds__(256) void eval_tail_kernel(const float* __restrict_
             const float wgt = weight ? weight[(size_t)b * npix + i] : 1.f;
             wsum += (double)wgt;
             if (t != 255) {
-                float m = fmaxf(l0, l1);
-                float lse = m + logf(expf(l0 - m) + expf(l1 - m));
-                ce += (double)((lse - (t == 1 ? l1 : l0)) * wgt);
+                ce += (double)(ce_pixel(l0, l1, t) * wgt);
                 cnt[0]++;
                 for (int j = 0; j < 2; ++j) {
                     cnt[1 + 3 * j] += (am == j && t == j);
@@ -902,16 +915,7 @@ __global__ __launch_bounds__(256) void eval_tail_kernel(const float* __restrict_
     v[0] = ce;
     for (int k = 0; k < 7; ++k) v[k + 1] = (double)cnt[k];
     if (weight) v[1] = wsum;      // loss denominator: sum of weights instead of the valid-pixel count
-    for (int k = 0; k < 8; ++k) {
-        double x = v[k];
-        for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][k] = x;
-    }
-    __syncthreads();
-    if (threadIdx.x < 8) {
-        int k = threadIdx.x;
-        part[((size_t)b * gridDim.x + blockIdx.x) * 8 + k] = (red[0][k] + red[1][k]) + (red[2][k] + red[3][k]);
-    }
+    tail_block_sums(v, part + ((size_t)b * gridDim.x + blockIdx.x) * 8);
 }
 // one wave per (episode, statistic): lane-strided partial sums then a fixed butterfly -> deterministic
 __global__ void eval_tail_final_kernel(const double* __restrict__ part, double* __restrict__ stats, int nblk) {
@@ -925,6 +929,65 @@ __global__ void eval_tail_final_kernel(const double* __restrict__ part, double* 
 static inline int tail_blocks(int Ho, int Wo) {
     int nb = cdiv(Ho * Wo, 256 * 4);
     return nb < 1 ? 1 : (nb > 256 ? 256 : nb);
+}
+
+// N-way tail: the K binary maps of an all-classes bank call pred[n][k][2][h][w] fused into one label map.  Per output pixel the
+// interpolation indices and weights are formed once and serve all 2K planes (~10 KB each, L2-resident); k walks upward.
+// Class k claims the pixel iff U1 > U0 (eval_tail's comparison), the claiming class with the largest margin
+// __fsub_rn(U1, U0) owns it (strict >: the lowest k wins equal margins), label = 1 + k or 0 when nobody claims;
+// margin = the winner's, or the largest (<= 0) margin where nobody claims.  With a target: part[n][blk][8] doubles in
+// eval_tail's layout -- the CE of class want[n]'s own logits, tp/fp/fn of the image (label == want[n] + 1).
+__global__ __launch_bounds__(256) void nway_tail_kernel(const float* __restrict__ pred, const int64_t* __restrict__ target,
+                                                        const int32_t* __restrict__ want, uint8_t* __restrict__ labels,
+                                                        float* __restrict__ margin, double* __restrict__ part, int K, int h,
+                                                        int w, int Ho, int Wo) {
+    const int n = blockIdx.y;
+    const int npix = Ho * Wo, hw = h * w;
+    const float* pn = pred + (size_t)n * K * 2 * hw;
+    const int wk = target ? want[n] : -1;
+    double ce = 0.0;
+    int cnt[7] = {0, 0, 0, 0, 0, 0, 0};  // valid, tp0, fp0, fn0, tp1, fp1, fn1
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < npix; i += gridDim.x * 256) {
+        int Y = i / Wo, X = i - Y * Wo;
+        Bilin by = bilin_exact(Y, h, Ho), bx = bilin_exact(X, w, Wo);
+        int best = 0;                               // the label so far
+        float bm = 0.f, top = -INFINITY;            // its margin; the largest margin of all classes
+        float w0 = 0.f, w1 = 0.f;                   // the wanted class's own logits
+        const float* p = pn;
+        for (int k = 0; k < K; ++k, p += 2 * hw) {
+            float l0 = bilerp(p, w, by, bx), l1 = bilerp(p + hw, w, by, bx);
+            float m = __fsub_rn(l1, l0);
+            if (l1 > l0 && (best == 0 || m > bm)) {
+                best = k + 1;
+                bm = m;
+            }
+            if (m > top) top = m;
+            if (k == wk) {
+                w0 = l0;
+                w1 = l1;
+            }
+        }
+        labels[(size_t)n * npix + i] = (uint8_t)best;
+        if (margin) margin[(size_t)n * npix + i] = best ? bm : top;
+        if (target) {
+            int t = (int)target[(size_t)n * npix + i];
+            if (t != 255) {
+                int am = best == wk + 1 ? 1 : 0;
+                ce += (double)ce_pixel(w0, w1, t);
+                cnt[0]++;
+                for (int j = 0; j < 2; ++j) {
+                    cnt[1 + 3 * j] += (am == j && t == j);
+                    cnt[2 + 3 * j] += (am == j && t != j);
+                    cnt[3 + 3 * j] += (am != j && t == j);
+                }
+            }
+        }
+    }
+    if (!target) return;                            // uniform over the grid: no statistics asked for
+    double v[8];
+    v[0] = ce;
+    for (int k = 0; k < 7; ++k) v[k + 1] = (double)cnt[k];
+    tail_block_sums(v, part + ((size_t)n * gridDim.x + blockIdx.x) * 8);
 }
 
 }  // namespace PEMP_HEAD_NS
@@ -1140,6 +1203,27 @@ static int pemp_eval_tail_weighted_f32(const float* pred, const int64_t* target,
                        logits_out, (double*)ws, h, w, Ho, Wo);
     hipLaunchKernelGGL(eval_tail_final_kernel, dim3(B, 8), dim3(64), 0, (hipStream_t)stream, (const double*)ws, stats, nb);
     return launch_status("eval_tail");
+}
+
+static size_t pemp_nway_tail_workspace_bytes(int N, int Ho, int Wo) { return pemp_eval_tail_workspace_bytes(N, Ho, Wo); }
+
+static int pemp_nway_tail_f32(const float* pred, const int64_t* target, const int32_t* want, uint8_t* labels, float* margin,
+                              double* stats, void* ws, size_t ws_bytes, int N, int K, int h, int w, int Ho, int Wo,
+                              void* stream) {
+    PEMP_REQUIRE(pred && labels && ws, "nway_tail: null pointer");
+    PEMP_REQUIRE((target != nullptr) == (want != nullptr) && (target != nullptr) == (stats != nullptr),
+                 "nway_tail: target, want and stats come together");
+    PEMP_REQUIRE(N > 0 && N <= 65535 && K > 0 && h > 0 && w > 0 && Ho > 0 && Wo > 0 && (long long)Ho * Wo < (1LL << 31) &&
+                     (long long)h * w < (1LL << 29),
+                 "nway_tail: bad dims");
+    PEMP_REQUIRE(K <= 255, "nway_tail: K <= 255 (the labels are uint8, 0 = no class)");
+    PEMP_REQUIRE(ws_bytes >= pemp_nway_tail_workspace_bytes(N, Ho, Wo), "nway_tail: workspace too small");
+    const int nb = tail_blocks(Ho, Wo);
+    hipLaunchKernelGGL(nway_tail_kernel, dim3(nb, N), dim3(256), 0, (hipStream_t)stream, pred, target, want, labels, margin,
+                       (double*)ws, K, h, w, Ho, Wo);
+    if (stats)
+        hipLaunchKernelGGL(eval_tail_final_kernel, dim3(N, 8), dim3(64), 0, (hipStream_t)stream, (const double*)ws, stats, nb);
+    return launch_status("nway_tail");
 }
 
 }  // namespace PEMP_HEAD_NS

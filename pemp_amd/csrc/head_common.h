@@ -129,6 +129,20 @@ __device__ __forceinline__ Bilin bilin(int dst, int in, int out) {
     b.l = f - (float)b.i0;
     return b;
 }
+// The same with contraction off, for the kernels whose outputs are compared bit for bit (upsample, eval_tail, nway_tail): l
+// comes from the ROUNDED f.  `bilin` leaves that to the compiler, which took fma(scale, dst, -i0) in the unrolled loop of
+// upsample_bilinear_kernel and f - i0 in its remainder loop -- one launch, two weights for the same coordinate, and neither tail
+// agreed with the first.  (The resize and backward kernels keep `bilin` and with it the bits their fixtures were made with.)
+__device__ __forceinline__ Bilin bilin_exact(int dst, int in, int out) {
+#pragma clang fp contract(off)
+    float scale = out > 1 ? (float)(in - 1) / (float)(out - 1) : 0.f;
+    float f = scale * (float)dst;
+    Bilin b;
+    b.i0 = min((int)f, in - 1);
+    b.i1 = b.i0 + (b.i0 < in - 1 ? 1 : 0);
+    b.l = f - (float)b.i0;
+    return b;
+}
 __device__ __forceinline__ float bilerp(const float* __restrict__ p, int w, Bilin by, Bilin bx) {
     float v00 = p[by.i0 * w + bx.i0], v01 = p[by.i0 * w + bx.i1];
     float v10 = p[by.i1 * w + bx.i0], v11 = p[by.i1 * w + bx.i1];
@@ -137,6 +151,13 @@ __device__ __forceinline__ float bilerp(const float* __restrict__ p, int w, Bili
     float top = __fmaf_rn(bx.l, v01, __fmul_rn(w0, v00));
     float bot = __fmaf_rn(bx.l, v11, __fmul_rn(w0, v10));
     return __fmaf_rn(by.l, bot, __fmul_rn(h0, top));
+}
+
+// CrossEntropyLoss of one pixel's two logits against its label t (0 | 1): the term both tails (eval_tail, nway_tail) sum
+__device__ __forceinline__ float ce_pixel(float l0, float l1, int t) {
+    float m = fmaxf(l0, l1);
+    float lse = m + logf(expf(l0 - m) + expf(l1 - m));
+    return lse - (t == 1 ? l1 : l0);
 }
 
 }  // namespace pemp

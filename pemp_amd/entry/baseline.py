@@ -52,6 +52,13 @@ def test_bank(_config, split, shot, exp_id, ckpt):
 
 
 @ex.command
+def test_nway(_config, split, shot, exp_id, ckpt):
+    """``test_bank`` with every query meeting every enrolled class (entry.pemp_stage1.NWayEvaluator)."""
+    from .pemp_stage1 import NWayEvaluator, run_test_bank
+    return run_test_bank(_config, NAME, ModelClass, split, shot, exp_id, ckpt, evaluator=NWayEvaluator, command="test_nway")
+
+
+@ex.command
 def train(_config, split, shot, seed, loss, sigma, exp_id):
     """Baseline training procedure (entry/baseline.py:54-62,65-110): no gradient clipping; VGG-16 or ResNet-50 per net.backbone."""
     from .pemp_stage1 import run_training

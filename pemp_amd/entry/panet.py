@@ -109,6 +109,13 @@ def test_bank(_config, split, shot, exp_id, ckpt):
 
 
 @ex.command
+def test_nway(_config, split, shot, exp_id, ckpt):
+    """``test_bank`` with every query meeting every enrolled class (entry.pemp_stage1.NWayEvaluator); the query loss only."""
+    from .pemp_stage1 import NWayEvaluator, run_test_bank
+    return run_test_bank(_config, NAME, ModelClass, split, shot, exp_id, ckpt, evaluator=NWayEvaluator, command="test_nway")
+
+
+@ex.command
 def train(_config, split, shot, seed, loss, sigma, exp_id, loss_coef):
     """PANet training procedure (entry/panet.py:103-146): loss + loss_coef * align_loss, no gradient clipping."""
     from .pemp_stage1 import run_training

@@ -420,16 +420,74 @@ class BankEvaluator(Evaluator):
         return self.test_step_batch(episodes)
 
 
-def run_test_bank(_config, name, model_class, split, shot, exp_id, ckpt, seed=None, evaluator=None, loss_label="Loss", **load_kw):
-    """Body of the ``test_bank`` commands: ``test`` with the enroll-once protocol (``BankEvaluator``).  Same checkpoint
-    lookup, same episode source (``data.base_dir`` or synthetic), same result string; no configuration key of its own.
+class NWayMixin:
+    """Over ``BankEvaluator`` (or a subclass that overrides ``_enroll``: RPMMs'): the enroll-once protocol with every query
+    meeting EVERY class.  Per round the walk first enrolls the first task's supports of every validation class -- it stops
+    as soon as all are enrolled, and a class that never occurs is an error: a competition against an empty slot would mean
+    nothing -- then every query of the rank's shard is segmented against all classes (``segment_lowres`` without an index) and
+    ``ops.nway_tail`` decides each pixel, one launch per distinct label size, with the query's own slot as ``want``.  The rows
+    keep the fused tail's layout: the loss is the class's own binary CE (``test_bank``'s), the counts -- hence mIoU and bIoU --
+    are those of the class under K-way competition."""
+
+    def _episodes(self, dataset, indices):
+        """The round's episodes of this rank as ((qry_img, bank slot), qry_msk, cls), after the enrolment of every class."""
+        walk, enrolled = Evaluator._episodes, set()
+        for i, (inputs, _, cls) in enumerate(walk(self, dataset, range(len(dataset)))):
+            c = int(cls[0])
+            if c not in self._labels:
+                raise ValueError(f"episode {i} has class {c}, which is not a validation class of the split {self._labels}")
+            if c not in enrolled:
+                enrolled.add(c)
+                with ops.eval_splitk(ops.EVAL_SPLITK if self.splitk is None else self.splitk):
+                    self._enroll(self._labels.index(c), c, inputs[0], inputs[1])
+                if len(enrolled) == len(self._labels):
+                    break
+        missing = [c for c in self._labels if c not in enrolled]
+        if missing:
+            raise ValueError(f"the round's {len(dataset)} tasks hold no task of the validation classes {missing}: every class "
+                             f"of the split {self._labels} must be enrolled before the queries meet all of them")
+        for inputs, qry_msk, cls in walk(self, dataset, indices):
+            yield (inputs[2], self._labels.index(int(cls[0]))), qry_msk, cls
+
+    def test_step_batch(self, episodes):
+        """``episodes``: list of ((qry_img [1,1,3,H,W], bank slot), qry_msk).  -> stats f64 [len(episodes), 8] on the GPU."""
+        qry = torch.cat([ep[0][0].to(self.device, non_blocking=True).flatten(0, 1) for ep in episodes])
+        want = [ep[0][1] for ep in episodes]
+        labels = [ep[1].view(-1, *ep[1].shape[-2:]).to(self.device, non_blocking=True) for ep in episodes]
+        seg = self.model.segment_graphed if self.use_graph else self.model.segment_lowres
+        with torch.no_grad(), ops.eval_splitk(ops.EVAL_SPLITK if self.splitk is None else self.splitk):
+            return self._nway_by_size(seg(self.bank, qry)[0], want, labels)
+
+    def _nway_by_size(self, pred, want, labels):
+        """``_tail_by_size`` on the all-classes prediction [N,K,2,h,w]: one N-way tail launch per distinct label size."""
+        stats = torch.empty((len(labels), 8), dtype=torch.float64, device=self.device)
+        by_size = {}
+        for i, lab in enumerate(labels):
+            by_size.setdefault(tuple(lab.shape[-2:]), []).append(i)
+        for idx in by_size.values():
+            sel = torch.tensor(idx, device=self.device)
+            _, _, st = ops.nway_tail(pred.index_select(0, sel), target=torch.cat([labels[i] for i in idx]),
+                                     want=[want[i] for i in idx], ws_cache=self._ws)
+            stats.index_copy_(0, sel, st)
+        return stats
+
+
+class NWayEvaluator(NWayMixin, BankEvaluator):
+    """``BankEvaluator`` with every query against every enrolled class (``NWayMixin``)."""
+
+
+def run_test_bank(_config, name, model_class, split, shot, exp_id, ckpt, seed=None, evaluator=None, loss_label="Loss",
+                  command="test_bank", **load_kw):
+    """Body of the ``test_bank`` and ``test_nway`` commands: ``test`` with the enroll-once protocol (``BankEvaluator``).  Same
+    checkpoint lookup, same episode source (``data.base_dir`` or synthetic), same result string; no configuration key of its own.
     ``model_class(logger)`` makes the model, ``load_kw`` goes to ``load_for_eval`` (PFENet's Wgen seed).  ``evaluator``: the
-    evaluator class (default ``BankEvaluator``), ``loss_label``: the name of the loss in the result line (RPMMs: ``Loss_p1``)."""
+    evaluator class (default ``BankEvaluator``), ``loss_label``: the name of the loss in the result line (RPMMs: ``Loss_p1``),
+    ``command``: the command's name in the message that asks for a split."""
     import logging
     logging.basicConfig(level=logging.INFO, format="%(message)s")
     logger = logging.getLogger(name)
     if split < 0:
-        raise ValueError("Argument `split` is required! For example: `python -m pemp_amd.entry.pemp_stage1 test_bank with split=0`")
+        raise ValueError(f"Argument `split` is required! For example: `python -m pemp_amd.entry.pemp_stage1 {command} with split=0`")
     if seed is not None:
         torch.manual_seed(seed)
     from ..core.snapshots import load_for_eval
@@ -449,6 +507,13 @@ def test_bank(_config, split, shot, seed, exp_id, ckpt):
     """``python -m pemp_amd.entry.pemp_stage1 test_bank with split=0 exp_id=1``: the evaluation rounds of ``test`` with the
     supports of every class enrolled once per round (its first task's) and all of the class's queries segmented against them."""
     return run_test_bank(_config, NAME, ModelClass, split, shot, exp_id, ckpt, seed)
+
+
+@ex.command
+def test_nway(_config, split, shot, seed, exp_id, ckpt):
+    """``python -m pemp_amd.entry.pemp_stage1 test_nway with split=0 exp_id=1``: ``test_bank`` with every query meeting every
+    enrolled class (``NWayEvaluator``): the loss is ``test_bank``'s, mIoU and bIoU are those of the classes under competition."""
+    return run_test_bank(_config, NAME, ModelClass, split, shot, exp_id, ckpt, seed, evaluator=NWayEvaluator, command="test_nway")
 
 
 @ex.command

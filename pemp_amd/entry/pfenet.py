@@ -72,6 +72,17 @@ def test_bank(_config, split, shot, query, exp_id, ckpt):
     return run_test_bank(_config, NAME, lambda logger: ModelClass(shot, logger), split, shot, exp_id, ckpt, wgen_seed=WGEN_SEED)
 
 
+@ex.command
+def test_nway(_config, split, shot, query, exp_id, ckpt):
+    """``python -m pemp_amd.entry.pfenet test_nway with split=0 ckpt=wgen [shot=5]``: ``test_bank`` with every query meeting
+    every enrolled class (entry.pemp_stage1.NWayEvaluator)."""
+    from .pemp_stage1 import NWayEvaluator, run_test_bank
+    if query != 1:
+        raise ValueError("PFENet takes exactly one query per episode (query=1)")
+    return run_test_bank(_config, NAME, lambda logger: ModelClass(shot, logger), split, shot, exp_id, ckpt, evaluator=NWayEvaluator,
+                         command="test_nway", wgen_seed=WGEN_SEED)
+
+
 def head_train_batches(trainer, dcfg, shot, split, rank, steps_per_epoch, device):
     """-> ``batches(epoch)`` for ``TrainingLoop``: synthetic episodes with the query label at the input size (the reference resizes
     a training label with its image)."""

@@ -329,6 +329,22 @@ class _HeadMixin:
         run = lambda s: self._segment_dev(bank, s[0], s[1] if idx is not None else None, ret_ind)
         return self._replay(eng, key, inputs, run, run)
 
+    def segment_labels(self, bank, qry_img, out_shape=None, want_margin=False, graphed=False):
+        """Every query against every enrolled class, decided per pixel: ``segment_lowres`` without an index (``graphed``:
+        ``segment_graphed``) and one fused launch (``ops.nway_tail``) that upsamples the K binary maps and keeps, per pixel, 0
+        where every class says background and else 1 + the slot of the class that claims it by the largest margin
+        (foreground logit - background logit; the lowest slot wins equal margins).  -> labels uint8 [N,Ho,Wo] of slot
+        numbers (``bank.labels`` maps them), with ``want_margin`` (labels, margin fp32 [N,Ho,Wo]).  ``out_shape`` defaults to
+        the query size.  No full-resolution logits are stored."""
+        self._segment_args(bank, qry_img, None, False, "segment_labels")
+        if len(bank) > 255:
+            raise ValueError(f"segment_labels: the bank holds {len(bank)} classes; the labels are uint8 with 0 for no class, "
+                             "so at most 255")
+        pred, _ = (self.segment_graphed if graphed else self.segment_lowres)(bank, qry_img)
+        out_shape = tuple(out_shape) if out_shape is not None else tuple(qry_img.shape[-2:])
+        labels, margin, _ = ops.nway_tail(pred, out_shape, want_margin=want_margin, ws_cache=self._engine_for(qry_img.device)["arena"].ws)
+        return (labels, margin) if want_margin else labels
+
 
 class PEMPStage1(_HeadMixin, backbones.BaseModel):
     """Stage 1 of the Prior-Enhanced network with Meta-Prototypes (reference class of the same name)."""

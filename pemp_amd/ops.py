@@ -1216,6 +1216,50 @@ def eval_tail(pred, target, want_logits=False, ws_cache=None, out_hw=None, weigh
     return am, stats, logits
 
 
+def nway_tail(pred, out_hw=None, target=None, want=None, want_margin=False, ws_cache=None):
+    """The K binary maps of an all-classes bank call fused into one label map: pred fp32 [N,K,2,h,w] (``segment_lowres``
+    without an index) -> (labels uint8 [N,Ho,Wo], margin fp32 [N,Ho,Wo] | None, stats f64 [N,8] | None).  Class k claims a
+    pixel of the upsampled logits iff its foreground logit exceeds its background logit; the label is 0 where no class
+    claims, else 1 + the claiming k with the largest margin (foreground - background; the lowest k wins equal margins):
+    slot numbers, ``bank.labels`` maps them.  ``margin`` (``want_margin``): the winner's, or the largest (<= 0) where nobody
+    claims.  ``target`` int64 [N,Ho,Wo] (gives the output size; ``out_hw`` otherwise) comes with ``want``, the slot scored per
+    query -- a Python sequence or a CPU tensor, checked here (``bank_index``) and uploaded, or a device int32 [N] -- and gives
+    ``stats`` in ``eval_tail``'s layout: the CE of the wanted class's own logits, tp/fp/fn of ``labels == want + 1``."""
+    lib = _lib.load()
+    if pred.dim() != 5 or pred.dtype != torch.float32 or not pred.is_contiguous() or pred.shape[2] != 2 or min(pred.shape) < 1:
+        raise ValueError(f"nway_tail: pred must be contiguous fp32 [N,K,2,h,w], got {tuple(pred.shape)} {pred.dtype}")
+    n, k, _, h, w = pred.shape
+    if k > 255:
+        raise ValueError(f"nway_tail: K = {k}: the labels are uint8 with 0 for no class, so K <= 255")
+    if (target is None) != (want is None):
+        raise ValueError("nway_tail: target and want come together")
+    if target is None:
+        if out_hw is None:
+            raise ValueError("nway_tail: out_hw is needed without a target")
+        ho, wo = int(out_hw[0]), int(out_hw[1])
+        if ho < 1 or wo < 1:
+            raise ValueError(f"nway_tail: out_hw = {(ho, wo)}")
+    else:
+        if target.dtype != torch.int64 or not target.is_contiguous() or target.dim() != 3 or target.shape[0] != n:
+            raise ValueError(f"nway_tail: target must be contiguous int64 [{n},Ho,Wo]")
+        ho, wo = (int(v) for v in target.shape[-2:])
+        if out_hw is not None and (int(out_hw[0]), int(out_hw[1])) != (ho, wo):
+            raise ValueError(f"nway_tail: out_hw = {tuple(out_hw)} against a target of {(ho, wo)}")
+        if isinstance(want, torch.Tensor) and want.device.type != "cpu":
+            if want.dtype != torch.int32 or tuple(want.shape) != (n,) or not want.is_contiguous():
+                raise ValueError(f"nway_tail: a device want must be contiguous int32 [{n}]")
+        else:
+            want = bank_index(want, n, k).to(pred.device, non_blocking=True)
+    _chk_dev(pred, target, want)
+    labels = torch.empty((n, ho, wo), dtype=torch.uint8, device=pred.device)
+    margin = torch.empty((n, ho, wo), dtype=torch.float32, device=pred.device) if want_margin else None
+    stats = torch.empty((n, 8), dtype=torch.float64, device=pred.device) if target is not None else None
+    ws = _ws(lib.pemp_nway_tail_workspace_bytes(n, ho, wo), pred.device, ws_cache, ("nway", n, ho, wo))
+    _lib.check(lib.pemp_nway_tail_f32(_p(pred), _p(target), _p(want), _p(labels), _p(margin), _p(stats), _p(ws), ws.numel(),
+                                      n, k, h, w, ho, wo, _stream()), "nway_tail")
+    return labels, margin, stats
+
+
 def cm_reduce(x, mask_in, stride, want_argmax=False):
     """ResNetCM.comm statistics: x NHWC [N,h,w,C] (or None: pool the mask only); mask_in [N,Hm,Wm]
     -> (mask_out [N,h,w], stat [N,2,C] | None) (+ argmax int32 [N,C] with ``want_argmax``: the first maximal pixel,
