@@ -85,6 +85,12 @@ int pemp_abi_version(void);
  *                       pad == dil == d, 256 + 2 d + d ceil((255 + 2 d) / W) <= 288; the plain fp32 output (affine, ReLU) only: no
  *                       PEMP_CONV_OUT_SPLIT3 / _ALSO, residual, padding value, per-image shift, split-K or workspace -- anything
  *                       else is an error ("unsupported").  Bit-identical to 146 / 149
+ *    34x  349             the form and results of 49 on a THREE-deep activation ring (conv_ring.hip: conv_ring_kernel): persistent 256 x
+ *                       128 tiles whose fp32 activations get two K steps to land instead of half a step.  1x1 convs without padding
+ *                       (any stride), ldx >= Cin, Kpad == Cin >= 128, Cout % 128 == 0; the fp32 output (affine, per-image shift, ReLU,
+ *                       ldy >= Cout) or PEMP_CONV_OUT_SPLIT3; no residual, PEMP_CONV_OUT_SPLIT3_ALSO, PEMP_CONV_IN_SPLIT3,
+ *                       PEMP_CONV_RES_S2, padding value, stem, split-K or workspace, pemp_conv2d_nhwc_f32 only -- anything else is an
+ *                       error ("unsupported").  Bit-identical to 43 / 49
  *     7x  71, 72          split3, activation-stationary (1x1 convs without padding, Kpad <= 256, pemp_conv2d_nhwc_f32 only): a
  *                       block of 4 waves keeps 128 output rows x K of split activations in registers and walks ALL of Cout, 128
  *                       (71) or 64 (72) columns at a time, with only the packed weights streaming through LDS; no padding value,

@@ -11,7 +11,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "_obj")
 OUT = os.path.join(HERE, "libpemp_hip.so")
-SOURCES = ("conv_igemm.hip", "conv_dma.hip", "conv_dma2.hip", "conv_panel.hip", "conv_row3.hip", "conv_stem_pool.hip", "conv_wgrad.hip", "train_ops.hip", "pool_misc.hip", "head.hip", "head_bwd.hip", "cedt.hip",
+SOURCES = ("conv_igemm.hip", "conv_dma.hip", "conv_dma2.hip", "conv_panel.hip", "conv_row3.hip", "conv_ring.hip", "conv_stem_pool.hip", "conv_wgrad.hip", "train_ops.hip", "pool_misc.hip", "head.hip", "head_bwd.hip", "cedt.hip",
            "episode_io.hip", "dropout.hip", "cm_linear.hip", "pfenet.hip", "pfenet_bwd.hip", "canet.hip", "canet_bwd.hip", "rpmms.hip", "rpmms_bwd.hip")
 FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC"]
 
@@ -33,7 +33,7 @@ def csrc_digest():
     return h.hexdigest()[:12]
 
 
-CONV_ENGINE = ("common.h", "conv_common.h", "conv_tiles.h", "conv_igemm.hip", "conv_dma.hip", "conv_dma2.hip", "conv_panel.hip", "conv_row3.hip", "conv_stem_pool.hip")
+CONV_ENGINE = ("common.h", "conv_common.h", "conv_tiles.h", "conv_igemm.hip", "conv_dma.hip", "conv_dma2.hip", "conv_panel.hip", "conv_row3.hip", "conv_ring.hip", "conv_stem_pool.hip")
 
 
 def conv_digest():

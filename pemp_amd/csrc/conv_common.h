@@ -496,6 +496,9 @@ int launch_conv_panel(int shape, const ConvArgs& a, hipStream_t st);
 // 249: one tile per block / persistent)
 bool conv_row3_supported(const ConvArgs& a);
 int launch_conv_row3(bool persistent, const ConvArgs& a, hipStream_t st);
+// conv_ring.hip: the persistent 256 x 128 form of 1x1 / pad 0 convs on fp32 activations with a three-deep activation ring (tile id 349)
+bool conv_ring_supported(const ConvArgs& a);
+int launch_conv_ring(const ConvArgs& a, hipStream_t st);
 int conv_dma2_simds();                                                     // SIMDs of the current device (4 per CU)
 int pack_split3(const float* w, void* out, int cout, int kpad, hipStream_t st);
 // conv_stem_pool.hip: the 7x7 / 2 / 3 NHWC4 stem (split3 weights) + its 3 / 2 / 1 ceil-mode max-pool in one launch (PEMP_CONV_POOL3S2)

@@ -342,6 +342,13 @@ static int conv2d_impl(const pemp_conv_desc* d, const float* x, const float* w, 
         tile = 3;
     }
     TileId t = decode_tile(tile);
+    if (t.ring) {                        // conv_ring.hip: same results as 43 / 49 where it applies, an error elsewhere
+        PEMP_REQUIRE(!ws && !pad_value && conv_ring_supported(a),
+                     "conv2d: tile %d unsupported: needs a 1x1 conv without padding on fp32 activations with Kpad == Cin >= 128 and Cout %% 128 == 0, the "
+                     "fp32 output or PEMP_CONV_OUT_SPLIT3 (ldy == Cout); no residual, PEMP_CONV_OUT_SPLIT3_ALSO, PEMP_CONV_IN_SPLIT3, PEMP_CONV_RES_S2, "
+                     "padding value, stem, split-K or workspace; operands < 2 GiB", tile);
+        return launch_conv_ring(a, (hipStream_t)stream);
+    }
     // y: bf16 [M][Cout / 32][3][32].  The persistent ids 47 / 49 / 149 run their producer variants (compile-time: no residual path,
     // which is what leaves registers for the split); a persistent shape without one would run as the id it walks -- same tiles,
     // same results (conv_dma2_persist_out_split3)

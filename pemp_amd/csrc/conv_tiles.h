@@ -74,11 +74,16 @@ struct TileId {
     bool panel;        // 71, 72: the activation-stationary 1x1 form (conv_panel.hip)
     bool presplit;     // 146, 149, 246, 249: the activations come pre-split (PEMP_CONV_IN_SPLIT3); the forms of 46 / 49
     bool row3;         // 246, 249: the tile of 146 / 149 with one A stage for the three taps of a kernel row (conv_row3.hip)
+    bool ring;         // 349: the form of 49 on a three-deep activation ring, 1x1 convs without padding only (conv_ring.hip)
 };
 
 inline TileId decode_tile(int id) {
-    TileId t = {TILE_NONE, 0, false, false, false, false, false, false};
+    TileId t = {TILE_NONE, 0, false, false, false, false, false, false, false};
     const int decade = id / 10, s = id % 10;
+    if (id == 349) {
+        t.family = TILE_SPLIT3, t.shape = 6, t.exists = t.persistent = t.ring = true;
+        return t;
+    }
     if (id == 146 || id == 149 || id == 246 || id == 249) {
         t.family = TILE_SPLIT3, t.shape = 6, t.exists = t.presplit = true, t.persistent = id % 10 == 9, t.row3 = id > 200;
         return t;

@@ -93,6 +93,9 @@ TILES.update({146: Tile(_SHAPES[6], "split3", False, None), 149: Tile(_SHAPES[6]
 #: ... and the tiles of 146 / 149 with ONE activation stage for the three taps of a kernel row (csrc/conv_row3.hip): 3x3 / stride 1 /
 #: pad == dil convs whose stage fits 288 rows (``_row3_ok``); 249: the persistent form of 246
 TILES.update({246: Tile(_SHAPES[6], "split3", False, None), 249: Tile(_SHAPES[6], "split3", False, 246)})
+#: ... and the form of 49 on a three-deep activation ring (csrc/conv_ring.hip): 1x1 convs without padding on fp32 activations with
+#: K >= 128 (``_ring_ok``), whose activations are a pure HBM stream and get two K steps to land instead of half a step
+TILES.update({349: Tile(_SHAPES[6], "split3", False, 46)})
 _NO_TILE = Tile(None, None, False, None)        # an id outside the registry: the library refuses it
 
 
@@ -126,6 +129,11 @@ SPLIT3_PRESPLIT = os.environ.get("PEMP_SPLIT3_PRESPLIT", "1") != "0"
 SPLIT3_ROW3_TILES = (246, 249)
 SPLIT3_ROW3 = os.environ.get("PEMP_SPLIT3_ROW3", "1") != "0"
 ROW3_STAGE_ROWS = 288
+#: ... and the three-deep activation ring of 49 for long-K 1x1 convs (bit-identical to the ids above): a registry of its own, offered
+#: to timing-based picks only, where ``_ring_ok`` holds (PEMP_SPLIT3_RING=0: never, the A/B switch)
+SPLIT3_RING_TILES = (349,)
+SPLIT3_RING = os.environ.get("PEMP_SPLIT3_RING", "1") != "0"
+RING_MIN_K = 128
 AUTOTUNE = True
 #: test hook: ``PICK_HOOK(kind, cands, key) -> one of cands`` decides every kernel-variant pick INSTEAD of timing (kind "conv":
 #: tile ids, "wgrad": block counts / (tile kind, block count) pairs), at any problem size.  Timing-based picks differ from box
@@ -309,6 +317,15 @@ def _row3_ok(p, w, residual, pad_value, out_split3, also_split3, per_image_shift
             and row3_stage_rows(w, p.dil) <= ROW3_STAGE_ROWS)
 
 
+def _ring_ok(p, x_split3, residual, pad_value, also_split3, splitk, res_s2=False):
+    """Whether the id of SPLIT3_RING_TILES takes this call of a split3 layer (conv_ring.hip: conv_ring_supported): a 1x1 conv without
+    padding on fp32 activations, K = Cin >= 128, Cout in whole 128-column tiles; the fp32 or the pre-split output; no residual, second
+    output, padding value, split-K.  (The operand sizes are conv2d's ``s3`` rule, which every split3 call passes first.)"""
+    return (SPLIT3_RING and PICK_HOOK is None and p.w3 is not None and not p.stem and (p.kh, p.kw, p.pad) == (1, 1, 0)
+            and p.cin % 32 == 0 and p.kpad == p.cin and p.kpad >= RING_MIN_K and p.cout % 128 == 0 and not x_split3 and residual is None
+            and pad_value is None and also_split3 is None and not splitk and not res_s2 and p.cout * p.kpad * 6 < 1 << 31)
+
+
 def pack_split3(w):
     """KRSC [Cout, Kpad] fp32 (Kpad % 32 == 0) -> its split3 form (pemp_pack_split3_bf16): bf16 [Cout, Kpad / 32, 3, 32], per row
     and 32-channel K step the planes h, m, l with w == h + m + l exactly."""
@@ -423,7 +440,7 @@ def conv2d(x, p, out=None, residual=None, shift_override=None, per_image_shift=F
             raise ValueError(f"conv2d: {what} needs a split3 layer (ConvParams.w3), not the fp32 chain or a stem")
         if splitk or dropblock is not None:
             raise ValueError(f"conv2d: {what} has no split-K / DropBlock form")
-        if out_split3 and tile and (tile not in SPLIT3_TILES + SPLIT3_PRESPLIT_TILES):
+        if out_split3 and tile and (tile not in SPLIT3_TILES + SPLIT3_PRESPLIT_TILES + SPLIT3_RING_TILES):
             raise ValueError(f"conv2d: a pre-split output needs an unsplit split3 tile id, got {tile}")
         if x_split3 and (p.kh * p.kw == 1 or per_image_shift or p.cin % 32 or p.cout % 128):
             raise ValueError("conv2d: a pre-split input needs a multi-tap conv with Cin % 32 == 0 and Cout % 128 == 0, no per-image shift")
@@ -533,8 +550,13 @@ def conv2d(x, p, out=None, residual=None, shift_override=None, per_image_shift=F
             row3 = bool(x_split3) and _row3_ok(p, w, residual, pad_value, out_split3, also_split3, per_image_shift)
             if row3:
                 key += (246,)
+            # ... and a producer call that the ring id takes, likewise (349; ``_ring_ok`` is false under the hook)
+            ring = _ring_ok(p, x_split3, residual, pad_value, also_split3, splitk)
+            if ring:
+                key += (349,)
             cands = lambda: _fits(list(SPLIT3_PRESPLIT_TILES if x_split3 else SPLIT3_TILES) +
-                                  (list(SPLIT3_ROW3_TILES) if row3 and PICK_HOOK is None else []), p.cout)
+                                  (list(SPLIT3_ROW3_TILES) if row3 and PICK_HOOK is None else []) +
+                                  (list(SPLIT3_RING_TILES) if ring else []), p.cout)
         elif res_s2:
             # a key of its own (128): a pick made with a dense residual is never replayed on the strided one, nor the reverse.  Only
             # the ids that take the flag are offered; the panel ones under their usual rule (and the residual's own extent < 2 GiB)
@@ -546,10 +568,15 @@ def conv2d(x, p, out=None, residual=None, shift_override=None, per_image_shift=F
             # a pick among candidates that include the panel ids is remembered under a key of its own (71): a call of the same
             # geometry that they do not take (a per-image shift, operands of 2 GiB) must never replay it
             panel = _panel_ok(p, n, ho, wo, ldx, ldy, ldr, h, w, pad_value, splitk, per_image_shift)
+            # ... and the ring id under a suffix of its own (349), in front of the panel one: an older pick is never replayed on the new
+            # candidate set, and a pick that includes the id never on a call that the id refuses (a residual, a padding value)
+            ring = _ring_ok(p, x_split3, residual, pad_value, also_split3, splitk)
+            if ring:
+                key += (349,)
             if panel:
                 key += (71,)
             cands = lambda: _fits(list(SPLIT3_TILES) + (list(SPLIT3_SPLITK_TILES) if splitk else []) +
-                                  (list(SPLIT3_PANEL_TILES) if panel else []), p.cout)
+                                  (list(SPLIT3_RING_TILES) if ring else []) + (list(SPLIT3_PANEL_TILES) if panel else []), p.cout)
         else:
             def cands():
                 ids = list(GROUP_TILES if dropblock is not None else TILE_VARIANTS) + (list(SPLITK_TILES) if splitk else [])

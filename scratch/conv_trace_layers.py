@@ -8,7 +8,7 @@ import sys
 trace, per_step = sys.argv[1], int(sys.argv[2])
 steps = int(sys.argv[3]) if len(sys.argv) > 3 else 20
 rows = sorted(csv.DictReader(open(trace)), key=lambda r: int(r["Start_Timestamp"]))
-conv = [r for r in rows if any(k in r["Kernel_Name"] for k in ("conv_dma", "conv_igemm", "conv_stem_pool", "conv_panel", "conv_row3"))][-steps * per_step:]
+conv = [r for r in rows if any(k in r["Kernel_Name"] for k in ("conv_dma", "conv_igemm", "conv_stem_pool", "conv_panel", "conv_row3", "conv_ring"))][-steps * per_step:]
 dur = lambda r: (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3
 pos = collections.defaultdict(list)
 for i, r in enumerate(conv):

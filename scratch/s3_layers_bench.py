@@ -3,7 +3,7 @@ TFLOP/s, bit-identity of every unsplit id with id 43, and a hash of every output
 compared.  The multi-tap layers also run the ids that read PRE-SPLIT activations (146 / 149, and 246 / 249 where they apply, the input
 split on the device by the reference arithmetic) -- without a residual also with the second, pre-split output ("149+s" = id 149 with also_split3: the fp32 tensor
 must be id 43's and the second one its split) -- and the 1x1 layers without a residual also run as producers of a pre-split output
-("43s" = id 43 with out_split3, "49s" = the persistent id's producer kernel; the result must be the split of id 43's).  Every cell carries the fastest and the slowest of its --reps timings.  GPU.
+("43s" = id 43 with out_split3, "49s" / "349s" = the persistent ids' producer kernels; the result must be the split of id 43's).  Every cell carries the fastest and the slowest of its --reps timings.  GPU.
 
     python3 scratch/s3_layers_bench.py [--only 256-256-k3[,...]] [--ids 49,149] [--reps N] [--res 0|1]
 
@@ -22,6 +22,7 @@ UNSPLIT = (43, 42, 41, 44, 46, 47, 49)     # 47 / 49: persistent forms of 43 / 4
 SPLIT = (52, 51, 54, 56)
 PANEL = ops.SPLIT3_PANEL_TILES             # 71 / 72: activation-stationary forms (1x1, Kpad <= 256; conv_panel.hip)
 PRESPLIT = ops.SPLIT3_PRESPLIT_TILES       # 146 / 149: the forms of 46 / 49 on pre-split activations
+RING = getattr(ops, "SPLIT3_RING_TILES", ())     # 349: the form of 49 on a three-deep activation ring (1x1, pad 0, K >= 128, no residual; conv_ring.hip); () on a tree without it
 ROW3 = ops.SPLIT3_ROW3_TILES               # 246 / 249: 146 / 149 with one activation stage per (chunk, kh) (3x3, pad == dil, no residual / padding value; conv_row3.hip)
 # (cin, cout, k, dil, residual, padding value[, stride, maps of HW x HW]): the six geometries that carry ~81 % of the step's conv time, and the 3 x 3 layer
 # once more with a padding value (the PADV instantiation)
@@ -33,6 +34,8 @@ LAYERS = ((256, 1024, 1, 1, True, False), (512, 1024, 1, 1, False, False), (1024
           # the other 3x3 widths (layer2: stride 1 at 51 x 51 and stride 2 from 101 x 101; layer1 at 101 x 101) and layer2's conv1
           (128, 128, 3, 1, False, False), (128, 128, 3, 1, False, False, 2, 101), (64, 64, 3, 1, False, False, 1, 101),
           (512, 128, 1, 1, False, False),
+          # layer3 block 0 conv1 and a 256 -> 256 1x1 (the 1x1 ASPP branch)
+          (512, 256, 1, 1, False, False), (256, 256, 1, 1, False, False),
           # layer1's last conv3 with row pruning: M = 130 050 compact rows, the residual on the 101 x 101 grid (residual_stride=2; a 9th
           # field: the residual's grid).  Against the dense-residual row 64-256-k1-hw101-res1 at M = 510 050
           (64, 256, 1, 1, True, False, 1, 51, 101),
@@ -101,6 +104,7 @@ def main():
     ap.add_argument("--only", default="", help="cin-cout-kK[-padv]: one layer")
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--ids", default="", help="comma-separated tile ids: only these are timed (a counter run of one kernel)")
+    ap.add_argument("--producers", action="store_true", help="with --ids: time the selected ids as producers of a pre-split output too")
     ap.add_argument("--res", type=int, choices=(0, 1), default=None, help="run the selected layers without / with a residual, whatever their row says")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
@@ -136,7 +140,8 @@ def main():
         ref = ops.conv2d(x, prm, residual=res, pad_value=pad_value, tile=43).clone()
         cells, hashes = [], [f"43={digest(ref)}"]
         panel = PANEL if k == 1 and kpad <= 256 and not padv else ()
-        for tile in keep(UNSPLIT + panel + SPLIT):
+        ring = RING if k == 1 and kpad >= 128 and not has_res and not padv and cout % 128 == 0 else ()
+        for tile in keep(UNSPLIT + ring + panel + SPLIT):
             if cout % ops._tile_bn(tile):
                 continue
             run = lambda: ops.conv2d(x, prm, residual=res, pad_value=pad_value, out=out, tile=tile)
@@ -176,7 +181,7 @@ def main():
         if k == 1 and not has_res:               # the same layer as the producer of a pre-split output
             want = presplit(ref)
             outs = torch.empty_like(want)
-            for tile in keep((43, 42, 41, 44, 46, 47, 49) if not args.ids else ()):
+            for tile in keep((43, 42, 41, 44, 46, 47, 49) + ring if not args.ids or args.producers else ()):
                 if cout % ops._tile_bn(tile):
                     continue
                 run = lambda: ops.conv2d(x, prm, out=outs, tile=tile, out_split3=True)
