@@ -98,3 +98,111 @@ def test_train_step_with_cedt_runs(hip_lib, dev):
     l_t, _ = util.torch_head_step(tr, sup, msk, qry, gt)
     assert abs(l_hip.item() - l_t.item()) < 2e-5
     assert (g_hip - tr.eng.flat.grad).abs().max().item() < 2e-2 * g_hip.abs().max().item()
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# The launch branches of pemp_cedt_weight_f32 against tests/cedt_ref.py: every weight within ONE ulp of the reference table
+# at the exact squared distance, exactly 1.0f past the cut-off and nowhere else.  The geometry cases run at sigma = 7.5 with
+# every pixel nearer than 257 px to the boundary, where one ulp pins D^2 itself (tests/test_cedt_cpu.py asserts that of the
+# cases, and validates the reference).  Each test prints its worst difference and the share of pixels held to an exact D^2.
+# ------------------------------------------------------------------------------------------------------------------
+def _weight(t, sigma, dev, **kw):
+    from pemp_amd import ops
+    return ops.cedt_weight(torch.from_numpy(np.array(t)).to(dev), sigma, **kw)
+
+
+def _checked(label, got, t, sigma, k=None):
+    from tests import cedt_ref as R
+    worst, share = R.check(got.cpu().numpy(), t, sigma, k)
+    print(f"cedt {label} sigma {sigma:g}: worst {worst:g} ulp, exact D^2 on {100 * share:.2f} % of {np.size(t)} pixels")
+    return worst, share
+
+
+def _geometry_names():
+    from tests import cedt_ref as R
+    return list(R.GEOMETRY)
+
+
+@pytest.mark.parametrize("name", _geometry_names())
+def test_cedt_geometry_cases_have_the_exact_squared_distance(hip_lib, dev, name):
+    """Column pass with the LDS opt-in (H >= 342), with 32 .. 2 columns per strip and 8 .. 128 row segments (H >= 833), ragged
+    last strips, an empty segment between two occupied ones, images shorter than the segment count, the 254-pixel pieces of
+    the boundary pass, clamped row scans (W > 4096), and a batch that mixes an image without any boundary with others."""
+    from tests import cedt_ref as R
+    t, k = R.case(name)
+    got = _weight(t, R.GEOMETRY_SIGMA, dev)
+    worst, share = _checked(name, got, t, R.GEOMETRY_SIGMA, k)
+    assert share == 1.0
+    if name in R.SEAM:                       # the boundary map itself: tab[0] = 2.0f on the boundary and nowhere else
+        assert np.array_equal(got.cpu().numpy() == R.tab(R.GEOMETRY_SIGMA)[0], R.boundary(t))
+
+
+def test_cedt_wide_row_far_from_its_only_blob(hip_lib, dev):
+    """3 x 4097 with one blob at the left end: the clamped scan runs the whole row.  Outside the every-pixel condition: only
+    the first ~257 columns (6.3 % of the pixels) are held to an exact D^2, the rest to one ulp, and from 936 px on to exactly
+    1.0f, which says of the distance only that it is past the cut-off."""
+    from tests import cedt_ref as R
+    t = R.left_blob(3, 4097)
+    worst, share = _checked("far-3x4097", _weight(t, R.GEOMETRY_SIGMA, dev), t, R.GEOMETRY_SIGMA)
+    assert 0.06 < share < 0.07
+
+
+@pytest.mark.parametrize("sigma", [0.5, 1.0, 5.0, 7.8])
+def test_cedt_other_sigmas_and_the_cut_off(hip_lib, dev, sigma):
+    """A 3 x 600 row with one blob at the left end crosses the cut-off at sigma <= 5 (18.6 px at sigma = 1, 418 px at 5): one
+    ulp before it, exactly 1.0f from the first table entry that is 1.0f.  The 97 x 97 target of the tests above at the same
+    sigmas."""
+    from tests import cedt_ref as R
+    t = R.left_blob(3, 600)
+    k = R.k_ref(R.boundary(t))
+    if sigma <= 5.0:
+        assert k.max() > R.k_cut(sigma) and (k == k[k < R.k_cut(sigma)].max()).any()
+    got = _weight(t, sigma, dev)
+    _checked("row-3x600", got, t, sigma, k)
+    past = k >= R.k_cut(sigma)
+    assert (got.cpu().numpy()[past] == 1.0).all() and (got.cpu().numpy()[~past] > 1.0).all()
+    t = R.existing_97()
+    _checked("masks-97x97", _weight(t, sigma, dev), t, sigma)
+
+
+def test_cedt_refusals_leave_the_next_call_intact(hip_lib, dev):
+    from pemp_amd import ops
+    from pemp_amd._lib import PempHipError
+    from tests import cedt_ref as R
+    t, k = R.case("mixed-batch-40x57")
+    td = torch.from_numpy(np.array(t)).to(dev)
+
+    def still_right():
+        assert R.check(ops.cedt_weight(td, R.GEOMETRY_SIGMA).cpu().numpy(), t, R.GEOMETRY_SIGMA, k)[1] == 1.0
+
+    for sigma, why in ((8.0, "sigma too large"), (0.0, "bad arguments"), (-1.0, "bad arguments")):
+        with pytest.raises(PempHipError, match=why):
+            ops.cedt_weight(td, sigma)
+        still_right()
+    for shape in ((1, 16385, 1), (1, 1, 16385)):
+        with pytest.raises(PempHipError, match="label images too large"):
+            ops.cedt_weight(torch.zeros(shape, dtype=torch.int64, device=dev), 5.0)
+        still_right()
+    for bad in (td.to(torch.int32), td.transpose(1, 2), td[:, :, ::2], td[0]):
+        with pytest.raises(ValueError, match="contiguous int64"):
+            ops.cedt_weight(bad, 5.0)
+        still_right()
+
+
+def test_cedt_call_sequence_through_one_workspace_cache(hip_lib, dev):
+    """Small, opted-in, narrowed and small again through one ws_cache: the LDS opt-in of an earlier launch and the workspaces
+    of other shapes leave no trace; the same target twice gives the same bits."""
+    from tests import cedt_ref as R
+    ws = {}
+    small = R.existing_97()
+    first = _weight(small, 5.0, dev, ws_cache=ws)
+    _checked("masks-97x97", first, small, 5.0)
+    for name in ("tall-401x70-s1", "tall-833x70-s1"):
+        t, k = R.case(name)
+        got = _weight(t, R.GEOMETRY_SIGMA, dev, ws_cache=ws)
+        assert _checked(name, got, t, R.GEOMETRY_SIGMA, k)[1] == 1.0
+        assert torch.equal(got, _weight(t, R.GEOMETRY_SIGMA, dev, ws_cache=ws))
+    again = _weight(small, 5.0, dev, ws_cache=ws)
+    _checked("masks-97x97", again, small, 5.0)
+    assert torch.equal(first, again)
+    assert len(ws) == 3
