@@ -333,6 +333,35 @@ int pemp_nway_tail_f32(const float* pred, const int64_t* target, const int32_t* 
                        float* margin, double* stats, void* ws, size_t ws_bytes,
                        int N, int K, int h, int w, int Ho, int Wo, void* stream);
 
+/* Ragged forms of both tails: ONE launch pair for a batch whose images each have their own output size (a query label keeps
+ * its size at test time: mask_mode 3 below).  One descriptor per image; the host fills Ho, Wo, calls
+ * pemp_tail_ragged_workspace_bytes() (validates, fills the "planned" fields, returns the workspace size; 0 on error), uploads
+ * the descriptors and calls a tail with both copies (the host copy is read during the call only; the kernels read, never
+ * write, the device copy).  target, pred_out / labels and margin are PACKED: image i's [Ho_i][Wo_i] map starts at element
+ * pix_off_i, the maps lie end to end in the batch's order.  Image i is walked by exactly nblk_i blocks in the fixed-size
+ * tail's order and its partial sums are added in the fixed-size tail's order: per image, every result is bit for bit what
+ * pemp_eval_tail_f32 / pemp_nway_tail_f32 give for that image alone.  Deterministic (no atomics).  No weight map and no
+ * logits_out: those stay on the fixed-size calls.                                                                        */
+typedef struct pemp_tail_item {
+    int32_t Ho, Wo;        /* the image's output size                                                                    */
+    /* planned (pemp_tail_ragged_workspace_bytes): */
+    int32_t nblk;          /* blocks that walk the image: ceil(Ho * Wo / 1024), at least 1, at most 256                  */
+    int32_t part_off;      /* the image's first row of partial sums in the workspace ([8] doubles per block)             */
+    int64_t pix_off;       /* element offset of the image inside the packed arrays: the running sum of Ho * Wo           */
+} pemp_tail_item;
+
+size_t pemp_tail_ragged_workspace_bytes(pemp_tail_item* items_host, int n);
+/* pred [B][2][h][w]; target packed int64 and stats [B][8]: both or neither (neither: arg-max only); pred_out packed uint8. */
+int pemp_eval_tail_ragged_f32(const float* pred, const int64_t* target, const pemp_tail_item* items_host,
+                              const pemp_tail_item* items_dev, int B, int h, int w, uint8_t* pred_out,
+                              double* stats, void* ws, size_t ws_bytes, void* stream);
+/* pred [N][K][2][h][w]; target packed int64, want int32 [N] on the device, stats [N][8]: all three or none; labels packed
+ * uint8; margin packed fp32 or NULL.                                                                                     */
+int pemp_nway_tail_ragged_f32(const float* pred, const int64_t* target, const int32_t* want,
+                              const pemp_tail_item* items_host, const pemp_tail_item* items_dev, int N, int K,
+                              int h, int w, uint8_t* labels, float* margin, double* stats, void* ws,
+                              size_t ws_bytes, void* stream);
+
 /* ResNetCM.comm statistics (networks/backbones.py:208-216): mask' = max_pool2d(mask,3,stride,1);
  * mean over ALL pixels and max over pixels of x*mask' per image and channel.
  *   x [N][Hx*Wx][ldx], mask_in [N][Hm][Wm], mask_out [N][Hx][Wx], stat [N][2][C] (mean, max).

@@ -31,6 +31,11 @@ class SampleDesc(C.Structure):
                 ("ws_off", C.c_int64)]
 
 
+class TailItem(C.Structure):
+    """struct pemp_tail_item (include/pemp_hip.h): one image of a ragged tail."""
+    _fields_ = [(n, C.c_int32) for n in ("Ho", "Wo", "nblk", "part_off")] + [("pix_off", C.c_int64)]
+
+
 CONV_RELU = 1
 CONV_SHIFT_PER_IMAGE = 2
 CONV_STEM4 = 4
@@ -77,6 +82,9 @@ SYMBOLS = {
     "pemp_eval_tail_f32": (c_int, [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_size] + [c_int] * 5 + [c_fp]),
     "pemp_nway_tail_workspace_bytes": (c_size, [c_int] * 3),
     "pemp_nway_tail_f32": (c_int, [c_fp] * 7 + [c_size] + [c_int] * 6 + [c_fp]),
+    "pemp_tail_ragged_workspace_bytes": (c_size, [C.POINTER(TailItem), c_int]),
+    "pemp_eval_tail_ragged_f32": (c_int, [c_fp, c_fp, C.POINTER(TailItem), c_fp] + [c_int] * 3 + [c_fp, c_fp, c_fp, c_size, c_fp]),
+    "pemp_nway_tail_ragged_f32": (c_int, [c_fp, c_fp, c_fp, C.POINTER(TailItem), c_fp] + [c_int] * 4 + [c_fp] * 4 + [c_size, c_fp]),
     "pemp_cm_reduce_f32": (c_int, [c_fp, c_int, c_fp, c_fp, c_fp] + [c_int] * 7 + [c_fp]),
     "pemp_argmax_masks_f32": (c_int, [c_fp, c_fp, c_int, c_int, c_fp]),
     "pemp_cm_reduce_arg_f32": (c_int, [c_fp, c_int, c_fp, c_fp, c_fp, c_fp] + [c_int] * 7 + [c_fp]),

@@ -91,3 +91,21 @@ extern "C" int pemp_nway_tail_f32(const float* pred, const int64_t* target, cons
                                   int Ho, int Wo, void* stream) {
     return j8::pemp_nway_tail_f32(pred, target, want, labels, margin, stats, ws, ws_bytes, N, K, h, w, Ho, Wo, stream);
 }
+
+extern "C" size_t pemp_tail_ragged_workspace_bytes(pemp_tail_item* items_host, int n) {
+    return j8::pemp_tail_ragged_workspace_bytes(items_host, n);
+}
+
+extern "C" int pemp_eval_tail_ragged_f32(const float* pred, const int64_t* target, const pemp_tail_item* items_host,
+                                         const pemp_tail_item* items_dev, int B, int h, int w, uint8_t* pred_out,
+                                         double* stats, void* ws, size_t ws_bytes, void* stream) {
+    return j8::pemp_eval_tail_ragged_f32(pred, target, items_host, items_dev, B, h, w, pred_out, stats, ws, ws_bytes, stream);
+}
+
+extern "C" int pemp_nway_tail_ragged_f32(const float* pred, const int64_t* target, const int32_t* want,
+                                         const pemp_tail_item* items_host, const pemp_tail_item* items_dev, int N, int K,
+                                         int h, int w, uint8_t* labels, float* margin, double* stats, void* ws,
+                                         size_t ws_bytes, void* stream) {
+    return j8::pemp_nway_tail_ragged_f32(pred, target, want, items_host, items_dev, N, K, h, w, labels, margin, stats, ws,
+                                         ws_bytes, stream);
+}

@@ -872,6 +872,52 @@ __device__ __forceinline__ void tail_block_sums(const double (&v)[8], double* __
     }
 }
 
+// What a tail thread adds up over its pixels: the CE sum, the weight sum, and valid, tp0, fp0, fn0, tp1, fp1, fn1.
+struct TailAcc {
+    double ce = 0.0, wsum = 0.0;
+    int cnt[7] = {0, 0, 0, 0, 0, 0, 0};
+    __device__ __forceinline__ void count(int am, int t) {
+        cnt[0]++;
+        for (int j = 0; j < 2; ++j) {
+            cnt[1 + 3 * j] += (am == j && t == j);
+            cnt[2 + 3 * j] += (am == j && t != j);
+            cnt[3 + 3 * j] += (am != j && t == j);
+        }
+    }
+    __device__ __forceinline__ void rows(double (&v)[8]) const {
+        v[0] = ce;
+        for (int k = 0; k < 7; ++k) v[k + 1] = (double)cnt[k];
+    }
+};
+
+// Pixel i of one image of the eval tail; the fixed-size and the ragged kernel both call it, so the arithmetic exists once.
+// p0, p1: the image's two low-resolution planes; target, weight, pred_out, lg0, lg1: at the image's first pixel (or null).
+__device__ __forceinline__ void eval_tail_pixel(const float* __restrict__ p0, const float* __restrict__ p1,
+                                                const int64_t* __restrict__ target, const float* __restrict__ weight,
+                                                uint8_t* __restrict__ pred_out, float* __restrict__ lg0, float* __restrict__ lg1,
+                                                int i, int h, int w, int Ho, int Wo, TailAcc& a) {
+    int Y = i / Wo, X = i - Y * Wo;
+    Bilin by = bilin_exact(Y, h, Ho), bx = bilin_exact(X, w, Wo);
+    float l0 = bilerp(p0, w, by, bx), l1 = bilerp(p1, w, by, bx);
+    int am = l1 > l0 ? 1 : 0;
+    pred_out[i] = (uint8_t)am;
+    if (lg0) {
+        lg0[i] = l0;
+        lg1[i] = l1;
+    }
+    if (target) {
+        int t = (int)target[i];
+        // CELossDT (core/losses.py:33-43): per-pixel weights; the denominator sums the weight of EVERY
+        // pixel, ignored ones included (their CE term is zero)
+        const float wgt = weight ? weight[i] : 1.f;
+        a.wsum += (double)wgt;
+        if (t != 255) {
+            a.ce += (double)(ce_pixel(l0, l1, t) * wgt);
+            a.count(am, t);
+        }
+    }
+}
+
 // eval tail: upsample + argmax + CE partials + tp/fp/fn partials.  part[b][blk][8] doubles.
 __global__ __launch_bounds__(256) void eval_tail_kernel(const float* __restrict__ pred,
                                                         const int64_t* __restrict__ target,
@@ -880,55 +926,71 @@ __global__ __launch_bounds__(256) void eval_tail_kernel(const float* __restrict_
                                                         double* __restrict__ part, int h, int w, int Ho, int Wo) {
     const int b = blockIdx.y;
     const int npix = Ho * Wo;
+    const size_t at = (size_t)b * npix;
     const float* p0 = pred + (size_t)b * 2 * h * w;
-    const float* p1 = p0 + h * w;
-    double ce = 0.0, wsum = 0.0;
-    int cnt[7] = {0, 0, 0, 0, 0, 0, 0};  // valid, tp0, fp0, fn0, tp1, fp1, fn1
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < npix; i += gridDim.x * 256) {
-        int Y = i / Wo, X = i - Y * Wo;
-        Bilin by = bilin_exact(Y, h, Ho), bx = bilin_exact(X, w, Wo);
-        float l0 = bilerp(p0, w, by, bx), l1 = bilerp(p1, w, by, bx);
-        int am = l1 > l0 ? 1 : 0;
-        pred_out[(size_t)b * npix + i] = (uint8_t)am;
-        if (logits) {
-            logits[((size_t)b * 2 + 0) * npix + i] = l0;
-            logits[((size_t)b * 2 + 1) * npix + i] = l1;
-        }
-        if (target) {
-            int t = (int)target[(size_t)b * npix + i];
-            // CELossDT (core/losses.py:33-43): per-pixel weights; the denominator sums the weight of EVERY
-            // pixel, ignored ones included (their CE term is zero)
-            const float wgt = weight ? weight[(size_t)b * npix + i] : 1.f;
-            wsum += (double)wgt;
-            if (t != 255) {
-                ce += (double)(ce_pixel(l0, l1, t) * wgt);
-                cnt[0]++;
-                for (int j = 0; j < 2; ++j) {
-                    cnt[1 + 3 * j] += (am == j && t == j);
-                    cnt[2 + 3 * j] += (am == j && t != j);
-                    cnt[3 + 3 * j] += (am != j && t == j);
-                }
-            }
-        }
-    }
+    TailAcc a;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < npix; i += gridDim.x * 256)
+        eval_tail_pixel(p0, p0 + h * w, target ? target + at : nullptr, weight ? weight + at : nullptr, pred_out + at,
+                        logits ? logits + 2 * at : nullptr, logits ? logits + 2 * at + npix : nullptr, i, h, w, Ho, Wo, a);
     double v[8];
-    v[0] = ce;
-    for (int k = 0; k < 7; ++k) v[k + 1] = (double)cnt[k];
-    if (weight) v[1] = wsum;      // loss denominator: sum of weights instead of the valid-pixel count
+    a.rows(v);
+    if (weight) v[1] = a.wsum;    // loss denominator: sum of weights instead of the valid-pixel count
     tail_block_sums(v, part + ((size_t)b * gridDim.x + blockIdx.x) * 8);
 }
-// one wave per (episode, statistic): lane-strided partial sums then a fixed butterfly -> deterministic
+
+// Statistic k of one image: its nblk partial rows summed lane-strided, then a fixed butterfly -> deterministic
+__device__ __forceinline__ double tail_final_sum(const double* __restrict__ rows, int nblk, int k, int lane) {
+    double s = 0.0;
+    for (int i = lane; i < nblk; i += 64) s += rows[(size_t)i * 8 + k];
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    return s;
+}
+// one wave per (episode, statistic)
 __global__ void eval_tail_final_kernel(const double* __restrict__ part, double* __restrict__ stats, int nblk) {
     const int b = blockIdx.x, k = blockIdx.y, lane = threadIdx.x;
-    double s = 0.0;
-    for (int i = lane; i < nblk; i += 64) s += part[((size_t)b * nblk + i) * 8 + k];
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    const double s = tail_final_sum(part + (size_t)b * nblk * 8, nblk, k, lane);
     if (lane == 0) stats[b * 8 + k] = s;
 }
 
 static inline int tail_blocks(int Ho, int Wo) {
     int nb = cdiv(Ho * Wo, 256 * 4);
     return nb < 1 ? 1 : (nb > 256 ? 256 : nb);
+}
+
+// Pixel i of one image of the N-way tail, shared like eval_tail_pixel.  pn: the image's K plane pairs; wk: the wanted class
+// (-1 without a target); target, labels, margin: at the image's first pixel (or null).
+__device__ __forceinline__ void nway_tail_pixel(const float* __restrict__ pn, const int64_t* __restrict__ target, int wk,
+                                                uint8_t* __restrict__ labels, float* __restrict__ margin, int i, int K, int h,
+                                                int w, int Ho, int Wo, TailAcc& a) {
+    const int hw = h * w;
+    int Y = i / Wo, X = i - Y * Wo;
+    Bilin by = bilin_exact(Y, h, Ho), bx = bilin_exact(X, w, Wo);
+    int best = 0;                               // the label so far
+    float bm = 0.f, top = -INFINITY;            // its margin; the largest margin of all classes
+    float w0 = 0.f, w1 = 0.f;                   // the wanted class's own logits
+    const float* p = pn;
+    for (int k = 0; k < K; ++k, p += 2 * hw) {
+        float l0 = bilerp(p, w, by, bx), l1 = bilerp(p + hw, w, by, bx);
+        float m = __fsub_rn(l1, l0);
+        if (l1 > l0 && (best == 0 || m > bm)) {
+            best = k + 1;
+            bm = m;
+        }
+        if (m > top) top = m;
+        if (k == wk) {
+            w0 = l0;
+            w1 = l1;
+        }
+    }
+    labels[i] = (uint8_t)best;
+    if (margin) margin[i] = best ? bm : top;
+    if (target) {
+        int t = (int)target[i];
+        if (t != 255) {
+            a.ce += (double)ce_pixel(w0, w1, t);
+            a.count(best == wk + 1 ? 1 : 0, t);
+        }
+    }
 }
 
 // N-way tail: the K binary maps of an all-classes bank call pred[n][k][2][h][w] fused into one label map.  Per output pixel the
@@ -942,52 +1004,74 @@ __global__ __launch_bounds__(256) void nway_tail_kernel(const float* __restrict_
                                                         float* __restrict__ margin, double* __restrict__ part, int K, int h,
                                                         int w, int Ho, int Wo) {
     const int n = blockIdx.y;
-    const int npix = Ho * Wo, hw = h * w;
-    const float* pn = pred + (size_t)n * K * 2 * hw;
+    const int npix = Ho * Wo;
+    const size_t at = (size_t)n * npix;
+    const float* pn = pred + (size_t)n * K * 2 * h * w;
     const int wk = target ? want[n] : -1;
-    double ce = 0.0;
-    int cnt[7] = {0, 0, 0, 0, 0, 0, 0};  // valid, tp0, fp0, fn0, tp1, fp1, fn1
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < npix; i += gridDim.x * 256) {
-        int Y = i / Wo, X = i - Y * Wo;
-        Bilin by = bilin_exact(Y, h, Ho), bx = bilin_exact(X, w, Wo);
-        int best = 0;                               // the label so far
-        float bm = 0.f, top = -INFINITY;            // its margin; the largest margin of all classes
-        float w0 = 0.f, w1 = 0.f;                   // the wanted class's own logits
-        const float* p = pn;
-        for (int k = 0; k < K; ++k, p += 2 * hw) {
-            float l0 = bilerp(p, w, by, bx), l1 = bilerp(p + hw, w, by, bx);
-            float m = __fsub_rn(l1, l0);
-            if (l1 > l0 && (best == 0 || m > bm)) {
-                best = k + 1;
-                bm = m;
-            }
-            if (m > top) top = m;
-            if (k == wk) {
-                w0 = l0;
-                w1 = l1;
-            }
-        }
-        labels[(size_t)n * npix + i] = (uint8_t)best;
-        if (margin) margin[(size_t)n * npix + i] = best ? bm : top;
-        if (target) {
-            int t = (int)target[(size_t)n * npix + i];
-            if (t != 255) {
-                int am = best == wk + 1 ? 1 : 0;
-                ce += (double)ce_pixel(w0, w1, t);
-                cnt[0]++;
-                for (int j = 0; j < 2; ++j) {
-                    cnt[1 + 3 * j] += (am == j && t == j);
-                    cnt[2 + 3 * j] += (am == j && t != j);
-                    cnt[3 + 3 * j] += (am != j && t == j);
-                }
-            }
-        }
-    }
+    TailAcc a;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < npix; i += gridDim.x * 256)
+        nway_tail_pixel(pn, target ? target + at : nullptr, wk, labels + at, margin ? margin + at : nullptr, i, K, h, w, Ho, Wo,
+                        a);
     if (!target) return;                            // uniform over the grid: no statistics asked for
     double v[8];
-    v[0] = ce;
-    for (int k = 0; k < 7; ++k) v[k + 1] = (double)cnt[k];
+    a.rows(v);
     tail_block_sums(v, part + ((size_t)n * gridDim.x + blockIdx.x) * 8);
+}
+
+// Ragged tails: image b has its own output size, items[b] (pemp_tail_item, planned by pemp_tail_ragged_workspace_bytes).  Grid
+// (max nblk, B): image b is walked by its first nblk_b blocks exactly as the fixed-size kernel walks it alone -- pixel
+// blk * 256 + tid, stride nblk_b * 256, the same pixel body, tail_block_sums, the same final sum -- so its results are the
+// fixed-size tail's bit for bit; the other blocks of the row leave at once.  The descriptor read is uniform per block and the
+// kernels only read it.  target, labels and margin are packed end to end: image b starts at element pix_off.
+__global__ __launch_bounds__(256) void eval_tail_ragged_kernel(const float* __restrict__ pred, const int64_t* __restrict__ target,
+                                                               const pemp_tail_item* __restrict__ items,
+                                                               uint8_t* __restrict__ pred_out, double* __restrict__ part, int h,
+                                                               int w) {
+    const int b = blockIdx.y;
+    const pemp_tail_item it = items[b];
+    if ((int)blockIdx.x >= it.nblk) return;
+    const int npix = it.Ho * it.Wo;
+    const float* p0 = pred + (size_t)b * 2 * h * w;
+    TailAcc a;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < npix; i += it.nblk * 256)
+        eval_tail_pixel(p0, p0 + h * w, target ? target + it.pix_off : nullptr, nullptr, pred_out + it.pix_off, nullptr, nullptr,
+                        i, h, w, it.Ho, it.Wo, a);
+    if (!target) return;
+    double v[8];
+    a.rows(v);
+    tail_block_sums(v, part + ((size_t)it.part_off + blockIdx.x) * 8);
+}
+
+// (8 waves per SIMD asked for: left alone the descriptor's fields take the kernel to 70 VGPRs and 7 waves, 7 % slower than
+// nway_tail_kernel's 62 and 8 on equal sizes)
+__global__ __launch_bounds__(256, 8) void nway_tail_ragged_kernel(const float* __restrict__ pred, const int64_t* __restrict__ target,
+                                                               const int32_t* __restrict__ want,
+                                                               const pemp_tail_item* __restrict__ items,
+                                                               uint8_t* __restrict__ labels, float* __restrict__ margin,
+                                                               double* __restrict__ part, int K, int h, int w) {
+    const int n = blockIdx.y;
+    const pemp_tail_item it = items[n];
+    if ((int)blockIdx.x >= it.nblk) return;
+    const int npix = it.Ho * it.Wo;
+    const float* pn = pred + (size_t)n * K * 2 * h * w;
+    const int wk = target ? want[n] : -1;
+    TailAcc a;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < npix; i += it.nblk * 256)
+        nway_tail_pixel(pn, target ? target + it.pix_off : nullptr, wk, labels + it.pix_off,
+                        margin ? margin + it.pix_off : nullptr, i, K, h, w, it.Ho, it.Wo, a);
+    if (!target) return;
+    double v[8];
+    a.rows(v);
+    tail_block_sums(v, part + ((size_t)it.part_off + blockIdx.x) * 8);
+}
+
+// one wave per (image, statistic), over the image's own nblk partial rows
+__global__ void tail_final_ragged_kernel(const double* __restrict__ part, const pemp_tail_item* __restrict__ items,
+                                         double* __restrict__ stats) {
+    const int b = blockIdx.x, k = blockIdx.y, lane = threadIdx.x;
+    const pemp_tail_item it = items[b];
+    const double s = tail_final_sum(part + (size_t)it.part_off * 8, it.nblk, k, lane);
+    if (lane == 0) stats[b * 8 + k] = s;
 }
 
 }  // namespace PEMP_HEAD_NS
@@ -1224,6 +1308,87 @@ static int pemp_nway_tail_f32(const float* pred, const int64_t* target, const in
     if (stats)
         hipLaunchKernelGGL(eval_tail_final_kernel, dim3(N, 8), dim3(64), 0, (hipStream_t)stream, (const double*)ws, stats, nb);
     return launch_status("nway_tail");
+}
+
+// Ragged tails: the planner (host only) and the two launches.  A pixel count stays below 2^31 - 2^16, so that the walk's
+// index cannot wrap when the last stride (at most 256 * 256) is added.
+static inline bool tail_item_ok(const pemp_tail_item& it) {
+    return it.Ho >= 1 && it.Wo >= 1 && (long long)it.Ho * it.Wo < (1LL << 31) - (1LL << 16);
+}
+
+static size_t pemp_tail_ragged_workspace_bytes(pemp_tail_item* items, int n) {
+    if (!items || n < 1 || n > 65535) {
+        set_error("tail_ragged: bad arguments (items %p, n = %d; 1 <= n <= 65535)", (void*)items, n);
+        return 0;
+    }
+    long long pix = 0, blk = 0;
+    for (int i = 0; i < n; ++i) {
+        pemp_tail_item& it = items[i];
+        if (!tail_item_ok(it)) {
+            set_error("tail_ragged: item %d has the size %d x %d", i, it.Ho, it.Wo);
+            return 0;
+        }
+        it.nblk = tail_blocks(it.Ho, it.Wo);
+        it.part_off = (int32_t)blk;
+        it.pix_off = pix;
+        blk += it.nblk;
+        pix += (long long)it.Ho * it.Wo;
+    }
+    return (size_t)blk * 8 * sizeof(double);
+}
+
+// The host copy of the descriptors checked against the plan -> the widest image's block count (the grid's x), or -1.
+static int tail_ragged_check(const char* what, const pemp_tail_item* items, int n, size_t ws_bytes) {
+    long long pix = 0, blk = 0;
+    int widest = 0;
+    for (int i = 0; i < n; ++i)
+        PEMP_REQUIRE(tail_item_ok(items[i]), "%s: item %d has the size %d x %d", what, i, items[i].Ho, items[i].Wo);
+    for (int i = 0; i < n; ++i) {
+        const pemp_tail_item& it = items[i];
+        PEMP_REQUIRE(it.nblk == tail_blocks(it.Ho, it.Wo) && it.part_off == blk && it.pix_off == pix,
+                     "%s: item %d was not planned (pemp_tail_ragged_workspace_bytes)", what, i);
+        blk += it.nblk;
+        pix += (long long)it.Ho * it.Wo;
+        widest = widest > it.nblk ? widest : it.nblk;
+    }
+    PEMP_REQUIRE(ws_bytes >= (size_t)blk * 8 * sizeof(double), "%s: workspace too small", what);
+    return widest;
+}
+
+static int pemp_eval_tail_ragged_f32(const float* pred, const int64_t* target, const pemp_tail_item* items_host,
+                                     const pemp_tail_item* items_dev, int B, int h, int w, uint8_t* pred_out, double* stats,
+                                     void* ws, size_t ws_bytes, void* stream) {
+    PEMP_REQUIRE(pred && items_host && items_dev && pred_out && ws, "eval_tail_ragged: null pointer");
+    PEMP_REQUIRE((target != nullptr) == (stats != nullptr), "eval_tail_ragged: target and stats come together");
+    PEMP_REQUIRE(B >= 1 && B <= 65535 && h > 0 && w > 0 && (long long)h * w < (1LL << 29), "eval_tail_ragged: bad dims");
+    const int nb = tail_ragged_check("eval_tail_ragged", items_host, B, ws_bytes);
+    if (nb < 0) return -1;
+    hipLaunchKernelGGL(eval_tail_ragged_kernel, dim3(nb, B), dim3(256), 0, (hipStream_t)stream, pred, target, items_dev,
+                       pred_out, (double*)ws, h, w);
+    if (stats)
+        hipLaunchKernelGGL(tail_final_ragged_kernel, dim3(B, 8), dim3(64), 0, (hipStream_t)stream, (const double*)ws, items_dev,
+                           stats);
+    return launch_status("eval_tail_ragged");
+}
+
+static int pemp_nway_tail_ragged_f32(const float* pred, const int64_t* target, const int32_t* want,
+                                     const pemp_tail_item* items_host, const pemp_tail_item* items_dev, int N, int K, int h,
+                                     int w, uint8_t* labels, float* margin, double* stats, void* ws, size_t ws_bytes,
+                                     void* stream) {
+    PEMP_REQUIRE(pred && items_host && items_dev && labels && ws, "nway_tail_ragged: null pointer");
+    PEMP_REQUIRE((target != nullptr) == (want != nullptr) && (target != nullptr) == (stats != nullptr),
+                 "nway_tail_ragged: target, want and stats come together");
+    PEMP_REQUIRE(N >= 1 && N <= 65535 && K > 0 && h > 0 && w > 0 && (long long)h * w < (1LL << 29),
+                 "nway_tail_ragged: bad dims");
+    PEMP_REQUIRE(K <= 255, "nway_tail_ragged: K <= 255 (the labels are uint8, 0 = no class)");
+    const int nb = tail_ragged_check("nway_tail_ragged", items_host, N, ws_bytes);
+    if (nb < 0) return -1;
+    hipLaunchKernelGGL(nway_tail_ragged_kernel, dim3(nb, N), dim3(256), 0, (hipStream_t)stream, pred, target, want, items_dev,
+                       labels, margin, (double*)ws, K, h, w);
+    if (stats)
+        hipLaunchKernelGGL(tail_final_ragged_kernel, dim3(N, 8), dim3(64), 0, (hipStream_t)stream, (const double*)ws, items_dev,
+                           stats);
+    return launch_status("nway_tail_ragged");
 }
 
 }  // namespace PEMP_HEAD_NS

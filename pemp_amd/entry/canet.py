@@ -144,21 +144,12 @@ class Evaluator(_Evaluator):
         if max(write) >= self.table.shape[0]:
             raise ValueError("the history table is too small for this round: call reset_history with the round's key count")
         dev_in = [torch.cat([ep[0][k].to(self.device, non_blocking=True) for ep in episodes]) for k in range(3)]
-        labels = [ep[1].view(-1, *ep[1].shape[-2:]).to(self.device, non_blocking=True) for ep in episodes]
+        labels = [ep[1].view(-1, *ep[1].shape[-2:]) for ep in episodes]
         rs = torch.tensor(read, dtype=torch.int32).to(self.device, non_blocking=True)
         ws = torch.tensor(write, dtype=torch.int32).to(self.device, non_blocking=True)
         with torch.no_grad(), ops.eval_splitk(ops.EVAL_SPLITK if self.splitk is None else self.splitk):
             fn = self.model.lowres_graphed_slots if self.use_graph else self.model.lowres_slots
-            pred = fn(*dev_in, self.table, rs, ws)
-            stats = torch.empty((len(episodes), 8), dtype=torch.float64, device=self.device)
-            by_size = {}
-            for i, lab in enumerate(labels):
-                by_size.setdefault(tuple(lab.shape[-2:]), []).append(i)
-            for idx in by_size.values():
-                sel = torch.tensor(idx, device=self.device)
-                _, st, _ = ops.eval_tail(pred.index_select(0, sel), torch.cat([labels[i] for i in idx]), ws_cache=self._ws)
-                stats.index_copy_(0, sel, st)
-        return stats
+            return ops.tail_rows(fn(*dev_in, self.table, rs, ws), labels, ws_cache=self._ws)
 
     def eval_round(self, dataset, batch=1, rank=0, world=1):
         """One round after ``dataset.sample_tasks()``: -> (stats rows [n,8] on the GPU in this rank's episode order, classes)."""

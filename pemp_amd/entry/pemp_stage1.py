@@ -232,25 +232,14 @@ class Evaluator:
 
     def test_step_batch(self, episodes):
         """``episodes``: list of (inputs, qry_msk) with one episode each (any query-label sizes).  One encoder + head
-        pass for all of them, then one fused tail launch per distinct label size.  -> stats f64 [len(episodes), 8] on
-        the GPU, rows in the given order.  Per-episode results are identical to ``test_step_device`` on each episode
-        alone (every image's rows are independent in the conv GEMMs and all kernel variants are bit-identical)."""
+        pass for all of them, then one ragged tail launch for all label sizes (``ops.tail_rows``).  -> stats f64
+        [len(episodes), 8] on the GPU, rows in the given order.  Per-episode results are identical to ``test_step_device``
+        on each episode alone (every image's rows are independent in the conv GEMMs, all kernel variants are bit-identical
+        and the ragged tail walks every image as the fixed-size tail does)."""
         dev_in = [torch.cat([ep[0][k].to(self.device, non_blocking=True) for ep in episodes]) for k in range(3)]
-        labels = [ep[1].view(-1, *ep[1].shape[-2:]).to(self.device, non_blocking=True) for ep in episodes]
+        labels = [ep[1].view(-1, *ep[1].shape[-2:]) for ep in episodes]
         with torch.no_grad():
-            return self._tail_by_size(self._lowres(dev_in), labels)
-
-    def _tail_by_size(self, pred, labels):
-        """One fused tail launch per distinct label size -> stats f64 [len(labels), 8], rows in the given order."""
-        stats = torch.empty((len(labels), 8), dtype=torch.float64, device=self.device)
-        by_size = {}
-        for i, lab in enumerate(labels):
-            by_size.setdefault(tuple(lab.shape[-2:]), []).append(i)
-        for idx in by_size.values():
-            sel = torch.tensor(idx, device=self.device)
-            _, st, _ = ops.eval_tail(pred.index_select(0, sel), torch.cat([labels[i] for i in idx]), ws_cache=self._ws)
-            stats.index_copy_(0, sel, st)
-        return stats
+            return ops.tail_rows(self._lowres(dev_in), labels, ws_cache=self._ws)
 
     def _lowres(self, dev_in):
         """Feature-resolution prediction of a batch of episodes (stage 2 overrides: stage-1 prior first)."""
@@ -407,10 +396,10 @@ class BankEvaluator(Evaluator):
         """``episodes``: list of ((qry_img [1,1,3,H,W], bank slot), qry_msk).  -> stats f64 [len(episodes), 8] on the GPU."""
         qry = torch.cat([ep[0][0].to(self.device, non_blocking=True).flatten(0, 1) for ep in episodes])
         index = [ep[0][1] for ep in episodes]
-        labels = [ep[1].view(-1, *ep[1].shape[-2:]).to(self.device, non_blocking=True) for ep in episodes]
+        labels = [ep[1].view(-1, *ep[1].shape[-2:]) for ep in episodes]
         seg = self.model.segment_graphed if self.use_graph else self.model.segment_lowres
         with torch.no_grad(), ops.eval_splitk(ops.EVAL_SPLITK if self.splitk is None else self.splitk):
-            return self._tail_by_size(seg(self.bank, qry, index=index)[0], labels)
+            return ops.tail_rows(seg(self.bank, qry, index=index)[0], labels, ws_cache=self._ws)
 
     def test_step_device(self, inputs, qry_msk):
         """One query per step -> (None, stats f64 [1,8]): the arg-max image is not kept on this path."""
@@ -425,7 +414,7 @@ class NWayMixin:
     meeting EVERY class.  Per round the walk first enrolls the first task's supports of every validation class -- it stops
     as soon as all are enrolled, and a class that never occurs is an error: a competition against an empty slot would mean
     nothing -- then every query of the rank's shard is segmented against all classes (``segment_lowres`` without an index) and
-    ``ops.nway_tail`` decides each pixel, one launch per distinct label size, with the query's own slot as ``want``.  The rows
+    the N-way tail decides each pixel, one ragged launch for all label sizes, with the query's own slot as ``want``.  The rows
     keep the fused tail's layout: the loss is the class's own binary CE (``test_bank``'s), the counts -- hence mIoU and bIoU --
     are those of the class under K-way competition."""
 
@@ -453,23 +442,10 @@ class NWayMixin:
         """``episodes``: list of ((qry_img [1,1,3,H,W], bank slot), qry_msk).  -> stats f64 [len(episodes), 8] on the GPU."""
         qry = torch.cat([ep[0][0].to(self.device, non_blocking=True).flatten(0, 1) for ep in episodes])
         want = [ep[0][1] for ep in episodes]
-        labels = [ep[1].view(-1, *ep[1].shape[-2:]).to(self.device, non_blocking=True) for ep in episodes]
+        labels = [ep[1].view(-1, *ep[1].shape[-2:]) for ep in episodes]
         seg = self.model.segment_graphed if self.use_graph else self.model.segment_lowres
         with torch.no_grad(), ops.eval_splitk(ops.EVAL_SPLITK if self.splitk is None else self.splitk):
-            return self._nway_by_size(seg(self.bank, qry)[0], want, labels)
-
-    def _nway_by_size(self, pred, want, labels):
-        """``_tail_by_size`` on the all-classes prediction [N,K,2,h,w]: one N-way tail launch per distinct label size."""
-        stats = torch.empty((len(labels), 8), dtype=torch.float64, device=self.device)
-        by_size = {}
-        for i, lab in enumerate(labels):
-            by_size.setdefault(tuple(lab.shape[-2:]), []).append(i)
-        for idx in by_size.values():
-            sel = torch.tensor(idx, device=self.device)
-            _, _, st = ops.nway_tail(pred.index_select(0, sel), target=torch.cat([labels[i] for i in idx]),
-                                     want=[want[i] for i in idx], ws_cache=self._ws)
-            stats.index_copy_(0, sel, st)
-        return stats
+            return ops.tail_rows(seg(self.bank, qry)[0], labels, want=want, ws_cache=self._ws)
 
 
 class NWayEvaluator(NWayMixin, BankEvaluator):

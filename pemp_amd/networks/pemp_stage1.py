@@ -335,12 +335,25 @@ class _HeadMixin:
         where every class says background and else 1 + the slot of the class that claims it by the largest margin
         (foreground logit - background logit; the lowest slot wins equal margins).  -> labels uint8 [N,Ho,Wo] of slot
         numbers (``bank.labels`` maps them), with ``want_margin`` (labels, margin fp32 [N,Ho,Wo]).  ``out_shape`` defaults to
-        the query size.  No full-resolution logits are stored."""
+        the query size.  No full-resolution logits are stored.  ``out_shape`` may also be a sequence of N (Ho, Wo) pairs, one
+        per query (frames resized from different originals): then the result is a list of N uint8 maps [Ho_i,Wo_i], with
+        ``want_margin`` a list of N (labels, margin) pairs, every map a view into one packed buffer, from one ragged launch
+        (``ops.nway_tail_ragged``); each map equals the single-query call with that ``out_shape``."""
         self._segment_args(bank, qry_img, None, False, "segment_labels")
         if len(bank) > 255:
             raise ValueError(f"segment_labels: the bank holds {len(bank)} classes; the labels are uint8 with 0 for no class, "
                              "so at most 255")
+        ragged = out_shape is not None and all(hasattr(s, "__len__") for s in out_shape)      # pairs (or none at all), not two ints
+        if ragged:
+            out_shape = [tuple(int(v) for v in s) for s in out_shape]
+            if len(out_shape) != qry_img.shape[0] or any(len(s) != 2 or min(s) < 1 for s in out_shape):
+                raise ValueError(f"segment_labels: out_shape must be one (Ho, Wo) or one pair per query ({qry_img.shape[0]}), "
+                                 f"got {out_shape}")
         pred, _ = (self.segment_graphed if graphed else self.segment_lowres)(bank, qry_img)
+        if ragged:
+            labels, margin, _ = ops.nway_tail_ragged(pred, out_shape, want_margin=want_margin,
+                                                     ws_cache=self._engine_for(qry_img.device)["arena"].ws)
+            return list(zip(labels, margin)) if want_margin else labels
         out_shape = tuple(out_shape) if out_shape is not None else tuple(qry_img.shape[-2:])
         labels, margin, _ = ops.nway_tail(pred, out_shape, want_margin=want_margin, ws_cache=self._engine_for(qry_img.device)["arena"].ws)
         return (labels, margin) if want_margin else labels

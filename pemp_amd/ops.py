@@ -1287,6 +1287,145 @@ def nway_tail(pred, out_hw=None, target=None, want=None, want_margin=False, ws_c
     return labels, margin, stats
 
 
+def _ragged_plan(what, n, sizes, targets, device):
+    """The shared front of the ragged tails: checks ``sizes`` / ``targets`` (every refusal is a ValueError raised before any
+    device work), plans one ``pemp_tail_item`` per image on the host and uploads the descriptors as ONE non-blocking copy.
+    -> (items on the host, items on the device, [(Ho, Wo)], [pix_off] + [total], packed target | None, workspace bytes)."""
+    if (sizes is None) == (targets is None):
+        raise ValueError(f"{what}: give either sizes or targets")
+    if targets is not None:
+        targets = list(targets)
+        if len(targets) != n:
+            raise ValueError(f"{what}: {len(targets)} targets for {n} images")
+        for i, t in enumerate(targets):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.int64 or t.dim() not in (2, 3) or (t.dim() == 3 and t.shape[0] != 1):
+                raise ValueError(f"{what}: target {i} must be an int64 tensor [Ho,Wo] or [1,Ho,Wo], got "
+                                 f"{tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__} {getattr(t, 'dtype', '')}")
+        hw = [(int(t.shape[-2]), int(t.shape[-1])) for t in targets]
+    else:
+        sizes = list(sizes)
+        if len(sizes) != n:
+            raise ValueError(f"{what}: {len(sizes)} sizes for {n} images")
+        if any(len(tuple(s)) != 2 for s in sizes):
+            raise ValueError(f"{what}: every size is a (Ho, Wo) pair, got {sizes}")
+        hw = [(int(s[0]), int(s[1])) for s in sizes]
+    for i, (ho, wo) in enumerate(hw):
+        if ho < 1 or wo < 1:
+            raise ValueError(f"{what}: image {i} has the size {(ho, wo)}")
+    if device.type != "cuda":
+        raise _lib.PempHipError("pemp_amd ops need device (cuda/HIP) tensors; there is no CPU path")
+    lib = _lib.load()
+    items = (_lib.TailItem * n)()
+    for it, (ho, wo) in zip(items, hw):
+        it.Ho, it.Wo = ho, wo
+    nbytes = lib.pemp_tail_ragged_workspace_bytes(items, n)
+    if nbytes == 0:
+        raise ValueError(f"{what}: {lib.pemp_last_error().decode(errors='replace')}")
+    offs = [0]
+    for ho, wo in hw:                                               # pix_off: the running sum of Ho * Wo
+        offs.append(offs[-1] + ho * wo)
+    items_dev = torch.frombuffer(items, dtype=torch.uint8).to(device, non_blocking=True)
+    packed = None
+    if targets is not None:
+        if all(t.device.type == "cpu" for t in targets):
+            # every label uploaded into its place in the packed buffer.  (Packing on the host first and uploading once was
+            # measured at 12 ms per 25 PASCAL-sized labels, against 1.3 ms for the 25 uploads: profiles/ragged_tail_bench.txt)
+            packed = torch.empty(offs[-1], dtype=torch.int64, device=device)
+            for i, t in enumerate(targets):
+                packed[offs[i]:offs[i + 1]].copy_(t.reshape(-1), non_blocking=True)
+        else:
+            packed = torch.cat([t.to(device, non_blocking=True).reshape(-1) for t in targets])
+    return items, items_dev, hw, offs, packed, nbytes
+
+
+def _ragged_views(packed, hw):
+    return [flat.view(ho, wo) for flat, (ho, wo) in zip(packed.split([ho * wo for ho, wo in hw]), hw)]
+
+
+def eval_tail_ragged(pred, targets=None, sizes=None, ws_cache=None, views=True):
+    """``eval_tail`` for a batch whose images each have their own output size, in ONE launch pair: pred [B,2,h,w];
+    ``targets``, a list of B int64 tensors [Ho_i,Wo_i] or [1,Ho_i,Wo_i] (device tensors are flattened and concatenated, CPU
+    tensors are uploaded each into its place in the packed buffer), or ``sizes``, a list of B (Ho, Wo): arg-max only.
+    -> (am_list, stats f64 [B,8] | None without targets, am_packed uint8 [sum Ho_i * Wo_i]); ``am_list[i]`` is a
+    [Ho_i,Wo_i] view into ``am_packed`` (``views`` off: None -- a caller that wants the rows alone saves the B views).  Per image
+    every result is bit for bit ``eval_tail``'s on that image alone."""
+    if pred.dim() != 4 or pred.shape[1] != 2 or pred.dtype != torch.float32 or not pred.is_contiguous() or min(pred.shape) < 1:
+        raise ValueError(f"eval_tail_ragged: pred must be contiguous fp32 [B,2,h,w], got {tuple(pred.shape)} {pred.dtype}")
+    b, _, h, w = pred.shape
+    items, items_dev, hw, offs, target, nbytes = _ragged_plan("eval_tail_ragged", b, sizes, targets, pred.device)
+    lib = _lib.load()
+    am = torch.empty(offs[-1], dtype=torch.uint8, device=pred.device)
+    stats = torch.empty((b, 8), dtype=torch.float64, device=pred.device) if target is not None else None
+    ws = _ws(nbytes, pred.device, ws_cache, ("tail_ragged", b))       # one per B: it grows to the largest size mix seen
+    _lib.check(lib.pemp_eval_tail_ragged_f32(_p(pred), _p(target), items, _p(items_dev), b, h, w, _p(am), _p(stats), _p(ws),
+                                             ws.numel(), _stream()), "eval_tail_ragged")
+    return (_ragged_views(am, hw) if views else None), stats, am
+
+
+def nway_tail_ragged(pred, sizes=None, targets=None, want=None, want_margin=False, ws_cache=None, views=True):
+    """``nway_tail`` for a batch whose images each have their own output size, in ONE launch pair: pred fp32 [N,K,2,h,w];
+    ``sizes`` (a list of N (Ho, Wo)) or ``targets`` (a list of N int64 tensors, as in ``eval_tail_ragged``) with ``want``
+    (``nway_tail``'s).  -> (labels_list, margin_list | None, stats f64 [N,8] | None): the maps of image i are [Ho_i,Wo_i]
+    views into one packed buffer each (``views`` off: the packed buffers themselves).  Per image every result is bit for bit
+    ``nway_tail``'s on that image alone."""
+    if pred.dim() != 5 or pred.dtype != torch.float32 or not pred.is_contiguous() or pred.shape[2] != 2 or min(pred.shape) < 1:
+        raise ValueError(f"nway_tail_ragged: pred must be contiguous fp32 [N,K,2,h,w], got {tuple(pred.shape)} {pred.dtype}")
+    n, k, _, h, w = pred.shape
+    if k > 255:
+        raise ValueError(f"nway_tail_ragged: K = {k}: the labels are uint8 with 0 for no class, so K <= 255")
+    if (targets is None) != (want is None):
+        raise ValueError("nway_tail_ragged: targets and want come together")
+    if want is not None:
+        if isinstance(want, torch.Tensor) and want.device.type != "cpu":
+            if want.dtype != torch.int32 or tuple(want.shape) != (n,) or not want.is_contiguous():
+                raise ValueError(f"nway_tail_ragged: a device want must be contiguous int32 [{n}]")
+        else:
+            want = bank_index(want, n, k)
+    items, items_dev, hw, offs, target, nbytes = _ragged_plan("nway_tail_ragged", n, sizes, targets, pred.device)
+    if want is not None:
+        want = want.to(pred.device, non_blocking=True)
+    lib = _lib.load()
+    labels = torch.empty(offs[-1], dtype=torch.uint8, device=pred.device)
+    margin = torch.empty(offs[-1], dtype=torch.float32, device=pred.device) if want_margin else None
+    stats = torch.empty((n, 8), dtype=torch.float64, device=pred.device) if target is not None else None
+    ws = _ws(nbytes, pred.device, ws_cache, ("tail_ragged", n))
+    _lib.check(lib.pemp_nway_tail_ragged_f32(_p(pred), _p(target), _p(want), items, _p(items_dev), n, k, h, w, _p(labels),
+                                             _p(margin), _p(stats), _p(ws), ws.numel(), _stream()), "nway_tail_ragged")
+    if not views:
+        return labels, margin, stats
+    return _ragged_views(labels, hw), (_ragged_views(margin, hw) if want_margin else None), stats
+
+
+#: PEMP_RAGGED_TAIL=0 withholds the ragged tails from the evaluators: ``tail_rows`` then makes one fixed-size launch pair per
+#: distinct label size (A/B switch; scratch/ragged_tail_bench.py measures both)
+RAGGED_TAIL = os.environ.get("PEMP_RAGGED_TAIL", "1") != "0"
+
+
+def tail_rows(pred, labels, want=None, ws_cache=None):
+    """The statistics rows of a batch of episodes whose query labels keep their own sizes: pred [B,2,h,w] (``want`` None:
+    the eval tail) or [B,K,2,h,w] (``want``: the scored slot per query, the N-way tail), ``labels`` a list of B int64
+    tensors [1,Ho_i,Wo_i] on the host or the device.  -> stats f64 [B,8] on the GPU, rows in the given order: one ragged
+    launch pair, or with ``RAGGED_TAIL`` off one fixed-size launch pair per distinct label size.  Either way row i is the
+    fixed-size tail's on episode i alone."""
+    if RAGGED_TAIL:
+        if want is None:
+            return eval_tail_ragged(pred, labels, ws_cache=ws_cache, views=False)[1]
+        return nway_tail_ragged(pred, targets=labels, want=want, ws_cache=ws_cache, views=False)[2]
+    stats = torch.empty((len(labels), 8), dtype=torch.float64, device=pred.device)
+    by_size = {}
+    for i, lab in enumerate(labels):
+        by_size.setdefault(tuple(lab.shape[-2:]), []).append(i)
+    for idx in by_size.values():
+        sel = torch.tensor(idx, device=pred.device)
+        tgt = torch.cat([labels[i].to(pred.device, non_blocking=True) for i in idx])
+        if want is None:
+            st = eval_tail(pred.index_select(0, sel), tgt, ws_cache=ws_cache)[1]
+        else:
+            st = nway_tail(pred.index_select(0, sel), target=tgt, want=[want[i] for i in idx], ws_cache=ws_cache)[2]
+        stats.index_copy_(0, sel, st)
+    return stats
+
+
 def cm_reduce(x, mask_in, stride, want_argmax=False):
     """ResNetCM.comm statistics: x NHWC [N,h,w,C] (or None: pool the mask only); mask_in [N,Hm,Wm]
     -> (mask_out [N,h,w], stat [N,2,C] | None) (+ argmax int32 [N,C] with ``want_argmax``: the first maximal pixel,
