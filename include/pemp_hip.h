@@ -362,6 +362,28 @@ int pemp_nway_tail_ragged_f32(const float* pred, const int64_t* target, const in
                               int h, int w, uint8_t* labels, float* margin, double* stats, void* ws,
                               size_t ws_bytes, void* stream);
 
+/* N-way confusion tails: the label of the N-way tail above (the same device function decides the pixel) counted against a
+ * target, for semantic IoU over a bank.  pred [N][K][2][h][w]; conf int64 [N][K+1][K+1], overwritten:
+ * conf[n][t][p] = the counted pixels of image n with target class t and label p (0 = no class, 1 + slot otherwise).
+ *   want == NULL: target holds slot labels 0..K.  want != NULL (int32 [N] on the device): target is the binary mask
+ *   0 / 1 / 255 of class want[n], lifted on the fly: 0 stays 0, 1 becomes want[n] + 1.  In both forms 255, and every other
+ *   value that is not a class of the table, is ignored and never indexes it.
+ *   labels uint8 [N][Ho][Wo] (ragged: packed) or NULL: with NULL nothing is written per pixel; given, they are
+ *   pemp_nway_tail_f32's bit for bit.
+ * K <= 63: a block counts in (K + 1)^2 <= 4096 uint32 bins of LDS, bin (0,0) in registers, and adds its non-zero bins to conf
+ * with 64-bit integer atomics after the entry has cleared conf: integer sums, exact and identical run to run whatever the
+ * grid or N.  That flush needs no workspace: pemp_nway_confusion_workspace_bytes returns 0, and ws / ws_bytes are accepted
+ * (NULL / 0 will do) and not used.  The ragged form takes the descriptors pemp_tail_ragged_workspace_bytes planned
+ * (target and labels packed as for the ragged tails); per image its table is the fixed-size call's on that image alone. */
+size_t pemp_nway_confusion_workspace_bytes(int N, int K, int Ho, int Wo);
+int pemp_nway_confusion_f32(const float* pred, const int64_t* target, const int32_t* want,
+                            uint8_t* labels, int64_t* conf, void* ws, size_t ws_bytes,
+                            int N, int K, int h, int w, int Ho, int Wo, void* stream);
+int pemp_nway_confusion_ragged_f32(const float* pred, const int64_t* target, const int32_t* want,
+                                   const pemp_tail_item* items_host, const pemp_tail_item* items_dev,
+                                   int N, int K, int h, int w, uint8_t* labels, int64_t* conf,
+                                   void* ws, size_t ws_bytes, void* stream);
+
 /* ResNetCM.comm statistics (networks/backbones.py:208-216): mask' = max_pool2d(mask,3,stride,1);
  * mean over ALL pixels and max over pixels of x*mask' per image and channel.
  *   x [N][Hx*Wx][ldx], mask_in [N][Hm][Wm], mask_out [N][Hx][Wx], stat [N][2][C] (mean, max).

@@ -85,6 +85,9 @@ SYMBOLS = {
     "pemp_tail_ragged_workspace_bytes": (c_size, [C.POINTER(TailItem), c_int]),
     "pemp_eval_tail_ragged_f32": (c_int, [c_fp, c_fp, C.POINTER(TailItem), c_fp] + [c_int] * 3 + [c_fp, c_fp, c_fp, c_size, c_fp]),
     "pemp_nway_tail_ragged_f32": (c_int, [c_fp, c_fp, c_fp, C.POINTER(TailItem), c_fp] + [c_int] * 4 + [c_fp] * 4 + [c_size, c_fp]),
+    "pemp_nway_confusion_workspace_bytes": (c_size, [c_int] * 4),
+    "pemp_nway_confusion_f32": (c_int, [c_fp] * 6 + [c_size] + [c_int] * 6 + [c_fp]),
+    "pemp_nway_confusion_ragged_f32": (c_int, [c_fp, c_fp, c_fp, C.POINTER(TailItem), c_fp] + [c_int] * 4 + [c_fp] * 3 + [c_size, c_fp]),
     "pemp_cm_reduce_f32": (c_int, [c_fp, c_int, c_fp, c_fp, c_fp] + [c_int] * 7 + [c_fp]),
     "pemp_argmax_masks_f32": (c_int, [c_fp, c_fp, c_int, c_int, c_fp]),
     "pemp_cm_reduce_arg_f32": (c_int, [c_fp, c_int, c_fp, c_fp, c_fp, c_fp] + [c_int] * 7 + [c_fp]),

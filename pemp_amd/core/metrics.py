@@ -44,6 +44,38 @@ class FewShotMetric:
         return per_class, per_class.mean()
 
 
+class SemanticMetric:
+    """Semantic segmentation over the ``num_slots`` classes of a bank, from confusion tables (``ops.nway_confusion``):
+    ``conf[t, p]`` counts the pixels with target class t and predicted label p, 0 = background / no class, 1 + slot otherwise.
+    The tables are integers, so they add exactly in any order, on the device and across ranks."""
+
+    def __init__(self, num_slots):
+        self.num_slots = int(num_slots)
+        self.conf = np.zeros((self.num_slots + 1, self.num_slots + 1), np.int64)
+
+    def update(self, conf):
+        """Adds one table [K+1,K+1] or a stack of them [...,K+1,K+1] (numpy or a tensor on any device)."""
+        conf = np.asarray(conf.cpu() if hasattr(conf, "cpu") else conf)
+        if conf.shape[-2:] != self.conf.shape or not np.issubdtype(conf.dtype, np.integer):
+            raise ValueError(f"SemanticMetric: expected integer tables [...,{self.conf.shape[0]},{self.conf.shape[1]}], got "
+                             f"{conf.shape} {conf.dtype}")
+        self.conf += conf.reshape((-1,) + self.conf.shape).sum(axis=0).astype(np.int64)
+
+    def iou(self):
+        """Per-class IoU [K+1] (index 0: background): diag / (row + col - diag); nan for a class with an empty union."""
+        diag = np.diag(self.conf).astype(np.float64)
+        union = (self.conf.sum(axis=1) + self.conf.sum(axis=0)).astype(np.float64) - diag
+        return np.divide(diag, union, out=np.full(diag.shape, np.nan), where=union > 0)
+
+    def result(self):
+        """-> dict: ``iou`` [K+1], ``mIoU`` over the K classes, ``mIoU_bg`` with the background, ``pixAcc``.  A class with an
+        empty union is left out of the means; a mean over no class at all, or an accuracy over no pixel, is nan."""
+        iou = self.iou()
+        mean = lambda v: float(np.mean(v[~np.isnan(v)])) if (~np.isnan(v)).any() else float("nan")
+        total = int(self.conf.sum())
+        return dict(iou=iou, mIoU=mean(iou[1:]), mIoU_bg=mean(iou), pixAcc=float(np.trace(self.conf)) / total if total else float("nan"))
+
+
 class _Series:
     """Values appended one by one (``loss=[]``): mean / std over the collected array along ``axis``."""
 

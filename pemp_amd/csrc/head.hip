@@ -109,3 +109,21 @@ extern "C" int pemp_nway_tail_ragged_f32(const float* pred, const int64_t* targe
     return j8::pemp_nway_tail_ragged_f32(pred, target, want, items_host, items_dev, N, K, h, w, labels, margin, stats, ws,
                                          ws_bytes, stream);
 }
+
+extern "C" size_t pemp_nway_confusion_workspace_bytes(int N, int K, int Ho, int Wo) {
+    return j8::pemp_nway_confusion_workspace_bytes(N, K, Ho, Wo);
+}
+
+extern "C" int pemp_nway_confusion_f32(const float* pred, const int64_t* target, const int32_t* want, uint8_t* labels,
+                                       int64_t* conf, void* ws, size_t ws_bytes, int N, int K, int h, int w, int Ho, int Wo,
+                                       void* stream) {
+    return j8::pemp_nway_confusion_f32(pred, target, want, labels, conf, ws, ws_bytes, N, K, h, w, Ho, Wo, stream);
+}
+
+extern "C" int pemp_nway_confusion_ragged_f32(const float* pred, const int64_t* target, const int32_t* want,
+                                              const pemp_tail_item* items_host, const pemp_tail_item* items_dev, int N, int K,
+                                              int h, int w, uint8_t* labels, int64_t* conf, void* ws, size_t ws_bytes,
+                                              void* stream) {
+    return j8::pemp_nway_confusion_ragged_f32(pred, target, want, items_host, items_dev, N, K, h, w, labels, conf, ws, ws_bytes,
+                                              stream);
+}

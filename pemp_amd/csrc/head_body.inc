@@ -957,17 +957,18 @@ static inline int tail_blocks(int Ho, int Wo) {
     return nb < 1 ? 1 : (nb > 256 ? 256 : nb);
 }
 
-// Pixel i of one image of the N-way tail, shared like eval_tail_pixel.  pn: the image's K plane pairs; wk: the wanted class
-// (-1 without a target); target, labels, margin: at the image's first pixel (or null).
-__device__ __forceinline__ void nway_tail_pixel(const float* __restrict__ pn, const int64_t* __restrict__ target, int wk,
-                                                uint8_t* __restrict__ labels, float* __restrict__ margin, int i, int K, int h,
-                                                int w, int Ho, int Wo, TailAcc& a) {
+// The N-way decision of pixel i, the one place the rule exists (the label tails and the confusion tails call it): the
+// upsample of the K plane pairs pn, the claim test l1 > l0, the margin __fsub_rn(l1, l0) and the strict > that lets the lowest k
+// win equal margins.  -> the label (0: nobody claims, else 1 + k); bm: the winner's margin, top: the largest margin of all
+// classes, w0 / w1: class wk's own logits (wk = -1: left at 0).  What a caller does not read costs nothing after inlining.
+__device__ __forceinline__ int nway_decide(const float* __restrict__ pn, int wk, int i, int K, int h, int w, int Ho, int Wo,
+                                           float& bm, float& top, float& w0, float& w1) {
     const int hw = h * w;
     int Y = i / Wo, X = i - Y * Wo;
     Bilin by = bilin_exact(Y, h, Ho), bx = bilin_exact(X, w, Wo);
     int best = 0;                               // the label so far
-    float bm = 0.f, top = -INFINITY;            // its margin; the largest margin of all classes
-    float w0 = 0.f, w1 = 0.f;                   // the wanted class's own logits
+    bm = 0.f, top = -INFINITY;                  // its margin; the largest margin of all classes
+    w0 = 0.f, w1 = 0.f;                         // the wanted class's own logits
     const float* p = pn;
     for (int k = 0; k < K; ++k, p += 2 * hw) {
         float l0 = bilerp(p, w, by, bx), l1 = bilerp(p + hw, w, by, bx);
@@ -982,6 +983,16 @@ __device__ __forceinline__ void nway_tail_pixel(const float* __restrict__ pn, co
             w1 = l1;
         }
     }
+    return best;
+}
+
+// Pixel i of one image of the N-way tail, shared like eval_tail_pixel.  pn: the image's K plane pairs; wk: the wanted class
+// (-1 without a target); target, labels, margin: at the image's first pixel (or null).
+__device__ __forceinline__ void nway_tail_pixel(const float* __restrict__ pn, const int64_t* __restrict__ target, int wk,
+                                                uint8_t* __restrict__ labels, float* __restrict__ margin, int i, int K, int h,
+                                                int w, int Ho, int Wo, TailAcc& a) {
+    float bm, top, w0, w1;
+    const int best = nway_decide(pn, wk, i, K, h, w, Ho, Wo, bm, top, w0, w1);
     labels[i] = (uint8_t)best;
     if (margin) margin[i] = best ? bm : top;
     if (target) {
@@ -1042,8 +1053,8 @@ __global__ __launch_bounds__(256) void eval_tail_ragged_kernel(const float* __re
     tail_block_sums(v, part + ((size_t)it.part_off + blockIdx.x) * 8);
 }
 
-// (8 waves per SIMD asked for: left alone the descriptor's fields take the kernel to 70 VGPRs and 7 waves, 7 % slower than
-// nway_tail_kernel's 62 and 8 on equal sizes)
+// (8 waves per SIMD asked for: left alone the descriptor's fields took the kernel to 70 VGPRs and 7 waves, 7 % slower than
+// nway_tail_kernel's 8 on equal sizes; both are at 58 VGPRs since the decision moved into nway_decide)
 __global__ __launch_bounds__(256, 8) void nway_tail_ragged_kernel(const float* __restrict__ pred, const int64_t* __restrict__ target,
                                                                const int32_t* __restrict__ want,
                                                                const pemp_tail_item* __restrict__ items,
@@ -1072,6 +1083,76 @@ __global__ void tail_final_ragged_kernel(const double* __restrict__ part, const 
     const pemp_tail_item it = items[b];
     const double s = tail_final_sum(part + (size_t)it.part_off * 8, it.nblk, k, lane);
     if (lane == 0) stats[b * 8 + k] = s;
+}
+
+// N-way confusion tail: the label of nway_decide counted against a target, conf[t][p] of one image ([K+1][K+1] int64, zeroed
+// by the entry) += the block's pixels.  Block blk of nblk walks the image as the label tails do.  hist: (K+1)^2 uint32 in LDS
+// (at most 4096 bins = 16 KB).  On real data most pixels are background predicted as background, and 64 lanes adding to one LDS
+// address serialise: bin (0,0) is counted in a register per thread and folded in by a wave butterfly, only the other bins go
+// through LDS integer atomics.  The block's non-zero bins then go to conf with 64-bit integer atomic adds: integer sums are
+// exact in any order, so the table does not depend on the grid, the batch or the run.  lifted: target is the binary mask
+// 0 / 1 / 255 of class slot `want` (1 -> want + 1); otherwise it holds slot labels 0..K.  Every other value is ignored before it
+// can index the table.
+constexpr int CONF_MAX_K = 63;
+
+__device__ __forceinline__ void nway_confusion_image(const float* __restrict__ pn, const int64_t* __restrict__ target,
+                                                     bool lifted, int want, uint8_t* __restrict__ labels,
+                                                     unsigned long long* __restrict__ conf, uint32_t* hist, int blk, int nblk,
+                                                     int K, int h, int w, int Ho, int Wo) {
+    const int C = K + 1, bins = C * C, tid = threadIdx.x, npix = Ho * Wo;
+    for (int b = tid; b < bins; b += 256) hist[b] = 0;
+    __syncthreads();
+    uint32_t c00 = 0;
+    for (int i = blk * 256 + tid; i < npix; i += nblk * 256) {
+        float bm, top, w0, w1;
+        const int best = nway_decide(pn, -1, i, K, h, w, Ho, Wo, bm, top, w0, w1);
+        if (labels) labels[i] = (uint8_t)best;
+        int64_t t = target[i];
+        if (lifted) t = t == 1 ? (int64_t)want + 1 : (t == 0 ? 0 : -1);
+        if (t >= 0 && t <= K) {
+            const int bin = (int)t * C + best;
+            if (bin == 0)
+                ++c00;
+            else
+                atomicAdd(&hist[bin], 1u);
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) c00 += __shfl_xor(c00, o, 64);
+    if ((tid & 63) == 0 && c00) atomicAdd(&hist[0], c00);
+    __syncthreads();
+    for (int b = tid; b < bins; b += 256) {
+        const uint32_t v = hist[b];
+        if (v) atomicAdd(conf + b, (unsigned long long)v);
+    }
+}
+
+__global__ __launch_bounds__(256, 8) void nway_confusion_kernel(const float* __restrict__ pred, const int64_t* __restrict__ target,
+                                                                const int32_t* __restrict__ want, uint8_t* __restrict__ labels,
+                                                                unsigned long long* __restrict__ conf, int K, int h, int w,
+                                                                int Ho, int Wo) {
+    extern __shared__ uint32_t conf_hist[];
+    const int n = blockIdx.y;
+    const size_t at = (size_t)n * Ho * Wo;
+    nway_confusion_image(pred + (size_t)n * K * 2 * h * w, target + at, want != nullptr, want ? want[n] : 0,
+                         labels ? labels + at : nullptr, conf + (size_t)n * (K + 1) * (K + 1), conf_hist, blockIdx.x, gridDim.x,
+                         K, h, w, Ho, Wo);
+}
+
+// the ragged walk of nway_tail_ragged_kernel: image n's first nblk blocks, target and labels packed
+__global__ __launch_bounds__(256, 8) void nway_confusion_ragged_kernel(const float* __restrict__ pred,
+                                                                       const int64_t* __restrict__ target,
+                                                                       const int32_t* __restrict__ want,
+                                                                       const pemp_tail_item* __restrict__ items,
+                                                                       uint8_t* __restrict__ labels,
+                                                                       unsigned long long* __restrict__ conf, int K, int h,
+                                                                       int w) {
+    extern __shared__ uint32_t conf_hist[];
+    const int n = blockIdx.y;
+    const pemp_tail_item it = items[n];
+    if ((int)blockIdx.x >= it.nblk) return;
+    nway_confusion_image(pred + (size_t)n * K * 2 * h * w, target + it.pix_off, want != nullptr, want ? want[n] : 0,
+                         labels ? labels + it.pix_off : nullptr, conf + (size_t)n * (K + 1) * (K + 1), conf_hist, blockIdx.x,
+                         it.nblk, K, h, w, it.Ho, it.Wo);
 }
 
 }  // namespace PEMP_HEAD_NS
@@ -1389,6 +1470,54 @@ static int pemp_nway_tail_ragged_f32(const float* pred, const int64_t* target, c
         hipLaunchKernelGGL(tail_final_ragged_kernel, dim3(N, 8), dim3(64), 0, (hipStream_t)stream, (const double*)ws, items_dev,
                            stats);
     return launch_status("nway_tail_ragged");
+}
+
+// N-way confusion tails.  The blocks flush into conf with global integer atomics after a memset (no partial tables: at K = 63
+// those would be 4096 bins x 256 blocks x 8 B = 8 MB per image), so neither form needs a workspace: the planner returns 0 and
+// ws / ws_bytes are accepted and left alone.
+static size_t pemp_nway_confusion_workspace_bytes(int N, int K, int Ho, int Wo) {
+    (void)N, (void)K, (void)Ho, (void)Wo;
+    return 0;
+}
+
+static int nway_confusion_clear(int64_t* conf, int N, int K, hipStream_t st, const char* what) {
+    const hipError_t e = hipMemsetAsync(conf, 0, (size_t)N * (K + 1) * (K + 1) * sizeof(int64_t), st);
+    if (e != hipSuccess) {
+        set_error("%s: clearing conf: %s", what, hipGetErrorString(e));
+        return (int)e;
+    }
+    return 0;
+}
+
+static int pemp_nway_confusion_f32(const float* pred, const int64_t* target, const int32_t* want, uint8_t* labels, int64_t* conf,
+                                   void* ws, size_t ws_bytes, int N, int K, int h, int w, int Ho, int Wo, void* stream) {
+    (void)ws, (void)ws_bytes;
+    PEMP_REQUIRE(pred && target && conf, "nway_confusion: null pointer");
+    PEMP_REQUIRE(N > 0 && N <= 65535 && K > 0 && h > 0 && w > 0 && Ho > 0 && Wo > 0 &&
+                     (long long)Ho * Wo < (1LL << 31) - (1LL << 16) && (long long)h * w < (1LL << 29),
+                 "nway_confusion: bad dims");
+    PEMP_REQUIRE(K <= CONF_MAX_K, "nway_confusion: K <= 63 (the block's table of (K + 1)^2 counters is 16 KB of LDS at most)");
+    if (int rc = nway_confusion_clear(conf, N, K, (hipStream_t)stream, "nway_confusion")) return rc;
+    hipLaunchKernelGGL(nway_confusion_kernel, dim3(tail_blocks(Ho, Wo), N), dim3(256), (size_t)(K + 1) * (K + 1) * sizeof(uint32_t),
+                       (hipStream_t)stream, pred, target, want, labels, (unsigned long long*)conf, K, h, w, Ho, Wo);
+    return launch_status("nway_confusion");
+}
+
+static int pemp_nway_confusion_ragged_f32(const float* pred, const int64_t* target, const int32_t* want,
+                                          const pemp_tail_item* items_host, const pemp_tail_item* items_dev, int N, int K, int h,
+                                          int w, uint8_t* labels, int64_t* conf, void* ws, size_t ws_bytes, void* stream) {
+    (void)ws, (void)ws_bytes;
+    PEMP_REQUIRE(pred && target && items_host && items_dev && conf, "nway_confusion_ragged: null pointer");
+    PEMP_REQUIRE(N >= 1 && N <= 65535 && K > 0 && h > 0 && w > 0 && (long long)h * w < (1LL << 29),
+                 "nway_confusion_ragged: bad dims");
+    PEMP_REQUIRE(K <= CONF_MAX_K,
+                 "nway_confusion_ragged: K <= 63 (the block's table of (K + 1)^2 counters is 16 KB of LDS at most)");
+    const int nb = tail_ragged_check("nway_confusion_ragged", items_host, N, ~(size_t)0);      // the plan alone: no workspace
+    if (nb < 0) return -1;
+    if (int rc = nway_confusion_clear(conf, N, K, (hipStream_t)stream, "nway_confusion_ragged")) return rc;
+    hipLaunchKernelGGL(nway_confusion_ragged_kernel, dim3(nb, N), dim3(256), (size_t)(K + 1) * (K + 1) * sizeof(uint32_t),
+                       (hipStream_t)stream, pred, target, want, items_dev, labels, (unsigned long long*)conf, K, h, w);
+    return launch_status("nway_confusion_ragged");
 }
 
 }  // namespace PEMP_HEAD_NS

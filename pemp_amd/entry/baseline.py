@@ -59,6 +59,13 @@ def test_nway(_config, split, shot, exp_id, ckpt):
 
 
 @ex.command
+def test_semantic(_config, split, shot, exp_id, ckpt):
+    """``test_nway``'s rounds scored as a semantic segmentation over the split's classes (entry.pemp_stage1.SemanticEvaluator)."""
+    from .pemp_stage1 import run_test_semantic
+    return run_test_semantic(_config, NAME, ModelClass, split, shot, exp_id, ckpt)
+
+
+@ex.command
 def train(_config, split, shot, seed, loss, sigma, exp_id):
     """Baseline training procedure (entry/baseline.py:54-62,65-110): no gradient clipping; VGG-16 or ResNet-50 per net.backbone."""
     from .pemp_stage1 import run_training

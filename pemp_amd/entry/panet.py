@@ -116,6 +116,13 @@ def test_nway(_config, split, shot, exp_id, ckpt):
 
 
 @ex.command
+def test_semantic(_config, split, shot, exp_id, ckpt):
+    """``test_nway``'s rounds scored as a semantic segmentation over the split's classes (entry.pemp_stage1.SemanticEvaluator)."""
+    from .pemp_stage1 import run_test_semantic
+    return run_test_semantic(_config, NAME, ModelClass, split, shot, exp_id, ckpt)
+
+
+@ex.command
 def train(_config, split, shot, seed, loss, sigma, exp_id, loss_coef):
     """PANet training procedure (entry/panet.py:103-146): loss + loss_coef * align_loss, no gradient clipping."""
     from .pemp_stage1 import run_training

@@ -452,13 +452,8 @@ class NWayEvaluator(NWayMixin, BankEvaluator):
     """``BankEvaluator`` with every query against every enrolled class (``NWayMixin``)."""
 
 
-def run_test_bank(_config, name, model_class, split, shot, exp_id, ckpt, seed=None, evaluator=None, loss_label="Loss",
-                  command="test_bank", **load_kw):
-    """Body of the ``test_bank`` and ``test_nway`` commands: ``test`` with the enroll-once protocol (``BankEvaluator``).  Same
-    checkpoint lookup, same episode source (``data.base_dir`` or synthetic), same result string; no configuration key of its own.
-    ``model_class(logger)`` makes the model, ``load_kw`` goes to ``load_for_eval`` (PFENet's Wgen seed).  ``evaluator``: the
-    evaluator class (default ``BankEvaluator``), ``loss_label``: the name of the loss in the result line (RPMMs: ``Loss_p1``),
-    ``command``: the command's name in the message that asks for a split."""
+def _bank_eval_setup(_config, name, model_class, split, shot, exp_id, ckpt, seed, command, load_kw):
+    """The front of the bank commands: -> (logger, model on the GPU in eval mode, episode source, data config)."""
     import logging
     logging.basicConfig(level=logging.INFO, format="%(message)s")
     logger = logging.getLogger(name)
@@ -471,11 +466,95 @@ def run_test_bank(_config, name, model_class, split, shot, exp_id, ckpt, seed=No
     load_for_eval(model, _config, exp_id, ckpt, logger, **load_kw)
     model = model.cuda().eval()
     dcfg = _config["data"]
-    data = eval_episodes(dcfg, shot, split)
+    return logger, model, eval_episodes(dcfg, shot, split), dcfg
+
+
+def run_test_bank(_config, name, model_class, split, shot, exp_id, ckpt, seed=None, evaluator=None, loss_label="Loss",
+                  command="test_bank", **load_kw):
+    """Body of the ``test_bank`` and ``test_nway`` commands: ``test`` with the enroll-once protocol (``BankEvaluator``).  Same
+    checkpoint lookup, same episode source (``data.base_dir`` or synthetic), same result string; no configuration key of its own.
+    ``model_class(logger)`` makes the model, ``load_kw`` goes to ``load_for_eval`` (PFENet's Wgen seed).  ``evaluator``: the
+    evaluator class (default ``BankEvaluator``), ``loss_label``: the name of the loss in the result line (RPMMs: ``Loss_p1``),
+    ``command``: the command's name in the message that asks for a split."""
+    logger, model, data, dcfg = _bank_eval_setup(_config, name, model_class, split, shot, exp_id, ckpt, seed, command, load_kw)
     ev = (BankEvaluator if evaluator is None else evaluator)(model)
     loss, miou, biou = ev.start_eval_loop(data, num_classes(dcfg["dataset"]), split, _config["te"]["epochs"], logger,
                                           batch=dcfg["test_bs"], dataset_name=dcfg["dataset"])
     return f"{loss_label}: {loss:.4f}, mIoU: {np.mean(miou) * 100:.2f}, bIoU: {np.mean(biou) * 100:.2f}"
+
+
+class SemanticMixin(NWayMixin):
+    """``NWayMixin``'s enrolment and walk, scored as a semantic segmentation over the split's K classes: per step ONE ragged
+    confusion launch (``ops.nway_confusion_ragged`` with the queries' own slots as ``want``, no label map stored) whose tables
+    are summed over the images into one int64 [K+1,K+1] table on the device; per round one ``all_reduce(SUM)`` of that table
+    when a process group exists and one fetch, then ``SemanticMetric``.  The table is integer-valued, so the result does not
+    depend on the batch or the number of ranks.  No loss is reported.
+
+    An episode carries the mask of its own class only.  Where another enrolled class really is in the query image and claims
+    its pixels correctly, the episode's mask calls them background, and the claim counts against that class.  The figures
+    are therefore a lower bound on those that full multi-class ground truth would give; such ground truth goes through
+    ``model.segment_confusion`` with ``ops.slot_targets``."""
+
+    def test_step_batch(self, episodes):
+        """``episodes``: list of ((qry_img [1,1,3,H,W], bank slot), qry_msk).  -> the step's table int64 [K+1,K+1] on the GPU."""
+        qry = torch.cat([ep[0][0].to(self.device, non_blocking=True).flatten(0, 1) for ep in episodes])
+        want = [ep[0][1] for ep in episodes]
+        labels = [ep[1].view(-1, *ep[1].shape[-2:]) for ep in episodes]
+        seg = self.model.segment_graphed if self.use_graph else self.model.segment_lowres
+        with torch.no_grad(), ops.eval_splitk(ops.EVAL_SPLITK if self.splitk is None else self.splitk):
+            return ops.nway_confusion_ragged(seg(self.bank, qry)[0], labels, want=want, ws_cache=self._ws)[0].sum(dim=0)
+
+    def start_eval_loop(self, dataset, num_classes, split, te_epochs=5, logger=None, batch=1, dataset_name="PASCAL"):
+        """The rounds of ``Evaluator.start_eval_loop`` with the confusion table in place of the statistics rows.
+        -> (mIoU over the K classes, mIoU with the background, pixel accuracy), each the mean over the rounds."""
+        from ..core.metrics import SemanticMetric
+        self._labels = [int(c) for c in get_val_labels(split, dataset_name)]
+        self.model.eval()
+        dataset.reset_sampler()
+        world = dist.get_world_size() if dist.is_initialized() else 1
+        rank = dist.get_rank() if dist.is_initialized() else 0
+        k = len(self._labels)
+        table = torch.zeros((k + 1, k + 1), dtype=torch.int64, device=self.device)
+        self.round_tables, results = [], []
+        for epoch in range(1, te_epochs + 1):
+            dataset.sample_tasks()
+            table.zero_()
+            group = []
+            for inputs, qry_msk, _ in self._episodes(dataset, shard_indices(len(dataset), rank, world)):
+                group.append((inputs, qry_msk))
+                if len(group) >= batch:
+                    table += self.test_step_batch(group)
+                    group = []
+            if group:
+                table += self.test_step_batch(group)
+            if world > 1:
+                dist.all_reduce(table, op=dist.ReduceOp.SUM)            # the round's only collective
+            metric = SemanticMetric(k)
+            metric.update(table)                                        # the round's only fetch
+            res = metric.result()
+            self.round_tables.append(metric.conf.copy())
+            results.append(res)
+            if logger is not None and rank == 0:
+                per_class = "  ".join(f"{c}: {v * 100:5.2f}" for c, v in zip(["bg"] + self._labels, res["iou"]))
+                logger.info(f"[round {epoch}/{te_epochs}] mIoU_sem: {res['mIoU'] * 100:5.2f}  |  mIoU_sem+bg: {res['mIoU_bg'] * 100:5.2f}"
+                            f"  |  pixAcc: {res['pixAcc'] * 100:5.2f}  |  IoU {per_class}")
+        #: per-class IoU of every round, [te_epochs, K + 1] (index 0: background; nan: empty union)
+        self.round_iou = np.array([r["iou"] for r in results])
+        return tuple(float(np.mean([r[key] for r in results])) for key in ("mIoU", "mIoU_bg", "pixAcc"))
+
+
+class SemanticEvaluator(SemanticMixin, BankEvaluator):
+    """``BankEvaluator``'s enrolment with every query against every class, scored by the confusion table (``SemanticMixin``)."""
+
+
+def run_test_semantic(_config, name, model_class, split, shot, exp_id, ckpt, seed=None, evaluator=None, **load_kw):
+    """Body of the ``test_semantic`` commands: ``test_nway``'s protocol and configuration keys, scored as a semantic
+    segmentation over the split's classes (``SemanticEvaluator``; per-class IoU goes to the log)."""
+    logger, model, data, dcfg = _bank_eval_setup(_config, name, model_class, split, shot, exp_id, ckpt, seed, "test_semantic", load_kw)
+    ev = (SemanticEvaluator if evaluator is None else evaluator)(model)
+    miou, miou_bg, acc = ev.start_eval_loop(data, num_classes(dcfg["dataset"]), split, _config["te"]["epochs"], logger,
+                                            batch=dcfg["test_bs"], dataset_name=dcfg["dataset"])
+    return f"mIoU_sem: {miou * 100:.2f}, mIoU_sem+bg: {miou_bg * 100:.2f}, pixAcc: {acc * 100:.2f}"
 
 
 @ex.command
@@ -490,6 +569,14 @@ def test_nway(_config, split, shot, seed, exp_id, ckpt):
     """``python -m pemp_amd.entry.pemp_stage1 test_nway with split=0 exp_id=1``: ``test_bank`` with every query meeting every
     enrolled class (``NWayEvaluator``): the loss is ``test_bank``'s, mIoU and bIoU are those of the classes under competition."""
     return run_test_bank(_config, NAME, ModelClass, split, shot, exp_id, ckpt, seed, evaluator=NWayEvaluator, command="test_nway")
+
+
+@ex.command
+def test_semantic(_config, split, shot, seed, exp_id, ckpt):
+    """``python -m pemp_amd.entry.pemp_stage1 test_semantic with split=0 exp_id=1``: ``test_nway``'s rounds scored as a semantic
+    segmentation over the split's classes (``SemanticEvaluator``): mIoU over the classes, mIoU with the background and the pixel
+    accuracy, from one confusion table per round."""
+    return run_test_semantic(_config, NAME, ModelClass, split, shot, exp_id, ckpt, seed)
 
 
 @ex.command

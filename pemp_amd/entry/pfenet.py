@@ -83,6 +83,16 @@ def test_nway(_config, split, shot, query, exp_id, ckpt):
                          command="test_nway", wgen_seed=WGEN_SEED)
 
 
+@ex.command
+def test_semantic(_config, split, shot, query, exp_id, ckpt):
+    """``python -m pemp_amd.entry.pfenet test_semantic with split=0 ckpt=wgen [shot=5]``: ``test_nway``'s rounds scored as a
+    semantic segmentation over the split's classes (entry.pemp_stage1.SemanticEvaluator)."""
+    from .pemp_stage1 import run_test_semantic
+    if query != 1:
+        raise ValueError("PFENet takes exactly one query per episode (query=1)")
+    return run_test_semantic(_config, NAME, lambda logger: ModelClass(shot, logger), split, shot, exp_id, ckpt, wgen_seed=WGEN_SEED)
+
+
 def head_train_batches(trainer, dcfg, shot, split, rank, steps_per_epoch, device):
     """-> ``batches(epoch)`` for ``TrainingLoop``: synthetic episodes with the query label at the input size (the reference resizes
     a training label with its image)."""

@@ -24,7 +24,7 @@ from ..train_rpmms import RPMMsTrainer
 from .pemp_stage1 import INGREDIENTS, SyntheticEpisodes, eval_episodes, get_val_labels, num_classes  # noqa: F401
 from .pemp_stage1 import BankEvaluator as _BankEvaluator
 from .pemp_stage1 import Evaluator as _Evaluator
-from .pemp_stage1 import NWayMixin
+from .pemp_stage1 import NWayMixin, SemanticMixin
 
 NAME = "PEMP"
 ex = Experiment(name=NAME, ingredients=[net_ingredient] + INGREDIENTS[1:])      # RPMMs' own net ingredient; data, tr, te, g, d
@@ -135,6 +135,24 @@ def test_nway(_config, split, shot, query, exp_id, ckpt, seed):
         raise ValueError("RPMMs is 1-shot with one query per episode (shot=1 query=1), as the reference is (rpmms.py:129, 266-267)")
     return run_test_bank(_config, NAME, ModelClass, split, shot, exp_id, ckpt, seed, evaluator=NWayEvaluator, loss_label="Loss_p1",
                          command="test_nway", wgen_seed=WGEN_SEED)
+
+
+class SemanticEvaluator(SemanticMixin, BankEvaluator):
+    """The semantic scoring of every query against every enrolled class (entry.pemp_stage1.SemanticMixin) over this entry's
+    ``BankEvaluator``: the initial mu is drawn before each enrolment as there."""
+
+
+@ex.command
+def test_semantic(_config, split, shot, query, exp_id, ckpt, seed):
+    """``python -m pemp_amd.entry.rpmms test_semantic with split=0 ckpt=wgen``: ``test_nway``'s rounds scored as a semantic
+    segmentation over the split's classes: mIoU over the classes, mIoU with the background and the pixel accuracy."""
+    from .pemp_stage1 import run_test_semantic
+    if split < 0:
+        raise ValueError("Argument `split` is required! For example: `python -m pemp_amd.entry.rpmms test_semantic with split=0`")
+    if shot != 1 or query != 1:
+        raise ValueError("RPMMs is 1-shot with one query per episode (shot=1 query=1), as the reference is (rpmms.py:129, 266-267)")
+    return run_test_semantic(_config, NAME, ModelClass, split, shot, exp_id, ckpt, seed, evaluator=SemanticEvaluator,
+                             wgen_seed=WGEN_SEED)
 
 
 def head_train_batches(trainer, dcfg, shot, split, rank, steps_per_epoch, device):

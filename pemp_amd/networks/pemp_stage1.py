@@ -358,6 +358,35 @@ class _HeadMixin:
         labels, margin, _ = ops.nway_tail(pred, out_shape, want_margin=want_margin, ws_cache=self._engine_for(qry_img.device)["arena"].ws)
         return (labels, margin) if want_margin else labels
 
+    def segment_confusion(self, bank, qry_img, target, want=None, graphed=False, want_labels=False):
+        """``segment_labels`` scored as a semantic segmentation: ``segment_lowres`` without an index (``graphed``:
+        ``segment_graphed``) and ONE confusion launch (``ops.nway_confusion``) that decides every pixel as ``segment_labels``
+        does and counts it against ``target``.  -> (conf int64 [N,K+1,K+1], labels | None): ``conf[n, t, p]`` is the number
+        of pixels of query n with target class t and label p, 0 for no class and 1 + slot otherwise
+        (``core.metrics.SemanticMetric`` turns the table into per-class IoU).  ``target``: one int64 tensor [N,Ho,Wo], or a
+        list of N int64 tensors with their own sizes (one ragged launch); it holds slot labels 0..K with 255 ignored
+        (``ops.slot_targets`` maps dataset class ids), or with ``want`` (N slots) the binary mask 0 / 1 / 255 of each query's
+        own class.  ``want_labels``: also the label maps, ``segment_labels``'s bit for bit.  At most 63 classes."""
+        self._segment_args(bank, qry_img, None, False, "segment_confusion")
+        if len(bank) > ops.CONFUSION_MAX_K:
+            raise ValueError(f"segment_confusion: the bank holds {len(bank)} classes; the confusion tail counts at most "
+                             f"{ops.CONFUSION_MAX_K}")
+        ragged = not isinstance(target, torch.Tensor)
+        n = qry_img.shape[0]
+        if ragged:
+            target = list(target)
+            if len(target) != n:
+                raise ValueError(f"segment_confusion: {len(target)} targets for {n} queries")
+        elif target.dim() != 3 or target.shape[0] != n or target.dtype != torch.int64:
+            raise ValueError(f"segment_confusion: target must be int64 [{n},Ho,Wo] or a list of {n} int64 maps, got "
+                             f"{tuple(target.shape)} {target.dtype}")
+        if want is not None and not (isinstance(want, torch.Tensor) and want.device.type != "cpu"):
+            want = ops.bank_index(want, n, len(bank))                                           # checked on the host
+        pred, _ = (self.segment_graphed if graphed else self.segment_lowres)(bank, qry_img)
+        if ragged:
+            return ops.nway_confusion_ragged(pred, target, want=want, want_labels=want_labels)
+        return ops.nway_confusion(pred, target.to(pred.device, non_blocking=True).contiguous(), want=want, want_labels=want_labels)
+
 
 class PEMPStage1(_HeadMixin, backbones.BaseModel):
     """Stage 1 of the Prior-Enhanced network with Meta-Prototypes (reference class of the same name)."""

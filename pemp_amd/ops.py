@@ -1396,6 +1396,91 @@ def nway_tail_ragged(pred, sizes=None, targets=None, want=None, want_margin=Fals
     return _ragged_views(labels, hw), (_ragged_views(margin, hw) if want_margin else None), stats
 
 
+#: the N-way confusion tails count in (K + 1)^2 <= 4096 bins of LDS per block
+CONFUSION_MAX_K = 63
+
+
+def _confusion_args(what, pred, want):
+    """The checks both confusion wrappers share, all on the host: -> (n, k, h, w, want as a host int32 tensor from
+    ``bank_index``, a checked device tensor, or None)."""
+    if pred.dim() != 5 or pred.dtype != torch.float32 or not pred.is_contiguous() or pred.shape[2] != 2 or min(pred.shape) < 1:
+        raise ValueError(f"{what}: pred must be contiguous fp32 [N,K,2,h,w], got {tuple(pred.shape)} {pred.dtype}")
+    n, k, _, h, w = pred.shape
+    if k > CONFUSION_MAX_K:
+        raise ValueError(f"{what}: K = {k}: a block counts in (K + 1)^2 <= 4096 bins, so K <= {CONFUSION_MAX_K}")
+    if want is not None:
+        if isinstance(want, torch.Tensor) and want.device.type != "cpu":
+            if want.dtype != torch.int32 or tuple(want.shape) != (n,) or not want.is_contiguous():
+                raise ValueError(f"{what}: a device want must be contiguous int32 [{n}]")
+        else:
+            want = bank_index(want, n, k)
+    return n, k, h, w, want
+
+
+def nway_confusion(pred, target, want=None, want_labels=False, ws_cache=None):
+    """The N-way label map of ``nway_tail`` counted against a target in one launch: pred fp32 [N,K,2,h,w], target int64
+    [N,Ho,Wo] -> (conf int64 [N,K+1,K+1], labels uint8 [N,Ho,Wo] | None).  ``conf[n, t, p]`` is the number of counted pixels of
+    image n with target class t and label p (0: no class, 1 + slot otherwise).  ``want`` None: the target holds slot labels
+    0..K (``slot_targets`` makes them from dataset class ids).  ``want`` (``nway_tail``'s: a Python sequence or a CPU tensor,
+    checked here, or a device int32 [N]): the target is the binary mask 0 / 1 / 255 of the query's own class, 1 standing for
+    slot ``want[n]``.  255 and every other value that is no class of the table is ignored (the values are not checked here:
+    that would need a synchronisation).  Without ``want_labels`` nothing is written per pixel; with it the labels are
+    ``nway_tail``'s bit for bit.  K <= 63.  The counts are integers: exact, and identical from run to run.  ``ws_cache`` is
+    taken as the other tails take it and not used: this tail has no workspace."""
+    lib = _lib.load()
+    n, k, h, w, want = _confusion_args("nway_confusion", pred, want)
+    if not isinstance(target, torch.Tensor) or target.dtype != torch.int64 or not target.is_contiguous() or target.dim() != 3 \
+            or target.shape[0] != n or min(target.shape) < 1:
+        raise ValueError(f"nway_confusion: target must be contiguous int64 [{n},Ho,Wo]")
+    ho, wo = (int(v) for v in target.shape[-2:])
+    _chk_dev(pred, target)
+    if want is not None:
+        want = want.to(pred.device, non_blocking=True)
+    conf = torch.empty((n, k + 1, k + 1), dtype=torch.int64, device=pred.device)
+    labels = torch.empty((n, ho, wo), dtype=torch.uint8, device=pred.device) if want_labels else None
+    # no workspace: the blocks flush into conf with integer atomics (pemp_nway_confusion_workspace_bytes is 0 at every size)
+    _lib.check(lib.pemp_nway_confusion_f32(_p(pred), _p(target), _p(want), _p(labels), _p(conf), _p(None), 0, n, k, h, w, ho, wo,
+                                           _stream()), "nway_confusion")
+    return conf, labels
+
+
+def nway_confusion_ragged(pred, targets, want=None, want_labels=False, ws_cache=None, views=True):
+    """``nway_confusion`` for a batch whose images each have their own size, in ONE launch: pred fp32 [N,K,2,h,w]; ``targets`` a
+    list of N int64 tensors [Ho_i,Wo_i] or [1,Ho_i,Wo_i] on the host or the device (``eval_tail_ragged``'s); ``want`` as in
+    ``nway_confusion``.  -> (conf int64 [N,K+1,K+1], labels | None): with ``want_labels`` a list of N uint8 [Ho_i,Wo_i] views
+    into one packed buffer (``views`` off: the packed buffer itself).  Per image the table and the labels are the fixed-size
+    call's on that image alone."""
+    n, k, h, w, want = _confusion_args("nway_confusion_ragged", pred, want)
+    if targets is None:
+        raise ValueError("nway_confusion_ragged: targets are needed (a confusion table counts against them)")
+    items, items_dev, hw, offs, target, _ = _ragged_plan("nway_confusion_ragged", n, None, targets, pred.device)
+    if want is not None:
+        want = want.to(pred.device, non_blocking=True)
+    lib = _lib.load()
+    conf = torch.empty((n, k + 1, k + 1), dtype=torch.int64, device=pred.device)
+    labels = torch.empty(offs[-1], dtype=torch.uint8, device=pred.device) if want_labels else None
+    _lib.check(lib.pemp_nway_confusion_ragged_f32(_p(pred), _p(target), _p(want), items, _p(items_dev), n, k, h, w, _p(labels),
+                                                  _p(conf), _p(None), 0, _stream()), "nway_confusion_ragged")
+    if labels is None or not views:
+        return conf, labels
+    return conf, _ragged_views(labels, hw)
+
+
+def slot_targets(target_ids, bank_labels):
+    """Ground truth in dataset class ids -> the slot labels ``nway_confusion`` counts against: an integer tensor of ids in
+    0..255 (any shape, any device) through a 256-entry table -> int64 of the same shape; the id ``bank_labels[s]`` becomes
+    ``s + 1``, an id the bank does not hold becomes 0 (background) and 255 stays 255 (ignored).  A plain gather, no kernel."""
+    ids = [int(v) for v in bank_labels]
+    if any(v != b for v, b in zip(ids, bank_labels)) or any(not 1 <= v <= 254 for v in ids) or len(set(ids)) != len(ids):
+        raise ValueError(f"slot_targets: bank_labels must be distinct class ids in 1..254, got {list(bank_labels)}")
+    if not isinstance(target_ids, torch.Tensor) or target_ids.dtype not in (torch.uint8, torch.int16, torch.int32, torch.int64):
+        raise ValueError("slot_targets: target_ids must be a uint8, int16, int32 or int64 tensor of ids in 0..255")
+    table = torch.zeros(256, dtype=torch.int64)
+    table[torch.tensor(ids, dtype=torch.int64)] = torch.arange(1, len(ids) + 1)
+    table[255] = 255
+    return table.to(target_ids.device)[target_ids.long()]
+
+
 #: PEMP_RAGGED_TAIL=0 withholds the ragged tails from the evaluators: ``tail_rows`` then makes one fixed-size launch pair per
 #: distinct label size (A/B switch; scratch/ragged_tail_bench.py measures both)
 RAGGED_TAIL = os.environ.get("PEMP_RAGGED_TAIL", "1") != "0"
